@@ -17,14 +17,23 @@ collective; weak scaling by default (--batch per GPU), strong scaling with
 only collectives.  ``--gpus N`` without a torchrun environment starts the N
 ranks itself (dist.launch_if_needed); under torchrun, WORLD_SIZE must equal N.
 
-Besides the headline line (exact mode), a single-GPU run reports, outside the
-timed region: the same batch at the reference's OSQP settings
-(``reference_settings``), the BASELINE config-2 batch of 4 096
-(``batch_4096``), and the latency of the reference's per-cycle call — one
-synchronous QPIKCubic through the host entry (``latency_b1``, p50 / p99).
+A plain run does only what the headline line (exact mode) needs: set-up,
+warm-up, the timed steps, the result line.  ``--dump-outputs DIR`` also writes
+what the last timed step returned (``qdot``, ``status``, ``iters``) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output
+for output.
+
+With ``--full`` a run also reports, outside the timed region: the counted
+FP64 operations per solve (``roofline.fp64_algorithmic``), the CPU baseline
+(``cpu_baseline``) and, on a single GPU, the same batch at the reference's
+OSQP settings (``reference_settings``), the BASELINE config-2 batch of 4 096
+(``batch_4096``), the latency of the reference's per-cycle call — one
+synchronous QPIKCubic through the host entry (``latency_b1``, p50 / p99) —
+and the latency roof.  ``--no-extras`` / ``--no-cpu-baseline`` take single
+legs out of a ``--full`` run.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--robot fr3] [--batch B | --global-batch G]
-                    [--solver exact|osqp_default] [--no-extras] [--no-cpu-baseline]
+                    [--solver exact|osqp_default] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline]]
 """
 import argparse
 import json
@@ -202,6 +211,27 @@ def timed_steps(torch, step, steps, warmup):
     return (time.perf_counter() - t0) / steps
 
 
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(path, tensors, rank=0, world=1):
+    """--dump-outputs: what the last timed step handed its caller, one
+    float64 <name>.npy per array (instances along the last axis) under
+    ``path``; every rank of a multi-GPU job writes <name>.rank<r>.npy.  Past
+    64 MB in all (per job), the same fixed, seeded sample of the instances is
+    kept of every array."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float64) for k, t in tensors.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    limit = DUMP_LIMIT_BYTES // world
+    if total > limit:
+        n = next(iter(arrays.values())).shape[-1]
+        idx = np.sort(np.random.default_rng(20250101).choice(n, size=max(1, n * limit // total), replace=False))
+        arrays = {k: np.ascontiguousarray(a[..., idx]) for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(path, "%s%s.npy" % (k, ".rank%d" % rank if world > 1 else "")), a)
+
+
 def iter_stats(iters, status):
     it = iters.cpu().numpy()
     return {"non_solved": int((status != 1).sum().item()), "admm_iters_mean": float(it.mean()),
@@ -364,8 +394,15 @@ def main():
     ap.add_argument("--global-batch", type=int, default=None, help="fixed total instances (strong scaling)")
     ap.add_argument("--solver", default="exact", choices=("exact", "osqp_default"),
                     help="exact: certified optimum (parity contract); osqp_default: the reference's OSQP settings")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip reference_settings / batch_4096 / latency_b1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure, outside the timed steps: the counted FP64 operations per solve, the CPU "
+                         "baseline and the single-GPU extras (reference_settings / batch_4096 / latency_b1 / "
+                         "latency_cycle / latency roof)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (qdot, status, iters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip reference_settings / batch_4096 / latency_b1")
     ap.add_argument("--chunks", type=int, default=4, help="concurrent sub-batches per call")
     ap.add_argument("--task-stage", type=int, default=0, choices=(0, 1, 2),
                     help="0 wave-per-instance task kernel (default), 1 lane stage + side-stream hand-backs, "
@@ -374,6 +411,8 @@ def main():
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="study: no per-kernel HIP events in the timed region (roofline kernel times then null)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rc = ddist.launch_if_needed(args.gpus, os.path.abspath(__file__), sys.argv[1:])
     if rc is not None:          # this process launched the ranks; it never touched the GPU
@@ -439,6 +478,8 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     wall_local = wall
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"qdot": out, "status": status, "iters": iters}, rank, world)
     step_event_ms = ev0.elapsed_time(ev1) / args.steps   # HIP events on the launch stream
     tw, tk, tq, nc = C.c_double(), C.c_double(), C.c_double(), C.c_int()
     _capi.check(_capi.lib().drc_debug_kernel_times(handle, C.byref(tw), C.byref(tk), C.byref(tq), C.byref(nc)))
@@ -476,8 +517,6 @@ def main():
         achieved = per_launch_bytes / (kernel_ms * 1e-3) / 1e9
         # counter summaries are used only when measured on this very build
         traffic = load_profile("pmc_traffic_%s.json" % robot, robot, B, build)
-        alg = algorithmic_flops(robot, args.solver, q, qd, xt, xdt)
-        fl = alg["flops_per_solve"] * B / (kernel_ms * 1e-3) / 1e12
         roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic.get("hbm_bytes_per_step") if traffic else None,
                 "traffic_source": ("profiles/pmc_traffic_%s.json (build %s)" % (robot, build)) if traffic else
@@ -488,9 +527,13 @@ def main():
                            % args.chunks),
                 "bytes_per_solve": bps, "bytes_per_launch": per_launch_bytes,
                 "kernel_ms": kernel_ms, "task_kernel_ms_sum": task_ms, "qp_kernel_ms_sum": qp_ms,
-                "step_event_ms": step_event_ms,
-                "fp64_algorithmic": dict(alg, achieved_tflops=fl, peak_tflops=FP64_VECTOR_PEAK_TFS,
-                                         frac=fl / FP64_VECTOR_PEAK_TFS)}
+                "step_event_ms": step_event_ms}
+        alg = None
+        if args.full:   # the counting build of the oracle on a sample of the batch (host, one thread)
+            alg = algorithmic_flops(robot, args.solver, q, qd, xt, xdt)
+            fl = alg["flops_per_solve"] * B / (kernel_ms * 1e-3) / 1e12
+            roof["fp64_algorithmic"] = dict(alg, achieved_tflops=fl, peak_tflops=FP64_VECTOR_PEAK_TFS,
+                                            frac=fl / FP64_VECTOR_PEAK_TFS)
         valu = load_profile("valu_counters_%s.json" % robot, robot, B, build)
         if valu:   # counter-based FP64 work per call (tools/valu_summary.py over rocprofv3 --pmc passes)
             f = valu["fp64_flops_per_step"]
@@ -502,7 +545,8 @@ def main():
                                  "executed_frac": issued * eff / FP64_VECTOR_PEAK_TFS,
                                  "fp64_flops_issued_per_step": f, "lane_efficiency": eff,
                                  "executed_flops_per_solve": f * eff / B,
-                                 "algorithmic_over_executed": alg["flops_per_solve"] / max(f * eff / B, 1e-30),
+                                 "algorithmic_over_executed": alg["flops_per_solve"] / max(f * eff / B, 1e-30)
+                                 if alg else None,
                                  "note": "issued counts 64 lanes per FP64 instruction; executed = issued x lane "
                                          "efficiency (active lanes); neither is algorithmic work",
                                  "source": "profiles/valu_counters_%s.json (build %s)" % (robot, build)}
@@ -527,9 +571,9 @@ def main():
             "non_solved": int(n_bad), "admm_iters_mean": it_mean,
         }
         line.update(whole_job(ranks, tier_keys, backend))
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             extras(torch, args, rd, mod, robot, link, q, qd, xt, xdt, dq, dqd, dxt, dxdt, line)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(robot, q, qd, xt, xdt)
         print(json.dumps(line), flush=True)
     if world > 1:

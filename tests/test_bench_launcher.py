@@ -90,6 +90,32 @@ def test_algorithmic_flop_count():
     assert a["flops_per_solve"] < 0.5 * a["dense_flops_per_solve"]
 
 
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 <name>.npy per array, whole while the dump
+    fits its byte limit; past it, the same seeded instances of every array, the
+    same from run to run; every rank of a multi-GPU job writes its own files."""
+    import numpy as np
+    import torch
+    import bench
+    out = torch.arange(7 * 50, dtype=torch.float64).reshape(7, 50)
+    st = torch.arange(50, dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"qdot": out, "status": st})
+    a = np.load(tmp_path / "a" / "qdot.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, out.numpy())
+    s = np.load(tmp_path / "a" / "status.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, np.arange(50.0))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 8 * 20)      # room for 20 of the 50 instances
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"qdot": out, "status": st})
+    b, sb = np.load(tmp_path / "b" / "qdot.npy"), np.load(tmp_path / "b" / "status.npy")
+    assert b.shape == (7, 20) and sb.shape == (20,) and b.nbytes + sb.nbytes <= 8 * 8 * 20
+    idx = sb.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(b, out.numpy()[:, idx])
+    assert np.array_equal(b, np.load(tmp_path / "c" / "qdot.npy"))
+    bench.dump_outputs(str(tmp_path / "r"), {"qdot": out}, rank=1, world=2)
+    assert np.load(tmp_path / "r" / "qdot.rank1.npy").shape == (7, 11)   # half the limit: 1 280 // 2 // 56 instances
+
+
 def test_valu_issue_roof():
     """roofline.valu_issue_roof: SIMDs x clock over the counted issue cycles,
     scaled by the job's GPUs, and absent without a count."""

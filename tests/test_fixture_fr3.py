@@ -1,23 +1,21 @@
 """Pins the one artefact the reference holds for the hot path: its FR3 model
-(/root/reference/examples/robots/fr3/fr3.{urdf,srdf}).  The bundled fixture
+(examples/robots/fr3/fr3.{urdf,srdf} of the reference, stored unchanged under
+tests/golden/reference_fr3/).  The bundled fixture
 (dyros_robot_controller_amd/robots/fr3, re-serialised by tools/gen_robots.py)
 must describe the same robot: joint tree, placements, axes, limits,
 inertias, the 35 collision primitives and the 180 active pairs that
 Manipulator::RobotData builds (src/manipulator/robot_data.cpp:21-62).  Both
-files go through the same parser (oracle/pyref_model.py).  Skipped where the
-reference tree is absent (the GPU box)."""
+files go through the same parser (oracle/pyref_model.py)."""
 import os
 
 import numpy as np
-import pytest
 
 import pyref_model
 from dyros_robot_controller_amd import robot_path
 
-REF = "/root/reference/examples/robots/fr3"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_fr3")
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "fr3.urdf")), reason="reference tree absent")
 def test_bundled_fr3_equals_reference_model():
     ref = pyref_model.load_urdf(os.path.join(REF, "fr3.urdf"), os.path.join(REF, "fr3.srdf"))
     ours = pyref_model.load_urdf(robot_path("fr3"), robot_path("fr3", "srdf"))

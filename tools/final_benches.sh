@@ -10,7 +10,7 @@ OUT=gpurun_out/final_$TAG
 mkdir -p $OUT
 run() {
   local name=$1; shift
-  timeout -k 10 300 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err
+  timeout -k 10 300 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err
   echo "$name: $(cut -c1-160 $OUT/$name.json)"
 }
 run fr3

@@ -17,5 +17,7 @@ for r in $ROBOTS; do
   timeout -k 10 900 bash tools/profile_round.sh ${TAG}_$r --robot $r > gpurun_out/final_${TAG}_$r.log 2>&1 || { tail -5 gpurun_out/final_${TAG}_$r.log; exit 1; }
   echo "$r: $(grep -m1 '^{' gpurun_out/prof_${TAG}_$r/bench.json | cut -c1-200)"
 done
-timeout -k 10 300 python3 bench.py --batch 4096 > gpurun_out/final_${TAG}_fr3_b4096.json 2> gpurun_out/final_${TAG}_fr3_b4096.err || exit 1
-echo "fr3 B=4096: $(cut -c1-200 gpurun_out/final_${TAG}_fr3_b4096.json)"
+OUT=${DRC_BENCH_OUT:-bench_out}   # the B = 4 096 line lands here
+mkdir -p $OUT
+timeout -k 10 300 python3 bench.py --full --batch 4096 > $OUT/final_${TAG}_fr3_b4096.json 2> $OUT/final_${TAG}_fr3_b4096.err || exit 1
+echo "fr3 B=4096: $(cut -c1-200 $OUT/final_${TAG}_fr3_b4096.json)"

@@ -10,9 +10,11 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 rc=$?
 tail -3 gpurun_out/gputest_$TAG.log
 [ $rc -eq 0 ] || exit $rc
+OUT=${DRC_BENCH_OUT:-bench_out}   # the bench lines land here
+mkdir -p $OUT
 for r in "$@"; do
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --robot $r > gpurun_out/bench_${TAG}_$r.json 2> gpurun_out/bench_${TAG}_$r.err || exit 1
-  python3 - gpurun_out/bench_${TAG}_$r.json <<'PY'
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --robot $r > $OUT/bench_${TAG}_$r.json 2> $OUT/bench_${TAG}_$r.err || exit 1
+  python3 - $OUT/bench_${TAG}_$r.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); ro = d["roofline"]
 print(d["config"]["robot"], "%.3fM" % (d["value"] / 1e6), "ms", round(d["ms_per_step"], 3), "task",

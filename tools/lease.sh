@@ -5,8 +5,8 @@
 #   test[:<k expr>]            pytest -m gpu [-k expr, commas become spaces] (gpurun_out/gputest_<tag>.log)
 #   smoke                      __graft_entry__.smoke()
 #   bench:<robot>[,<robot>]    one bench line per robot, no CPU baseline (tools/gpu_check.sh's summary)
-#   line[:<args>]              the default bench line (with CPU baseline), extra bench.py args after ':'
-#                              (commas become spaces), into gpurun_out/line_<tag>.json
+#   line[:<args>]              the --full bench line (with CPU baseline), extra bench.py args after ':'
+#                              (commas become spaces), into $DRC_BENCH_OUT/line_<tag>.json (default bench_out/)
 #   ab:<lib>,<lib>:<robot>,<robot>[:reps]   library A/B (tools/ab_bench.sh)
 #   env:<E=V+E2=V>,base:<robot>,..[:reps]   environment A/B (tools/env_ab.sh; '+' joins variables)
 #   bits:<lib>,<lib>           bit-for-bit comparison of two builds on all five robots (tools/lib_bits.py)
@@ -21,6 +21,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $ROOT
 TAG=$1; shift
 mkdir -p gpurun_out
+OUT=${DRC_BENCH_OUT:-bench_out}   # the bench and line steps' lines land here
+mkdir -p $OUT
 summ() {
   python3 - "$1" <<'PY'
 import json, sys
@@ -49,14 +51,14 @@ for step in "$@"; do
       tail -2 gpurun_out/smoke_$TAG.log ;;
     bench)
       for r in ${rest//,/ }; do
-        timeout -k 10 300 python3 bench.py --no-cpu-baseline --robot $r > gpurun_out/bench_${TAG}_$r.json \
-          2> gpurun_out/bench_${TAG}_$r.err || { tail -5 gpurun_out/bench_${TAG}_$r.err; exit 1; }
-        summ gpurun_out/bench_${TAG}_$r.json
+        timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --robot $r > $OUT/bench_${TAG}_$r.json \
+          2> $OUT/bench_${TAG}_$r.err || { tail -5 $OUT/bench_${TAG}_$r.err; exit 1; }
+        summ $OUT/bench_${TAG}_$r.json
       done ;;
     line)
-      timeout -k 10 400 python3 bench.py ${rest//,/ } > gpurun_out/line_$TAG.json 2> gpurun_out/line_$TAG.err \
-        || { tail -5 gpurun_out/line_$TAG.err; exit 1; }
-      summ gpurun_out/line_$TAG.json ;;
+      timeout -k 10 400 python3 bench.py --full ${rest//,/ } > $OUT/line_$TAG.json 2> $OUT/line_$TAG.err \
+        || { tail -5 $OUT/line_$TAG.err; exit 1; }
+      summ $OUT/line_$TAG.json ;;
     ab)
       IFS=: read -r libs robots reps <<< "$rest"
       timeout -k 10 900 bash tools/ab_bench.sh $TAG "${libs//,/ }" "${robots//,/ }" ${reps:-2} || exit 1 ;;

@@ -11,7 +11,7 @@ ARGS="$@"
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $ROOT
-timeout -k 10 420 python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 420 python3 bench.py --full $ARGS > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 cd /tmp
 export TMPDIR=/tmp
