@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "drc_mobile_fk_jacobian", "drc_mobile_ik_jacobian",
     "drc_default_qpik_params", "drc_qpik_batch", "drc_qpik_stages_batch", "drc_debug_kernel_timing", "drc_debug_lds_plan",
     "drc_debug_host_timeline", "drc_debug_waves", "drc_debug_qpik_stamps",
-    "drc_debug_kernel_times", "drc_debug_instance_order", "drc_set_concurrency", "drc_set_fusion", "drc_model_release_stream", "drc_debug_lane_stage", "drc_qpik_host", "drc_qpik_stages_host",
+    "drc_debug_kernel_times", "drc_debug_instance_order", "drc_set_concurrency", "drc_set_fusion", "drc_model_release_stream", "drc_debug_lane_stage", "drc_debug_eqp_small_cap", "drc_qpik_host", "drc_qpik_stages_host",
     "drc_dynamics_batch", "drc_dynamics_host", "drc_joint_torque_step_batch", "drc_joint_torque_step_host",
     "drc_default_qpid_params", "drc_qpid_batch", "drc_qpid_stages_batch", "drc_qpid_host",
     "drc_qpid_stages_host", "drc_clik_batch", "drc_osf_batch", "drc_closed_form_host",
@@ -152,6 +152,8 @@ def _load():
         lib.drc_debug_lds_plan.argtypes = [vp, C.POINTER(QPIKParams), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.drc_debug_kernel_times.argtypes = [vp, dp, dp, dp, ip]
     lib.drc_debug_lane_stage.argtypes = [vp, C.c_int]
+    if hasattr(lib, "drc_debug_eqp_small_cap"):  # absent from older A/B builds
+        lib.drc_debug_eqp_small_cap.argtypes = [vp, C.c_int]
     lib.drc_set_concurrency.argtypes = [vp, C.c_int]
     lib.drc_model_release_stream.argtypes = [vp, vp]
     lib.drc_set_fusion.argtypes = [vp, C.c_int]

@@ -81,6 +81,7 @@ struct drc_model_impl {
   Lanes ln;
   int timing = 0;  // drc_debug_kernel_timing: HIP events around each launch
   int lane_stage = 0;  // drc_debug_lane_stage: 0 off, 1 lane stage + side-stream hard path, 2 + serial hard path, 3 auto
+  int eqp_small_cap = -1;  // drc_debug_eqp_small_cap: -1 the compiled tiers, 0 general EQP only, k small EQP for N <= k
   // timed calls: {caller-stream start, caller-stream end, per chunk: task start, task end, qp end}
   // timed calls: {call start, call end, task start, task end, QP end of the
   // sub-batch on the caller's stream} and the call's sub-batch count
@@ -609,6 +610,7 @@ static int make_kparams(const drc_model_impl* mm, const drc_qpik_params* p, int 
   k->mode = p->mode;
   k->stages = stages;
   k->s = p->solver;
+  k->eqp_small = mm->eqp_small_cap < 0 || mm->eqp_small_cap > kEqpSmallCap ? kEqpSmallCap : mm->eqp_small_cap;
   k->nv = M.nv;
   if (M.kind == 0) {
     k->narm = M.nv;
@@ -1246,7 +1248,20 @@ int drc_debug_phase_cycles(unsigned long long* out, int reset) {
     return DRC_ERR_HIP;
   return DRC_OK;
 }
+// diagnostic build only: polish EQPs by reduced-KKT size N (bins 0 .. 14, then N >= 15)
+int drc_debug_eqp_hist(unsigned long long* out, int reset) {
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  if (drc_amd::phase_cycles_qp_hist(out, reset) || drc_amd::phase_cycles_fused_hist(out, reset)) return DRC_ERR_HIP;
+  return DRC_OK;
+}
 #endif
+
+int drc_debug_eqp_small_cap(drc_model* m, int cap) {
+  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  std::lock_guard<std::mutex> g(m->launch_mu);
+  m->eqp_small_cap = cap < 0 ? -1 : cap;
+  return DRC_OK;
+}
 
 int drc_model_create_manipulator(const char* urdf, const char* srdf, const char* packages, int device,
                                  drc_model** out) {

@@ -13,10 +13,15 @@ static __device__ unsigned long long g_phase_cycles[64];
 // device array once, at its end): a global atomic per phase and call from
 // every wave queued at the L2 and inflated the very cycles being measured
 static __shared__ unsigned long long g_ph_lds[64];
+// histogram of the polish's reduced-KKT sizes (PH_HIST: bins 0 .. 15, the last
+// one open-ended), kept the same way; drc_debug_eqp_hist sums the units
+static __device__ unsigned long long g_phase_hist[16];
+static __shared__ unsigned long long g_ph_hist_lds[16];
 }
 #define PH_KINIT()                         \
   do {                                     \
     g_ph_lds[__lane_id()] = 0ull;          \
+    if (__lane_id() < 16) g_ph_hist_lds[__lane_id()] = 0ull; \
     __builtin_amdgcn_wave_barrier();       \
   } while (0)
 #define PH_KFLUSH()                                                   \
@@ -24,6 +29,8 @@ static __shared__ unsigned long long g_ph_lds[64];
     __builtin_amdgcn_wave_barrier();                                  \
     const unsigned long long v_ = g_ph_lds[__lane_id()];              \
     if (v_) atomicAdd(&g_phase_cycles[__lane_id()], v_);              \
+    const unsigned long long h_ = g_ph_hist_lds[__lane_id() & 15];    \
+    if (h_ && __lane_id() < 16) atomicAdd(&g_phase_hist[__lane_id()], h_); \
   } while (0)
 // PH_KSCOPE(): zero the wave's slots at kernel entry, add them to the device
 // array at kernel exit
@@ -43,6 +50,10 @@ struct PhKernelScope {
     if (__lane_id() == 0) g_ph_lds[(slot)] += (unsigned long long)(val);                        \
   } while (0)
 #define PH_SINCE(slot, v) PH_ADD(slot, __builtin_amdgcn_s_memtime() - (v))
+#define PH_HIST(bin)                                                              \
+  do {                                                                            \
+    if (__lane_id() == 0) g_ph_hist_lds[(bin) < 15 ? (bin) : 15] += 1ull;         \
+  } while (0)
 // a private accumulator and an addition of the cycles since a stamp
 #define PH_ACC(v) unsigned long long v = 0
 #define PH_ACC_SINCE(acc, v) ((acc) += __builtin_amdgcn_s_memtime() - (v))
@@ -92,6 +103,16 @@ struct PhKernelScope {
       if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), v, sizeof(v)) != hipSuccess) return 1;     \
     }                                                                                              \
     return 0;                                                                                      \
+  }                                                                                                \
+  int fn##_hist(unsigned long long* out, int reset) {                                              \
+    unsigned long long v[16];                                                                      \
+    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_phase_hist), sizeof(v)) != hipSuccess) return 1;       \
+    for (int i = 0; i < 16; ++i) out[i] += v[i];                                                   \
+    if (reset) {                                                                                   \
+      for (int i = 0; i < 16; ++i) v[i] = 0;                                                       \
+      if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_hist), v, sizeof(v)) != hipSuccess) return 1;       \
+    }                                                                                              \
+    return 0;                                                                                      \
   }
 #else
 #define PH_ONLY(...)
@@ -101,6 +122,7 @@ struct PhKernelScope {
 #define PH_STAMP(v) do {} while (0)
 #define PH_ADD(slot, val) do {} while (0)
 #define PH_SINCE(slot, v) do {} while (0)
+#define PH_HIST(bin) do {} while (0)
 #define PH_ACC(v) do {} while (0)
 #define PH_ACC_SINCE(acc, v) do {} while (0)
 #define PH_DECL

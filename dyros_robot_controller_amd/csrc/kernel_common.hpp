@@ -49,6 +49,7 @@ struct KParams {
   int rQd, rBias, rMgd, rDgd;          // QPID extras of the task record
   int nbuf;                            // polish work-vector stride (>= ncap)
   int ncap;                            // largest polish KKT the LDS plan holds (nx + ng, or 48 for QPID)
+  int eqp_small;                       // polish: reduced KKTs of up to this many rows take the small EQP (<= kEqpSmallCap; 0 = never)
   drc_solver_settings s;
   // persistent QP region
   int oP, oG, oQ, oAB, oL, oU, oD, oE, oRho, oX, oZ, oY, oDY, oXT, oZT, oT1, oT2, oRed, oSc;
@@ -653,6 +654,10 @@ __device__ __forceinline__ void pinv_cod6_wave(const double* A, double* X, doubl
 // Register EQP of the polish (eqp_regs): reduced KKTs of up to this many rows
 // are solved lane-per-row in registers; the LDS plan sizes follow it.
 constexpr int kEqpRegCap = 16;
+// Small EQP of the polish (eqp_small): the largest compiled tier.  Reduced
+// KKTs of the manipulator QPIK shapes with at most this many rows (FR3: 96 %
+// of them) are factored whole in every lane's registers.
+constexpr int kEqpSmallCap = 4;
 
 // Lanes per QP instance (qp_kernel): 64, or 32 = two instances per wave
 // (Grp<32>; DESIGN.md: measured slower on FR3, so 64 is the default).

@@ -41,6 +41,9 @@ int phase_cycles_task(unsigned long long* out, int reset);
 int phase_cycles_qp(unsigned long long* out, int reset);
 int phase_cycles_qpid(unsigned long long* out, int reset);
 int phase_cycles_fused(unsigned long long* out, int reset);
+// ... and the QP kernels' histogram of polish reduced-KKT sizes to out[16]
+int phase_cycles_qp_hist(unsigned long long* out, int reset);
+int phase_cycles_fused_hist(unsigned long long* out, int reset);
 #endif
 
 }  // namespace drc_amd

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "kernel_common.hpp"
+#include "eqp_small.hpp"
 
 namespace drc_amd {
 
@@ -699,6 +700,206 @@ __device__ __forceinline__ bool eqp_regs(const KParams& kp, double* S, int actb,
   return true;
 }
 
+// Small form of eqp for the manipulator QPIK shapes: reduced KKTs of at most
+// NS rows (FR3: mean 1.9 rows, 96 % of them <= 4).  Same regularised system,
+// right-hand sides, refinement against K0 and zero-pivot outcome as eqp_regs;
+// only the rounding of the factorisation differs.  One wave is one instance,
+// so the branch on N is wave-uniform.  Straight-line code on NS-entry arrays:
+//   - the free-variable / active-row indices come off freeMask / rowMask by
+//     ctz chains (wave-uniform: scalar registers), no LDS index lists;
+//   - every lane reads the packed lower triangle of K0 at uniform LDS addresses
+//     (broadcast reads) and the right-hand sides of the owner lanes by
+//     v_readlane, then factors and solves the system redundantly in its own
+//     registers (eqp_small_core: LDL^T, one reciprocal per pivot): no cross-lane
+//     traffic and no LDS round trip per pivot;
+//   - unused rows are padded with the identity (inert);
+//   - N = 0 (every variable at a bound, no active row) factors nothing.
+// The caller (polish's drop rule) has already put the fixed values b_j / ab_j
+// and the free variables' zeros in xx and synchronised, so they are not
+// written again.  Leaves in LDS the free variables' xx, yy = 0 of the free
+// variables and yy of every G row (the active rows' multipliers, zeros
+// elsewhere); the bound multipliers of the fixed variables are formed by
+// polish_pass_small, with the candidate and the residuals.
+template <class QD>
+constexpr bool kEqpSmallShape = QD::nx > 0 && QD::np < QD::nx && QD::gs == 64;
+
+template <class QD, int NS>
+__device__ __forceinline__ bool eqp_small(const KParams& kp, double* S, int actb, int actg, double* xx, double* yy,
+                                          unsigned long long freeMask, unsigned long long rowMask, int nF, int nR) {
+  using GL = Grp<QD::gs>;
+  constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
+  const int l = GL::lane(), N = nF + nR;
+  const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *lo = S + kp.oL, *up = S + kp.oU;
+  double vF = 0.0, vR = 0.0;  // this lane's solution entries: free variable l, active G row l
+  if (N > 0) {
+    PH_STAMP(es_t0);
+    // right-hand sides by their owners, as eqp_regs (same sums, same order)
+    double rF = 0.0, rG = 0.0;
+    if (l < NX && actb == 0) {
+      double r = -q[l];
+      if (l < NP) {
+        const int lp = l < NP ? l : 0;
+#pragma unroll
+        for (int c = 0; c < NP; ++c) r -= P[lp * NP + c] * xx[c];
+      }
+      rF = r;
+    }
+    if (l < NG && actg != 0) {
+      const int lg = l < NG ? l : 0;
+      double r = actg < 0 ? lo[NX + lg] : up[NX + lg];
+#pragma unroll
+      for (int c = 0; c < NP; ++c) r -= G[lg * NX + c] * xx[c];
+      r -= G[lg * NX + NP + lg] * xx[NP + lg];
+      rG = r;
+    }
+    // position j of the reduced system: free variable idx[j] (j < nF), active
+    // row idx[j] (nF <= j < N), padding (j >= N)
+    int idx[NS];
+    {
+      unsigned long long fm = freeMask, rm = rowMask;
+#pragma unroll
+      for (int j = 0; j < NS; ++j) {
+        int v = 0;
+        if (fm) {
+          v = __builtin_ctzll(fm);
+          fm &= fm - 1;
+        } else if (rm) {
+          v = __builtin_ctzll(rm);
+          rm &= rm - 1;
+        }
+        idx[j] = v;
+      }
+    }
+    double K0[NS * (NS + 1) / 2], reg[NS], rhs[NS], sol[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const bool fi = i < nF, ri = !fi && i < N;
+      const double a = GL::bcast(rF, idx[i]), b = GL::bcast(rG, idx[i]);
+      rhs[i] = fi ? a : (ri ? b : 0.0);
+      reg[i] = eqp_small_reg(i, nF, N, kp.s.delta);
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {  // (j <= i: a free row i has only free columns)
+        const bool fj = j < nF;
+        const bool use = fi ? (idx[i] < NP && idx[j] < NP) : (ri && fj);
+        const int off = !use ? 0 : (fi ? kp.oP + idx[i] * NP + idx[j] : kp.oG + idx[i] * NX + idx[j]);
+        const double v = S[off];
+        K0[eqp_pk(i, j)] = use ? v : 0.0;
+      }
+    }
+    PH_SINCE(52, es_t0);
+    PH_STAMP(es_t1);
+    if (!eqp_small_core<NS>(K0, reg, rhs, kp.s.polish_refine_iter, sol)) return false;  // uniform
+    PH_SINCE(53, es_t1);
+    const unsigned long long below = (1ull << l) - 1;
+    const int pf = __popcll(freeMask & below), pr = nF + __popcll(rowMask & below);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      vF = pf == j ? sol[j] : vF;
+      vR = pr == j ? sol[j] : vR;
+    }
+  }
+  PH_STAMP(es_t2);
+  if (l < NX && actb == 0) {
+    xx[l] = vF;
+    yy[l] = 0.0;
+  }
+  if (l < NG) yy[NX + l] = actg != 0 ? vR : 0.0;
+  wsync();
+  PH_SINCE(55, es_t2);
+  return true;
+}
+
+// The polish's work on a small-EQP point, one pass where the general path
+// makes three (the fixed variables' multipliers from stationarity, the
+// candidate z = clamp(A xx), residuals<QD, false, true>): lane l < NX forms
+// P[l,:] xx and sum_i G[i,l] yy[nx+i] once and uses them for its bound
+// multiplier and for its dual-residual and norm terms; lane l < NG forms
+// G[l,:] xx once.  G^T y takes the active rows only, in row order (the other
+// terms are exact zeros).  The seven wave maxima are reduced together, step
+// by step, so their DPP chains overlap.  Same quantities as the general path
+// (SC_PRI, SC_DUA, SC_EPSP, SC_EPSD), returned in registers; the sums P x and
+// G^T y are rounded once instead of once per use.  Writes yy of the fixed
+// variables and zz; the caller synchronises before other lanes read them.
+template <class QD, int NS>
+__device__ __forceinline__ void polish_pass_small(const KParams& kp, double* S, int actb, int actg, const double* xx,
+                                                  double* yy, double* zz, double eps, double& axb, double& axg,
+                                                  double& pr1, double& dr1, double& epsp, double& epsd) {
+  using GL = Grp<QD::gs>;
+  constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
+  const int l = GL::lane();
+  const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU,
+               *Di = S + kp.oDi, *Ei = S + kp.oEi;
+  const unsigned long long rowMask = GL::ballot(l < NG && actg != 0);
+  double mx[7] = {0, 0, 0, 0, 0, 0, 0};  // pr, nAx, nz, dr, nPx, nAty, nq
+  axb = 0.0;
+  axg = 0.0;
+  if (l < NX) {
+    const int lx = l < NX ? l : 0;
+    double px = 0.0, gty = 0.0;
+    if (l < NP) {
+      const int lp = l < NP ? l : 0;
+#pragma unroll
+      for (int c = 0; c < NP; ++c) px += P[lp * NP + c] * xx[c];
+    }
+    {
+      unsigned long long rm = rowMask;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        if (rm) {  // uniform
+          const int i = __builtin_ctzll(rm);
+          rm &= rm - 1;
+          gty += G[i * NX + lx] * yy[NX + i];
+        }
+      }
+    }
+    const double a = ab[lx], ql = q[lx], di = Di[lx], ei = Ei[lx];
+    double yl = 0.0;
+    if (actb != 0) {  // bound multiplier from stationarity
+      yl = -(ql + px + gty) / a;
+      yy[lx] = yl;
+    }
+    axb = a * xx[lx];
+    const double zb = fmin(fmax(axb, lo[lx]), up[lx]);
+    zz[lx] = zb;
+    const double aty = a * yl + gty, rr = px + ql + aty;
+    mx[0] = fabs((axb - zb) * ei);
+    mx[1] = fabs(axb * ei);
+    mx[2] = fabs(zb * ei);
+    mx[3] = fabs(rr * di);
+    mx[4] = fabs(px * di);
+    mx[5] = fabs(aty * di);
+    mx[6] = fabs(ql * di);
+  }
+  if (l < NG) {
+    const int lg = l < NG ? l : 0, row = NX + lg;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) axg += G[lg * NX + j] * xx[j];
+    axg += G[lg * NX + NP + lg] * xx[NP + lg];
+    const double zg = fmin(fmax(axg, lo[row]), up[row]), ei = Ei[row];
+    zz[row] = zg;
+    mx[0] = fmax(mx[0], fabs((axg - zg) * ei));
+    mx[1] = fmax(mx[1], fabs(axg * ei));
+    mx[2] = fmax(mx[2], fabs(zg * ei));
+  }
+  // seven maxima, reduced side by side (fmax is exact: same values as seven GL::max)
+#pragma unroll
+  for (int k = 0; k < 7; ++k) mx[k] = fmax(mx[k], dpp_d<kDppQuad1032>(mx[k]));
+#pragma unroll
+  for (int k = 0; k < 7; ++k) mx[k] = fmax(mx[k], dpp_d<kDppQuad2301>(mx[k]));
+#pragma unroll
+  for (int k = 0; k < 7; ++k) mx[k] = fmax(mx[k], dpp_d<kDppHalfMirror>(mx[k]));
+#pragma unroll
+  for (int k = 0; k < 7; ++k) mx[k] = fmax(mx[k], dpp_d<kDppMirror>(mx[k]));
+#pragma unroll
+  for (int k = 0; k < 7; ++k)
+    mx[k] = fmax(fmax(rd_lane(mx[k], 0), rd_lane(mx[k], 16)), fmax(rd_lane(mx[k], 32), rd_lane(mx[k], 48)));
+  const double ci = S[kp.oSc + SC_CINV];
+  pr1 = mx[0];
+  dr1 = mx[3] * ci;
+  epsp = eps + eps * fmax(mx[1], mx[2]);
+  epsd = eps + eps * fmax(fmax(mx[4], mx[5]), mx[6]) * ci;
+}
+
 // Range-space form of eqp for the whole-body QPs (no variable bounds, so
 // every variable is free and the reduced KKT is [H, G_R^T; G_R, -dI] with
 // H = P + dI fixed for the instance).  Its inverse applied to (r_x, r_l):
@@ -878,8 +1079,12 @@ __device__ __forceinline__ bool eqp_range(const KParams& kp, double* S, int actg
 // left-looking LDL^T with iterative refinement against the unregularised
 // system.  Writes the full primal xx[nx] and dual yy[m] (scaled space).
 // Flags: actb (bound row l) / actg (G row l) held by lane l.
+// small: set when the point came from eqp_small, which leaves the fixed
+// variables' multipliers to polish_pass_small (and expects the fixed values in
+// xx on entry, as polish's drop rule leaves them).
 template <class QD>
-__device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int actg, double* xx, double* yy) {
+__device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int actg, double* xx, double* yy,
+                                    bool& small) {
   using GL = Grp<QD::gs>;
   const int l = GL::lane(), nx = DNX, ng = DNG, np = DNP, m = DM;
   const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL,
@@ -891,6 +1096,16 @@ __device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int 
   PH_STAMP(eq_t0);
   PH_ADD(41, 1);
   PH_ADD(42, N);
+  PH_HIST(N);
+  small = false;
+  if constexpr (kEqpSmallShape<QD>) {
+    if (kp.problem == 0 && N <= kp.eqp_small) {  // uniform
+      small = true;
+      const bool ok_ = eqp_small<QD, kEqpSmallCap>(kp, S, actb, actg, xx, yy, freeMask, rowMask, nF, nR);
+      PH_SINCE(40, eq_t0);
+      return ok_;
+    }
+  }
   if constexpr (QD::gs < 64) {  // two instances per wave: register EQP only (ncap <= kEqpRegCap)
     if (N > kEqpRegCap) return false;
   }
@@ -1158,7 +1373,8 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
       }
     }
     PH_SINCE(51, pd_t0);
-    if (!eqp<QD>(kp, S, actb, actg, xx, yy)) break;
+    bool small = false;
+    if (!eqp<QD>(kp, S, actb, actg, xx, yy, small)) break;
     PH_STAMP(pr_t0);
     if (have_feas) {
       double stepmax = 0, xnorm = 0;
@@ -1218,27 +1434,43 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
     PH_STAMP(pc_t0);
     // candidate point: z = clamp(A x), residuals, certification
     double axb = 0, axg = 0;
-    if (l < nx) {
-      axb = ab[l] * xx[l];
-      zz[l] = fmin(fmax(axb, lo[l]), up[l]);
-    }
-    if (l < ng) {
-      const int lg = l < ng ? l : 0;
-#pragma unroll
-      for (int j = 0; j < nx; ++j) {
-        if (j >= np && slk) break;
-        axg += G[lg * nx + j] * xx[j];
+    double pr1 = 0, dr1 = 0, epsp = 0, epsd = 0;
+    bool fused_pass = false;
+    if constexpr (kEqpSmallShape<QD>) {
+      if (small) {  // uniform: multipliers, candidate and residuals in one pass
+        fused_pass = true;
+        polish_pass_small<QD, kEqpSmallCap>(kp, S, actb, actg, xx, yy, zz, kp.s.eps_exact, axb, axg, pr1, dr1, epsp,
+                                            epsd);
+        PH_SINCE(43, pc_t0);
       }
-      if (slk) axg += G[lg * nx + np + lg] * xx[np + lg];
-      zz[nx + lg] = fmin(fmax(axg, lo[nx + lg]), up[nx + lg]);
     }
-    wsync();
-    PH_SINCE(57, pc_t0);
-    PH_STAMP(rs_t0);
-    residuals<QD, false, true>(kp, S, xx, zz, yy, kp.s.eps_exact, kp.s.eps_exact, axb, axg);
-    PH_SINCE(43, rs_t0);
+    if (!fused_pass) {
+      if (l < nx) {
+        axb = ab[l] * xx[l];
+        zz[l] = fmin(fmax(axb, lo[l]), up[l]);
+      }
+      if (l < ng) {
+        const int lg = l < ng ? l : 0;
+#pragma unroll
+        for (int j = 0; j < nx; ++j) {
+          if (j >= np && slk) break;
+          axg += G[lg * nx + j] * xx[j];
+        }
+        if (slk) axg += G[lg * nx + np + lg] * xx[np + lg];
+        zz[nx + lg] = fmin(fmax(axg, lo[nx + lg]), up[nx + lg]);
+      }
+      wsync();
+      PH_SINCE(57, pc_t0);
+      PH_STAMP(rs_t0);
+      residuals<QD, false, true>(kp, S, xx, zz, yy, kp.s.eps_exact, kp.s.eps_exact, axb, axg);
+      PH_SINCE(43, rs_t0);
+      pr1 = sc[SC_PRI];
+      dr1 = sc[SC_DUA];
+      epsp = sc[SC_EPSP];
+      epsd = sc[SC_EPSD];
+    }
     PH_STAMP(pk_t0);
-    const double pr1 = sc[SC_PRI], dr1 = sc[SC_DUA], epsp = sc[SC_EPSP], epsd = sc[SC_EPSD], ci = sc[SC_CINV];
+    const double ci = sc[SC_CINV];
     const double* Ei = S + kp.oEi;
     bool ok = (pr1 < pr0 && dr1 < dr0) || (pr1 < pr0 && dr0 < 1e-10) || (dr1 < dr0 && pr0 < 1e-10);
     double wv = 0;
@@ -1270,6 +1502,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
       }
     }
     if (ok) {
+      if (fused_pass) wsync();  // zz of the G rows: written by their own lanes, read below by row index
       if (l < nx) x[l] = xx[l];
       for (int row = l; row < m; row += GL::size) {
         y[row] = yy[row];

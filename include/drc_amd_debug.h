@@ -73,6 +73,15 @@ int drc_debug_lane_stage(drc_model* model, int enable);
  * tools/stamp_study.py --order); no reference counterpart. */
 int drc_debug_instance_order(drc_model* model, const int32_t* order, int64_t n);
 
+/* Certified polish of the manipulator QPIK kernels: reduced KKTs (free
+ * variables + active rows, N) of up to `cap` rows take the small straight-line
+ * EQP, larger ones the general register EQP.  -1: the compiled tiers (default);
+ * 0: the general path only; k: the small path for N <= min(k, largest tier).
+ * Both paths solve the same system (only the rounding of the factorisation and
+ * of the residual sums differs); the switch lets tests compare them on
+ * identical inputs and exercise each size boundary. */
+int drc_debug_eqp_small_cap(drc_model* model, int cap);
+
 #ifdef __cplusplus
 }
 #endif

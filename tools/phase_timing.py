@@ -19,8 +19,12 @@ link = spec["link"]
 ctrl.QPIK_step_batch(*args, link); torch.cuda.synchronize()
 buf = (C.c_ulonglong * 64)()
 _capi.lib().drc_debug_phase_cycles(buf, 1)
+hist = (C.c_ulonglong * 16)()
+has_hist = hasattr(_capi.lib(), "drc_debug_eqp_hist")  # (absent from older timing builds)
+if has_hist: _capi.lib().drc_debug_eqp_hist(hist, 1)
 ctrl.QPIK_step_batch(*args, link); torch.cuda.synchronize()
 _capi.lib().drc_debug_phase_cycles(buf, 0)
+if has_hist: _capi.lib().drc_debug_eqp_hist(hist, 0)
 v = np.array(buf[:], dtype=np.float64)
 names_t = ["fk+geoms", "J+taskvel", "manip", "broad+sphere", "gjk cand", "epa", "argmin+witness", "grad"]
 names_q = ["load+assemble", "scaling", "-", "rho+factor+admm+checks", "-", "output"]
@@ -49,3 +53,11 @@ sub = [("jacobi guess", 50), ("drop rule", 51), ("eqp setup (K0, rhs)", 52), ("e
        ("eqp solve + refinement", 54), ("eqp x, y, stationarity", 55), ("ratio test", 56), ("candidate z", 57),
        ("polish residuals", 43), ("certify + add/drop", 58)]
 print("polish sub-phases (cycles/instance): " + ", ".join("%s %.0f" % (n, v[k] / B) for n, k in sub))
+# (small EQP, N <= kEqpSmallCap: its factor + solve + refinement count under "Gauss-Jordan", its x / y write-out under
+# "x, y, stationarity", and its one pass for multipliers + candidate + residuals under "polish residuals")
+print("polish total: %.0f cycles/instance, %.2f EQPs/instance, %.0f cycles/EQP" % (v[35] / B, v[41] / B, v[35] / max(v[41], 1)))
+if has_hist:
+    h = np.array(hist[:], dtype=np.float64)
+    n = max(h.sum(), 1)
+    print("reduced-KKT size N of the %d EQPs: " % h.sum() + ", ".join("%s %.2f%%" % (("N=%d" % k) if k < 9 else "N>=9", 100 * x / n)
+          for k, x in enumerate(list(h[:9]) + [h[9:].sum()])))
