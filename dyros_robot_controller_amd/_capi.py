@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "drc_default_qpid_params", "drc_qpid_batch", "drc_qpid_stages_batch", "drc_qpid_host",
     "drc_qpid_stages_host", "drc_clik_batch", "drc_osf_batch", "drc_closed_form_host",
     "drc_error_string", "drc_last_error", "drc_build_id", "drc_qpik_host_timed", "drc_kinematics_batch",
-    "drc_state_host",
+    "drc_state_host", "drc_model_geom_info", "drc_mesh_convex_hull",
 )
 
 
@@ -130,6 +130,9 @@ def _load():
     lib.drc_model_destroy.restype = None
     lib.drc_model_info.argtypes = [vp, ip, ip, ip, ip, ip, ip]
     lib.drc_model_limits.argtypes = [vp, dp, dp, dp, dp]
+    if hasattr(lib, "drc_model_geom_info"):  # collision meshes: absent from older A/B builds
+        lib.drc_model_geom_info.argtypes = [vp, C.c_int, ip, dp, ip, dp]
+        lib.drc_mesh_convex_hull.argtypes = [C.c_char_p, dp, C.c_int, dp, C.c_int, ip, dp]
     lib.drc_model_find_frame.argtypes = [vp, C.c_char_p, ip]
     lib.drc_model_mobile_fk_jacobian.argtypes = [vp, dp]
     lib.drc_mobile_fk_jacobian.argtypes = [C.POINTER(KinematicParam), dp, dp, ip]
@@ -180,7 +183,8 @@ def _load():
     lib.drc_closed_form_host.argtypes = [vp, C.POINTER(QPIKParams), C.c_int, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]
     for name in EXPORTED_SYMBOLS:
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
-                    "drc_debug_qpik_stamps", "drc_debug_instance_order") and not hasattr(lib, name):
+                    "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info",
+                    "drc_mesh_convex_hull") and not hasattr(lib, name):
             continue  # diagnostics an older A/B build may lack
         if name not in ("drc_model_destroy", "drc_error_string", "drc_last_error", "drc_build_id"):
             getattr(lib, name).restype = C.c_int

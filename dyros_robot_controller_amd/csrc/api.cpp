@@ -22,6 +22,7 @@
 #include "dynamics.hpp"
 #include "kernel_common.hpp"
 #include "launch.hpp"
+#include "mesh.hpp"
 
 // ==========================================================================
 // host side: the C-ABI (include/drc_amd.h)
@@ -72,6 +73,7 @@ struct Lanes {
 struct drc_model_impl {
   HostModel hm;
   DevModel* d_model = nullptr;
+  double* d_mesh = nullptr;  // hull vertices of the collision meshes (DevModel::mesh_verts)
   int device = 0;
   drc_kinematic_param kparam{};
   drc_joint_index jidx{};
@@ -379,8 +381,18 @@ static int mobile_ik_jacobian(const drc_kinematic_param& p, const double* wheel_
   return set_err(DRC_ERR_INVALID_ARGUMENT, "unknown drive type");
 }
 
+// lane_task.hpp (the off-by-default debug stage) knows the primitives only
+static const char kMeshStageMsg[] =
+    "the model has collision meshes: the lane-per-instance debug stage handles sphere, cylinder and box geometry only";
+
 static int upload(drc_model_impl* m) {
   HIP_TRY(hipSetDevice(m->device));
+  if (m->hm.has_mesh()) {  // the hulls' vertices: one model-owned buffer
+    const size_t bytes = m->hm.mesh_verts.size() * sizeof(double);
+    HIP_TRY(hipMalloc(&m->d_mesh, bytes));
+    HIP_TRY(hipMemcpy(m->d_mesh, m->hm.mesh_verts.data(), bytes, hipMemcpyHostToDevice));
+    m->hm.dev.mesh_verts = m->d_mesh;
+  }
   HIP_TRY(hipMalloc(&m->d_model, sizeof(DevModel)));
   HIP_TRY(hipMemcpy(m->d_model, &m->hm.dev, sizeof(DevModel), hipMemcpyHostToDevice));
   return DRC_OK;
@@ -688,7 +700,7 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
   // (DESIGN.md), and stage and QPIK calls then see the same GJK witnesses)
   const int ls = m->lane_stage;
   const bool lane = (ls == 1 || ls == 2 || (ls == 3 && stages)) && (dm.nv == 6 || dm.nv == 7) &&
-                    dm.ncand_slots <= kMaxCandSlots;
+                    dm.ncand_slots <= kMaxCandSlots && !dm.has_mesh;
   // fused up to 16 Ki instances: there a call is a few instances per wave, its
   // makespan the tail the fused kernel and the EPA-first order below shorten;
   // at full batch the overlapped sub-batch pipeline wins.  Measured at
@@ -841,7 +853,8 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
     const size_t lds_t = static_cast<size_t>(kt_c.lds_doubles) * sizeof(double);
     const size_t lds_q = stages ? 0 : static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
     auto launch_task = [&](hipStream_t sm) -> int {
-      HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io)));
+      HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io,
+                                                         dm.has_mesh != 0)));
       return DRC_OK;
     };
     auto launch_qp = [&]() -> int {
@@ -865,7 +878,7 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
           sizeof(double);
       io.queue = qc;
       HIP_TRY(static_cast<hipError_t>(
-          launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io)));
+          launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, dm.has_mesh != 0)));
       if (timed_c) HIP_TRY(hipEventRecord(e1, cs));
     } else if (!lane) {  // wave-per-instance task kernel on every instance, then the QP
       if (int r = launch_task(cs)) return r;
@@ -985,7 +998,7 @@ static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, 
   io.queue = qc;
   HIP_TRY(static_cast<hipError_t>(launch_task_kernel(1, static_cast<unsigned>(grid),
                                                      static_cast<size_t>(kt_c.lds_doubles) * sizeof(double), st,
-                                                     m->d_model, kt_c, io)));
+                                                     m->d_model, kt_c, io, m->hm.dev.has_mesh != 0)));
   if (!stages) {
     io.queue = qc + 8;
     const size_t lds = static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
@@ -1211,6 +1224,7 @@ int drc_set_concurrency(drc_model* m, int chunks) {
 
 int drc_debug_lane_stage(drc_model* m, int enable) {
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  if (enable && m->hm.has_mesh()) return drc_amd::set_err(DRC_ERR_UNSUPPORTED, drc_amd::kMeshStageMsg);
   std::lock_guard<std::mutex> g(m->launch_mu);
   m->lane_stage = enable < 0 ? 0 : (enable > 3 ? 3 : enable);
   return DRC_OK;
@@ -1265,11 +1279,10 @@ int drc_debug_eqp_small_cap(drc_model* m, int cap) {
 
 int drc_model_create_manipulator(const char* urdf, const char* srdf, const char* packages, int device,
                                  drc_model** out) {
-  (void)packages;  // collision meshes are not supported: primitives only
   if (!urdf || !out) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null argument");
   auto* m = new drc_model();
   std::string err;
-  int rc = drc_amd::build_model_from_urdf(urdf, srdf ? srdf : "", &m->hm, &err);
+  int rc = drc_amd::build_model_from_urdf(urdf, srdf ? srdf : "", packages ? packages : "", &m->hm, &err);
   if (rc) {
     delete m;
     return drc_amd::set_err(rc, err);
@@ -1288,11 +1301,10 @@ int drc_model_create_manipulator(const char* urdf, const char* srdf, const char*
 int drc_model_create_mobile_manipulator(const drc_kinematic_param* param, const drc_joint_index* ji,
                                         const drc_actuator_index* ai, const char* urdf, const char* srdf,
                                         const char* packages, int device, drc_model** out) {
-  (void)packages;
   if (!param || !ji || !ai || !urdf || !out) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null argument");
   auto* m = new drc_model();
   std::string err;
-  int rc = drc_amd::build_model_from_urdf(urdf, srdf ? srdf : "", &m->hm, &err);
+  int rc = drc_amd::build_model_from_urdf(urdf, srdf ? srdf : "", packages ? packages : "", &m->hm, &err);
   if (rc) {
     delete m;
     return drc_amd::set_err(rc, err);
@@ -1366,6 +1378,7 @@ void drc_model_destroy(drc_model* m) {
   for (auto& c : m->ctxs) drc_amd::free_ctx(c.get());
   drc_amd::free_lanes(&m->ln);
   if (m->d_model) (void)hipFree(m->d_model);
+  if (m->d_mesh) (void)hipFree(m->d_mesh);
   if (m->d_order) (void)hipFree(m->d_order);
   if (m->hstream) (void)hipStreamSynchronize(m->hstream), (void)hipStreamDestroy(m->hstream);
   if (m->stage) (void)hipFree(m->stage);
@@ -1390,6 +1403,39 @@ int drc_model_info(const drc_model* m, int* dof, int* act, int* mani, int* mobi,
   if (mobi) *mobi = d.kind == 1 ? d.n_wheel : 0;
   if (ngeom) *ngeom = d.ngeom;
   if (npairs) *npairs = d.npairs;
+  return DRC_OK;
+}
+
+int drc_model_geom_info(const drc_model* m, int geom, int* type, double param[3], int* n_vertices,
+                        double* hull_residual) {
+  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  const drc_amd::DevModel& d = m->hm.dev;
+  if (geom < 0 || geom >= d.ngeom) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "geometry index out of range");
+  if (type) *type = d.gtype[geom];
+  if (param)
+    for (int i = 0; i < 3; ++i) param[i] = d.gparam[geom][i];
+  if (n_vertices) *n_vertices = m->hm.mesh_count[geom];
+  if (hull_residual) *hull_residual = m->hm.mesh_residual[geom];
+  return DRC_OK;
+}
+
+int drc_mesh_convex_hull(const char* path, const double scale[3], int max_vertices, double* verts_out, int cap,
+                         int* n_out, double* residual_out) {
+  if (!path || !n_out) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null argument");
+  *n_out = 0;
+  drc_amd::MeshHull hull;
+  std::string err;
+  const int rc = drc_amd::mesh_convex_hull(path, scale, max_vertices > 0 ? max_vertices : drc_amd::kMaxMeshVerts,
+                                           &hull, &err);
+  if (rc) return drc_amd::set_err(rc, err);
+  const int n = static_cast<int>(hull.verts.size());
+  *n_out = n;
+  if (residual_out) *residual_out = hull.residual;
+  if (n > cap || (n > 0 && !verts_out))
+    return drc_amd::set_err(DRC_ERR_SIZE_MISMATCH, "verts_out holds " + std::to_string(cap < 0 ? 0 : cap) +
+                                                       " vertices, the hull has " + std::to_string(n));
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) verts_out[3 * i + k] = hull.verts[i][k];
   return DRC_OK;
 }
 

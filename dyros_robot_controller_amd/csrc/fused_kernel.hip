@@ -21,7 +21,8 @@ namespace drc_amd {
 #ifndef DRC_FUSED_WAVES
 #define DRC_FUSED_WAVES 2
 #endif
-template <class QD>
+// MESH: the build for models with convex-hull geometry (task_stage.hpp)
+template <class QD, bool MESH = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
 fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io) {
   extern __shared__ __attribute__((aligned(16))) double S[];
@@ -46,31 +47,49 @@ fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     const int64_t b = io.ordered(jj);
     stage_stamp(io, ST_TASK0, io.b0 + b);
     stage_where(io, ST_WTASK, io.b0 + b);
-    task_instance<0>(M0, kt, iol, S, b);
+    task_instance<0, MESH>(M0, kt, iol, S, b);
     wsync();
     stage_stamp(io, ST_TASK1, io.b0 + b);
     qp_instance<QD>(M0, kq, kpl, iol, S, b);
   }
 }
 
-int launch_fused_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+template <bool MESH>
+static int launch_fused(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                         const KParams& kq, const IO& io) {
   const dim3 g(grid), blk(64);
   if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
-    hipLaunchKernelGGL((fused_kernel<Dims<23, 16, 7, true, true, 64>>), g, blk, lds, st, m, kt, kq, io);
+    hipLaunchKernelGGL((fused_kernel<Dims<23, 16, 7, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
   else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
-    hipLaunchKernelGGL((fused_kernel<Dims<20, 14, 6, true, true, 64>>), g, blk, lds, st, m, kt, kq, io);
+    hipLaunchKernelGGL((fused_kernel<Dims<20, 14, 6, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
   else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
-    hipLaunchKernelGGL((fused_kernel<Dims<9, 16, 9, true, true, 64>>), g, blk, lds, st, m, kt, kq, io);
+    hipLaunchKernelGGL((fused_kernel<Dims<9, 16, 9, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
   else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
-    hipLaunchKernelGGL((fused_kernel<Dims<11, 16, 11, true, true, 64>>), g, blk, lds, st, m, kt, kq, io);
+    hipLaunchKernelGGL((fused_kernel<Dims<11, 16, 11, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
   else
     return hipErrorInvalidValue;  // not a compiled shape: the two-kernel pipeline runs it
   return hipGetLastError();
 }
 
+// The builds for models with hulls are a translation unit of their own
+// (fused_mesh_kernel.hip includes this file with DRC_FUSED_MESH defined), so
+// this unit compiles to what it was without them.
+#ifdef DRC_FUSED_MESH
+int launch_fused_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                             const KParams& kq, const IO& io) {
+  return launch_fused<true>(grid, lds, st, m, kt, kq, io);
+}
+#else
+int launch_fused_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                             const KParams& kq, const IO& io);
+int launch_fused_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                        const KParams& kq, const IO& io, bool mesh) {
+  return mesh ? launch_fused_mesh_kernel(grid, lds, st, m, kt, kq, io) : launch_fused<false>(grid, lds, st, m, kt, kq, io);
+}
+
 #ifdef DRC_PHASE_TIMING
 DRC_PHASE_EXPORT(phase_cycles_fused)
+#endif
 #endif
 
 }  // namespace drc_amd

@@ -10,8 +10,10 @@
 namespace drc_amd {
 
 // task_kernel<problem>: 0 QPIK stage, 1 QPID stage, 2 closed-form CLIK / OSF
+// mesh: the model has convex-hull geometry (problems 0 and 1 then run the
+// build with the hull narrow phase; 2 has no distance stage)
 int launch_task_kernel(int problem, unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
-                       const IO& io);
+                       const IO& io, bool mesh = false);
 // register-budget waves per SIMD of the task build launch_task_kernel picks
 // for a plan of `lds` bytes per wave, and of the QP kernel
 int task_waves_per_simd(int problem, size_t lds);
@@ -26,8 +28,9 @@ int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* 
 int launch_qpid_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io);
 // fused task + QP kernel (compiled QPIK shapes; hipErrorInvalidValue otherwise);
 // lds = both plans' maximum plus the record slot
+// mesh: the build with the hull narrow phase, as for launch_task_kernel
 int launch_fused_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
-                        const KParams& kq, const IO& io);
+                        const KParams& kq, const IO& io, bool mesh = false);
 
 // queue order of one sub-batch (order_kernel.hip): penetration-prone
 // instances first (*hot_n zeroed; hot_list [B], hot_flag [B] scratch), then the

@@ -12,6 +12,7 @@
 //   lowerPositionLimit / velocityLimit    from <limit>.
 #include "model.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +23,7 @@
 #include <sstream>
 
 #include "../../include/drc_amd.h"
+#include "mesh.hpp"
 
 namespace drc_amd {
 namespace {
@@ -222,7 +224,9 @@ struct Builder {
   HostModel* hm;
   std::vector<std::string> geom_link;
   std::map<std::string, int> frame_of_link;
+  std::string packages, urdf_dir;  // where mesh URIs are looked up
   std::string err;
+  int err_code = DRC_ERR_UNSUPPORTED;
 
   bool add_link(const std::string& lname, int jid, const SE3& place) {
     DevModel& m = hm->dev;
@@ -241,6 +245,7 @@ struct Builder {
       if (m.ngeom >= kMaxGeoms) return fail("too many collision geometries");
       int gi = m.ngeom;
       double prm[3] = {0, 0, 0};
+      SE3 centre;  // mesh: from the file's frame to the bounding box's centre
       if (s->tag == "sphere") {
         m.gtype[gi] = kSphere;
         if (!parse_vec(s->get("radius"), 1, prm)) return fail("bad sphere radius");
@@ -259,12 +264,52 @@ struct Builder {
         if (!parse_vec(s->get("size"), 3, sz)) return fail("bad box size");
         for (int i = 0; i < 3; ++i) prm[i] = 0.5 * sz[i];
         m.gbound[gi] = std::sqrt(prm[0] * prm[0] + prm[1] * prm[1] + prm[2] * prm[2]);
+      } else if (s->tag == "mesh") {
+        // the convex hull of the file's vertices, centred on its bounding box:
+        // gparam / gbound describe that box, which the broad phase takes for
+        // the mesh (a lower bound on the box holds for the hull inside it)
+        m.gtype[gi] = kMesh;
+        const char* fn = s->get("filename");
+        if (!fn) return fail("mesh without filename in link " + lname);
+        double sc[3] = {1, 1, 1};
+        if (s->get("scale") && !parse_vec(s->get("scale"), 3, sc)) return fail("bad mesh scale in link " + lname);
+        std::string path, e;
+        MeshHull hull;
+        int rc = resolve_mesh_uri(fn, packages, urdf_dir, &path, &e);
+        if (!rc) rc = mesh_convex_hull(path, sc, kMaxMeshVerts, &hull, &e);
+        if (rc) return fail("collision mesh of link " + lname + ": " + e, rc);
+        const int first = static_cast<int>(hm->mesh_verts.size() / 3), nvx = static_cast<int>(hull.verts.size());
+        if (first + nvx > kMaxMeshVertsModel)
+          return fail("collision meshes exceed " + std::to_string(kMaxMeshVertsModel) +
+                      " hull vertices per model (link " + lname + ", " + path + ")");
+        double lo[3], hi[3];
+        for (int i = 0; i < 3; ++i) lo[i] = hi[i] = hull.verts[0][i];
+        for (const P3& v : hull.verts)
+          for (int i = 0; i < 3; ++i) {
+            lo[i] = std::min(lo[i], v[i]);
+            hi[i] = std::max(hi[i], v[i]);
+          }
+        for (int i = 0; i < 3; ++i) {
+          centre.p[i] = 0.5 * (lo[i] + hi[i]);
+          prm[i] = 0.5 * (hi[i] - lo[i]);
+        }
+        for (const P3& v : hull.verts)
+          for (int i = 0; i < 3; ++i) hm->mesh_verts.push_back(v[i] - centre.p[i]);
+        m.gbound[gi] = std::sqrt(prm[0] * prm[0] + prm[1] * prm[1] + prm[2] * prm[2]);
+        hm->mesh_first.resize(gi + 1, 0);
+        hm->mesh_count.resize(gi + 1, 0);
+        hm->mesh_residual.resize(gi + 1, 0.0);
+        hm->mesh_files.resize(gi + 1);
+        hm->mesh_first[gi] = first;
+        hm->mesh_count[gi] = nvx;
+        hm->mesh_residual[gi] = hull.residual;
+        hm->mesh_files[gi] = path;
       } else {
-        return fail("unsupported collision geometry <" + s->tag + "> (mesh) in link " + lname);
+        return fail("unsupported collision geometry <" + s->tag + "> in link " + lname);
       }
       std::memcpy(m.gparam[gi], prm, sizeof(prm));
       m.gparent[gi] = jid;
-      put12(mul(place, origin_of(c)), m.gplace[gi]);
+      put12(mul(mul(place, origin_of(c)), centre), m.gplace[gi]);
       hm->geom_names.push_back(lname + "_" + std::to_string(k++));
       geom_link.push_back(lname);
       ++m.ngeom;
@@ -351,8 +396,9 @@ struct Builder {
     }
     return true;
   }
-  bool fail(const std::string& e) {
+  bool fail(const std::string& e, int code = DRC_ERR_UNSUPPORTED) {
     err = e;
+    err_code = code;
     return false;
   }
 };
@@ -360,7 +406,7 @@ struct Builder {
 }  // namespace
 
 int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_path,
-                          HostModel* out, std::string* err) {
+                          const std::string& packages_path, HostModel* out, std::string* err) {
   std::string text;
   if (!read_file(urdf_path, &text)) {
     *err = "URDF file does not exist: " + urdf_path;
@@ -377,6 +423,11 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
   Builder b;
   b.robot = root.get();
   b.hm = out;
+  b.packages = packages_path;
+  {
+    const size_t sep = urdf_path.find_last_of('/');
+    b.urdf_dir = sep == std::string::npos ? "" : (sep == 0 ? "/" : urdf_path.substr(0, sep));
+  }
   std::set<std::string> child_links;
   for (auto& k : root->kids) {
     if (k->tag == "link") b.links[k->get("name", "")] = k.get();
@@ -405,9 +456,18 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
   }
   if (!b.walk(roots[0], 0, SE3())) {
     *err = b.err;
-    return DRC_ERR_UNSUPPORTED;
+    return b.err_code;
   }
   DevModel& m = out->dev;
+  out->mesh_first.resize(m.ngeom, 0);
+  out->mesh_count.resize(m.ngeom, 0);
+  out->mesh_residual.resize(m.ngeom, 0.0);
+  out->mesh_files.resize(m.ngeom);
+  m.has_mesh = out->has_mesh() ? 1 : 0;
+  for (int g = 0; g < m.ngeom; ++g) {
+    m.gmesh_first[g] = out->mesh_first[g];
+    m.gmesh_count[g] = out->mesh_count[g];
+  }
   // addAllCollisionPairs
   std::vector<std::pair<int, int>> pairs;
   for (int i = 0; i < m.ngeom; ++i)
@@ -454,14 +514,16 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
   }
   // pair order of the wave kernel's closed-form / bound pass: by type class
   // (sphere-sphere, sphere-cylinder, sphere-box, cylinder-cylinder,
-  // cylinder-box, box-box), pair index order within a class
+  // cylinder-box, box-box, then every pair with a mesh), pair index order
+  // within a class
   {
     int n = 0;
-    for (int cls = 0; cls < 6; ++cls)
+    for (int cls = 0; cls < 7; ++cls)
       for (int p = 0; p < m.npairs; ++p) {
         int ta = m.gtype[m.pair_a[p]], tb = m.gtype[m.pair_b[p]];
         if (ta > tb) std::swap(ta, tb);
-        const int c = ta == 0 ? tb : (ta == 1 ? 2 + tb : 5);  // (0,0)0 (0,1)1 (0,2)2 (1,1)3 (1,2)4 (2,2)5
+        // (0,0)0 (0,1)1 (0,2)2 (1,1)3 (1,2)4 (2,2)5 (*,mesh)6
+        const int c = tb == kMesh ? 6 : (ta == 0 ? tb : (ta == 1 ? 2 + tb : 5));
         if (c == cls) m.pair_order[n++] = static_cast<int16_t>(p);
       }
     for (int sl = 0; sl < m.npairs; ++sl) {

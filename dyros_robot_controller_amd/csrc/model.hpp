@@ -17,7 +17,7 @@ constexpr int kMaxWheels = 8;
 constexpr int kMaxCandSlots = 128;  // non-sphere pairs the lane-per-instance task stage tracks
 
 enum JointType : int { kRevolute = 0, kPrismatic = 1 };
-enum GeomType : int { kSphere = 0, kCylinder = 1, kBox = 2 };
+enum GeomType : int { kSphere = 0, kCylinder = 1, kBox = 2, kMesh = 3 };  // kMesh: convex hull of a mesh's vertices
 enum DriveKind : int { kDriveDifferential = 0, kDriveMecanum = 1, kDriveCaster = 2 };  // DRC_DRIVE_*
 
 // Flat, POD model image in HBM.  Transforms are 12 doubles: R row-major, p.
@@ -38,7 +38,7 @@ struct DevModel {
   int gparent[kMaxGeoms];
   int gtype[kMaxGeoms];
   double gplace[kMaxGeoms][12];
-  double gparam[kMaxGeoms][3];     // sphere r | cylinder r, h/2 | box half extents
+  double gparam[kMaxGeoms][3];     // sphere r | cylinder r, h/2 | box half extents | mesh: its bounding box's
   double gbound[kMaxGeoms];        // conservative core/bounding radius for the broad phase
   int16_t pair_a[kMaxPairs], pair_b[kMaxPairs];
   int16_t cand_slot[kMaxPairs];       // pair -> GJK candidate slot (pairs without a sphere), or -1
@@ -56,6 +56,12 @@ struct DevModel {
   // {mass, com x, y, z, Ixx, Iyy, Izz, Ixy, Ixz, Iyz} with I about the com
   double inertia[kMaxJoints + 1][10];
   int dyn_origin;                  // joint whose origin the dynamics kernel takes as spatial reference (0 = world)
+  // convex hulls of the collision meshes (appended: the layout above is what
+  // the kernels of mesh-free models were built against).  Geometry g of type
+  // kMesh owns mesh_verts[3 * gmesh_first[g] ...], gmesh_count[g] vertices
+  int has_mesh;
+  int gmesh_first[kMaxGeoms], gmesh_count[kMaxGeoms];
+  const double* mesh_verts;        // device buffer [n][3] (model-owned), null without meshes
 };
 
 struct HostModel {
@@ -64,10 +70,19 @@ struct HostModel {
   std::vector<std::string> frame_names;   // link (BODY) frames, index = frame id
   std::vector<std::string> geom_names;
   std::vector<double> effort;
+  // convex hulls of the collision meshes (mesh.hpp), all in one buffer:
+  // geometry g owns vertices [mesh_first[g], mesh_first[g] + mesh_count[g]),
+  // relative to the centre of their bounding box (the offset is in gplace)
+  std::vector<double> mesh_verts;         // [n][3]
+  std::vector<int> mesh_first, mesh_count;  // per geometry (count 0: primitive)
+  std::vector<double> mesh_residual;        // per geometry: what a reduced hull leaves out (mesh.hpp)
+  std::vector<std::string> mesh_files;      // per geometry: the resolved file
+  bool has_mesh() const { return !mesh_verts.empty(); }
 };
 
 // Returns 0 on success, DRC_ERR_* otherwise; err gets a readable reason.
+// packages_path: where package://a/b mesh URIs are looked up (<packages_path>/a/b).
 int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_path,
-                          HostModel* out, std::string* err);
+                          const std::string& packages_path, HostModel* out, std::string* err);
 
 }  // namespace drc_amd

@@ -72,6 +72,8 @@ __global__ void __launch_bounds__(64) order_kernel(const DevModel* __restrict__ 
     double TA[12], TB[12];
     tmul(Tw[M->gparent[ga]], M->gplace[ga], TA);
     tmul(Tw[M->gparent[gb_]], M->gplace[gb_], TB);
+    // (a hull, kMesh, is predicted as its bounding box: gparam holds the box's half extents, and support(),
+    // core_segment() and pair_lower_bound() take every type but sphere and cylinder for a box)
     const Shape A{M->gtype[ga], TA, M->gparam[ga][0], M->gparam[ga][1], M->gparam[ga][2]};
     const Shape Bs{M->gtype[gb_], TB, M->gparam[gb_][0], M->gparam[gb_][1], M->gparam[gb_][2]};
     // bounding spheres apart: the pair cannot touch (cheap reject)

@@ -301,11 +301,32 @@ DRC_HD __forceinline__ void tmul(const double* a, const double* b, double* c) {
 // a flat access
 template <class PT>
 struct ShapeT {
+  static constexpr bool kHasMesh = false;
   int type;
   PT T;              // pose (3x3 row-major rotation, then the origin)
   double p0, p1, p2; // parameters
 };
 using Shape = ShapeT<const double*>;
+// A shape that may also be a convex hull (kMesh): nv hull vertices v[nv][3] in
+// the shape's frame, centred on their bounding box (p0..p2: its half extents).
+// The vertices are model constants in HBM, read through L2.  The kernels of
+// mesh-free models never see this type (ShapeT has no mesh branch at all).
+// COOP: support() is called by the whole wave with wave-uniform arguments and
+// scans the vertices 64 at a time (lane l takes l, l + 64, ...); otherwise
+// one lane scans them all.  Both pick the same vertex (mesh_support).
+template <class PT, bool COOP>
+struct ShapeMT {
+  static constexpr bool kHasMesh = true, kCoop = COOP;
+  int type;
+  PT T;
+  double p0, p1, p2;
+  const double* v;
+  int nv;
+};
+template <class PT, bool COOP>
+DRC_HD __forceinline__ ShapeMT<PT, false> serial_shape(const ShapeMT<PT, COOP>& s) {
+  return ShapeMT<PT, false>{s.type, s.T, s.p0, s.p1, s.p2, s.v, s.nv};
+}
 #ifdef __HIP_DEVICE_COMPILE__
 typedef __attribute__((address_space(3))) const double lds_pose;
 #else
@@ -313,8 +334,46 @@ typedef const double lds_pose;
 #endif
 using ShapeL = ShapeT<lds_pose*>;
 
+// Support point of a hull: the direction goes into the hull's frame once, the
+// arg-max of v . d runs over the local vertices and only the winner is
+// transformed.  Ties go to the lowest vertex index (every lane visits its
+// vertices in ascending order and keeps the first strict maximum; the wave
+// reduction orders (value, index) totally), so the cooperative and the serial
+// scan return the same vertex whatever the dealing of vertices to lanes.
+template <class SH>
+DRC_HD __forceinline__ V3 mesh_support(const SH& s, V3 d) {
+  const V3 dl = rotT(s.T, d);
+  double bv = -1.7976931348623157e308;
+  int bi = 0x7fffffff;
+#ifdef __HIP_DEVICE_COMPILE__
+  if constexpr (SH::kCoop) {
+    for (int i = threadIdx.x & 63; i < s.nv; i += 64) {
+      const double val = s.v[3 * i] * dl.x + s.v[3 * i + 1] * dl.y + s.v[3 * i + 2] * dl.z;
+      if (val > bv) {
+        bv = val;
+        bi = i;
+      }
+    }
+    double nb = -bv;
+    wave_argmin(nb, bi);
+    return xform(s.T, ld3(s.v + 3 * bi));
+  }
+#endif
+  for (int i = 0; i < s.nv; ++i) {
+    const double val = s.v[3 * i] * dl.x + s.v[3 * i + 1] * dl.y + s.v[3 * i + 2] * dl.z;
+    if (val > bv) {
+      bv = val;
+      bi = i;
+    }
+  }
+  return xform(s.T, ld3(s.v + 3 * bi));
+}
+
 template <class SH>
 DRC_HD __forceinline__ V3 support(const SH& s, V3 d) {
+  if constexpr (SH::kHasMesh) {
+    if (s.type == kMesh) return mesh_support(s, d);
+  }
   if (s.type == kSphere) return v3(s.T[9], s.T[10], s.T[11]);
   V3 dl = rotT(s.T, d), loc;
   if (s.type == kCylinder) {
@@ -539,8 +598,11 @@ struct GjkState {
 // cut: the caller only needs the distance if it is <= cut.  Every support
 // point gives the lower bound v.w / |v| of the (signed) distance; once it
 // exceeds cut the pair cannot matter and the run stops with pruned = 1.
+// tol: the gap tolerance.  0 for two polytopes: their GJK ends exactly, when
+// the support point repeats (the duplicate test below).
 template <bool ANY = false, class SH = Shape>
-DRC_HD __forceinline__ void gjk_run(const SH& A, const SH& B, GjkState& g, double cut = 1e300) {
+DRC_HD __forceinline__ void gjk_run(const SH& A, const SH& B, GjkState& g, double cut = 1e300,
+                                    double tol = kGjkTol) {
   SV2(&S)[4] = g.S;
 #pragma unroll
   for (int i = 0; i < 4; ++i) S[i].w = S[i].a = v3(0, 0, 0);
@@ -558,7 +620,7 @@ DRC_HD __forceinline__ void gjk_run(const SH& A, const SH& B, GjkState& g, doubl
       g.pruned = 1;
       break;
     }
-    if (n > 0 && vv - vw <= kGjkTol * sv) break;
+    if (n > 0 && vv - vw <= tol * sv) break;
     bool dup = false;
 #pragma unroll
     for (int i = 0; i < 4; ++i) dup |= i < n && S[i].w.x == w.w.x && S[i].w.y == w.w.y && S[i].w.z == w.w.z;
@@ -623,6 +685,34 @@ DRC_HD inline __noinline__ GjkDist gjk(const SH A, const SH B, double cut = 1e30
   o.intersect = g.intersect;
   o.pruned = g.pruned;
   // witnesses: sum_i lam_i a_i and sum_i lam_i b_i (oracle accumulation order)
+  V3 pA = v3(0, 0, 0), pB = v3(0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < g.n) {
+      pA = pA + g.lam[i] * g.S[i].a;
+      pB = pB + g.lam[i] * (g.S[i].a - g.S[i].w);
+    }
+  o.pA = pA;
+  o.pB = pB;
+  o.dist = sqrt(dot(g.v, g.v));
+  return o;
+}
+// gjk for a pair with a hull, on the whole wave: every lane runs the same
+// iteration on the same (wave-uniform) simplex while the support of a hull is
+// shared out over the lanes (ShapeMT<.., true>), so a 150-vertex scan costs
+// three vertices a lane instead of stalling 63 lanes behind one.  Same
+// contract as gjk (cut exit, intersect flag, EPA stash by one lane); every
+// lane returns the same result.
+template <class SH>
+__device__ inline __noinline__ GjkDist gjk_wave(const SH A, const SH B, double cut, double tol, EpaPoly* stash,
+                                                int pair) {
+  static_assert(SH::kHasMesh && SH::kCoop, "gjk_wave runs on cooperative shapes");
+  GjkState g;
+  gjk_run(A, B, g, cut, tol);
+  if (stash && g.intersect && (threadIdx.x & 63) == 0) epa_stash(stash, g, pair);
+  GjkDist o;
+  o.intersect = g.intersect;
+  o.pruned = g.pruned;
   V3 pA = v3(0, 0, 0), pB = v3(0, 0, 0);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -1118,8 +1208,14 @@ __device__ __forceinline__ double epa_run_wave(const SH& A, const SH& B, EpaPoly
   const int l = threadIdx.x & 63;
   const unsigned long long ti = st ? __builtin_amdgcn_s_memtime() : 0;
   if (l == ln) {  // seed from the stashed simplex (sk >= 0) or rerun GJK
-    if (sk >= 0) epa_init_stash(A, B, E, sk, sn);
-    else epa_init(A, B, E);
+    if constexpr (SH::kHasMesh) {  // one lane: a hull's support scans serially here
+      const auto As = serial_shape(A), Bs = serial_shape(B);
+      if (sk >= 0) epa_init_stash(As, Bs, E, sk, sn);
+      else epa_init(As, Bs, E);
+    } else {
+      if (sk >= 0) epa_init_stash(A, B, E, sk, sn);
+      else epa_init(A, B, E);
+    }
   }
   wsync();
   if (st) st[8] += __builtin_amdgcn_s_memtime() - ti;  // (timing builds: the seed polytope)
@@ -1297,6 +1393,22 @@ DRC_HD __forceinline__ double sphere_pair(const SH& A, const SH& B, V3* pA, V3* 
     *pB = q;
   }
   return sd - s.p0;
+}
+
+// Sphere against hull from the centre's result: (d, pA, pB) of the centre
+// (d < 0: the centre is inside, EPA's depth) become those of the sphere of
+// radius r, in sphere_pair's convention (the sphere's witness lies r along
+// the centre -> surface direction, reversed for a centre inside).
+DRC_HD __forceinline__ void sphere_hull_witness(bool a_is_sphere, double r, double* d, V3* pA, V3* pB) {
+  const V3 c = a_is_sphere ? *pA : *pB, q = a_is_sphere ? *pB : *pA;
+  const V3 u = q - c;
+  const double L = sqrt(dot(u, u));
+  V3 n = L > 0 ? (1.0 / L) * u : v3(1, 0, 0);
+  if (*d < 0) n = -1.0 * n;
+  const V3 ps = c + r * n;
+  if (a_is_sphere) *pA = ps;
+  else *pB = ps;
+  *d -= r;
 }
 
 // ------------------------------------------------------------ witness refinement
@@ -1606,6 +1718,209 @@ DRC_HD inline __noinline__ bool refine_witness(const SH A, const SH B, double* d
     uB = rw_params(fB, rotT(B.T, XB - cB));
   }
   return false;
+}
+
+// Exact finish for a pair with a hull.  Two polytopes (hull, box, a sphere's
+// centre) need none: their GJK ends exactly.  Against a cylinder GJK only
+// converges like the primitives' (curved surface), so a separated winner is
+// refined the same way.  The hull's feature comes from the distinct hull
+// vertices of GJK's final simplex (one lane reruns the pair's GJK for them:
+// the witnesses alone give the normal only to ~sqrt(gap / d)): one a vertex,
+// two an edge, three a face.  It is affine, like the box's vertex / edge /
+// face that rw_classify / rw_eval parametrise, so it is handed to
+// refine_witness as the matching feature of a thin box laid onto it (its
+// corner, edge or top face; a face as an unbounded plane).  The result is
+// kept only if it is a critical point on the hull itself: the new normal
+// supports the hull at the point, and a face point lies inside the face's
+// polygon (the hull vertices in the support plane).  A penetrating winner
+// has no such simplex: its feature is read off the hull under EPA's normal.
+template <class SH>
+DRC_HD inline bool refine_hull_cylinder(const SH& A, const SH& B, double* d, V3* pA, V3* pB) {
+  const bool hull_is_a = A.type == kMesh;
+  const SH& H = hull_is_a ? A : B;
+  const SH& Cy = hull_is_a ? B : A;
+  if (!(fabs(*d) > 1e-9)) return false;
+  const V3 pH = hull_is_a ? *pA : *pB, pC = hull_is_a ? *pB : *pA;
+  // outward normal of the hull at its witness (pB - pA = d n with n from A to B, either sign of d)
+  V3 n0 = (1.0 / *d) * (pC - pH);
+  n0 = (1.0 / sqrt(dot(n0, n0))) * n0;
+  V3 hv[3] = {v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0)};
+  int nh = 0;
+  if (*d > 0) {
+    GjkState g;
+    gjk_run(A, B, g, 1e300, kGjkTol);
+    if (g.intersect || g.n < 1) return false;
+    for (int i = 0; i < 4; ++i) {
+      if (i >= g.n || !(g.lam[i] > 0)) continue;
+      const V3 b = hull_is_a ? g.S[i].a : g.S[i].a - g.S[i].w;
+      bool seen = false;
+      for (int k = 0; k < 3; ++k) {
+        const V3 e = b - hv[k < nh ? k : 0];
+        seen |= k < nh && dot(e, e) < 1e-18;
+      }
+      if (seen) continue;
+      if (nh == 3) return false;
+      hv[nh++] = b;
+    }
+  } else {
+    // penetrating: EPA leaves no simplex on the hull, and its normal is good
+    // to ~sqrt(tolerance / size) only.  The feature is what the hull shows
+    // within kRwSlab of its support plane under that normal, taken only if
+    // it is unambiguous: one vertex, vertices on one line (an edge, by its
+    // end points) or in one plane (a face, by three of them).
+    // (kRwSlab: 4 % of the hull's half diagonal, 2 mm on a 10 cm part; the
+    // flatness test in the same proportion)
+    const double hd = sqrt(H.p0 * H.p0 + H.p1 * H.p1 + H.p2 * H.p2), kRwSlab = 0.04 * hd, kRwFlat = 2e-6 * hd;
+    const V3 nl = rotT(H.T, n0);
+    double hmax = -1.7976931348623157e308;
+    for (int i = 0; i < H.nv; ++i) hmax = fmax(hmax, dot(ld3(H.v + 3 * i), nl));
+    int cnt = 0, i0 = 0;
+    for (int i = H.nv - 1; i >= 0; --i)
+      if (dot(ld3(H.v + 3 * i), nl) >= hmax - kRwSlab) {
+        ++cnt;
+        i0 = i;
+      }
+    auto farthest = [&](V3 from) {
+      int b = i0;
+      double bd = -1;
+      for (int i = 0; i < H.nv; ++i) {
+        const V3 v = ld3(H.v + 3 * i), e = v - from;
+        if (dot(v, nl) >= hmax - kRwSlab && dot(e, e) > bd) {
+          bd = dot(e, e);
+          b = i;
+        }
+      }
+      return b;
+    };
+    const int i1 = farthest(ld3(H.v + 3 * i0)), i2 = farthest(ld3(H.v + 3 * i1));
+    const V3 v0 = ld3(H.v + 3 * i2), v1 = ld3(H.v + 3 * i1);  // a diameter of the active set
+    const V3 e01 = v1 - v0;
+    const double len = sqrt(dot(e01, e01));
+    if (cnt == 1 || !(len > 1e-9)) {
+      hv[nh++] = xform(H.T, ld3(H.v + 3 * i0));
+    } else {
+      V3 v2 = v0, c2 = v3(0, 0, 0);
+      double area = 0;
+      for (int i = 0; i < H.nv; ++i) {
+        const V3 v = ld3(H.v + 3 * i);
+        if (!(dot(v, nl) >= hmax - kRwSlab)) continue;
+        const V3 c = cross(e01, v - v0);
+        if (dot(c, c) > area) {
+          area = dot(c, c);
+          v2 = v;
+          c2 = c;
+        }
+      }
+      const bool line = !(sqrt(area) > kRwFlat * len);  // every active vertex within kRwFlat of the line
+      if (!line) {
+        c2 = (1.0 / sqrt(area)) * c2;
+        for (int i = 0; i < H.nv; ++i) {
+          const V3 v = ld3(H.v + 3 * i);
+          if (dot(v, nl) >= hmax - kRwSlab && fabs(dot(c2, v - v0)) > kRwFlat) return false;  // not one face
+        }
+      }
+      hv[nh++] = xform(H.T, v0);
+      hv[nh++] = xform(H.T, v1);
+      if (!line) hv[nh++] = xform(H.T, v2);
+    }
+  }
+  if (nh < 1) return false;
+  // the thin box: eps thick (any thickness above rw_classify's kRwTau will do, whatever the hull's size);
+  // a face is a plane: half extents far beyond any hull
+  const double eps = 1e-3, big = 1e6;
+  V3 ex, ey, ez, org, nf = v3(0, 0, 0);
+  double hx, hy, hz;
+  if (nh == 3) {
+    nf = cross(hv[1] - hv[0], hv[2] - hv[0]);
+    const double a2 = sqrt(dot(nf, nf));
+    const V3 e01 = hv[1] - hv[0];
+    if (!(a2 > 1e-12) || !(dot(e01, e01) > 1e-18)) return false;
+    nf = (1.0 / a2) * nf;
+    if (dot(nf, n0) < 0) nf = -1.0 * nf;
+    ex = (1.0 / sqrt(dot(e01, e01))) * e01;
+    ez = nf;
+    ey = cross(ez, ex);
+    org = hv[0] - eps * ez;
+    hx = hy = big;
+    hz = eps;
+  } else if (nh == 2) {
+    const V3 e01 = hv[1] - hv[0];
+    const double len = sqrt(dot(e01, e01));
+    ex = (1.0 / len) * e01;
+    V3 pp = n0 - dot(n0, ex) * ex;
+    const double lp = sqrt(dot(pp, pp));
+    if (!(lp > 1e-6)) return false;
+    pp = (1.0 / lp) * pp;
+    const V3 r = cross(ex, pp);
+    const double c2 = 0.70710678118654752;
+    ey = c2 * (pp - r);
+    ez = c2 * (pp + r);
+    org = 0.5 * (hv[0] + hv[1]) - eps * (ey + ez);
+    hx = 0.5 * len;
+    hy = hz = eps;
+  } else {
+    const V3 a = fabs(n0.x) < 0.9 ? v3(1, 0, 0) : v3(0, 1, 0);
+    V3 u = a - dot(a, n0) * n0;
+    u = (1.0 / sqrt(dot(u, u))) * u;
+    const V3 w = cross(n0, u);
+    const double c3 = 0.57735026918962576, c23 = 0.81649658092772603, sn = 0.86602540378443865;
+    ex = c3 * n0 + c23 * u;
+    ey = c3 * n0 + c23 * (-0.5 * u + sn * w);
+    ez = c3 * n0 + c23 * (-0.5 * u - sn * w);
+    org = hv[0] - eps * (ex + ey + ez);
+    hx = hy = hz = eps;
+  }
+  // the box laid onto the feature, and the cylinder, with poses in registers
+  double TF[12], TC[12];
+  TF[0] = ex.x; TF[1] = ey.x; TF[2] = ez.x;
+  TF[3] = ex.y; TF[4] = ey.y; TF[5] = ez.y;
+  TF[6] = ex.z; TF[7] = ey.z; TF[8] = ez.z;
+  TF[9] = org.x; TF[10] = org.y; TF[11] = org.z;
+  for (int i = 0; i < 12; ++i) TC[i] = Cy.T[i];
+  const Shape F{kBox, TF, hx, hy, hz}, C{kCylinder, TC, Cy.p0, Cy.p1, Cy.p2};
+  double dn = *d;
+  // start on the feature itself (EPA's hull witness can sit ~1e-4 inside it)
+  V3 qH = pH, qC = pC;
+  if (nh == 3) qH = pH - dot(pH - hv[0], nf) * nf;
+  else if (nh == 2) qH = hv[0] + dot(pH - hv[0], ex) * ex;
+  else qH = hv[0];
+  if (!refine_witness(F, C, &dn, &qH, &qC)) return false;
+  if ((dn > 0) != (*d > 0)) return false;
+  // accept only a critical point of the hull itself
+  const V3 n2 = (1.0 / dn) * (qC - qH);
+  const V3 n2l = rotT(H.T, n2), xl = rotT(H.T, qH - v3(H.T[9], H.T[10], H.T[11]));
+  const double h2 = dot(xl, n2l);
+  for (int i = 0; i < H.nv; ++i)
+    if (dot(ld3(H.v + 3 * i), n2l) > h2 + 1e-9) return false;
+  if (nh == 3) {  // inside the face polygon: every line through the point and a face vertex has vertices on both sides
+    const V3 nfl = rotT(H.T, nf);
+    for (int i = 0; i < H.nv; ++i) {
+      const V3 vi = ld3(H.v + 3 * i);
+      if (!(dot(vi, n2l) >= h2 - 1e-7)) continue;
+      bool pos = false, neg = false;
+      for (int j = 0; j < H.nv; ++j) {
+        const V3 vj = ld3(H.v + 3 * j);
+        if (!(dot(vj, n2l) >= h2 - 1e-7)) continue;
+        const double sd = dot(nfl, cross(vi - xl, vj - xl));
+        pos |= sd > 1e-14;
+        neg |= sd < -1e-14;
+      }
+      if (!(pos && neg)) return false;
+    }
+  }
+  *d = dn;
+  *pA = hull_is_a ? qH : qC;
+  *pB = hull_is_a ? qC : qH;
+  return true;
+}
+// refine_witness for shapes that may be hulls (the task stage's winner)
+template <class SH>
+DRC_HD inline bool refine_witness_hull(const SH& A, const SH& B, double* d, V3* pA, V3* pB) {
+  static_assert(SH::kHasMesh && !SH::kCoop, "one lane refines: serial shapes");
+  if (A.type != kMesh && B.type != kMesh) return refine_witness(A, B, d, pA, pB);
+  if ((A.type == kMesh && B.type == kCylinder) || (B.type == kMesh && A.type == kCylinder))
+    return refine_hull_cylinder(A, B, d, pA, pB);
+  return false;  // two polytopes, or a sphere's centre: GJK ended exactly
 }
 
 // Lower bound on the distance of two geometries via their swept cores:

@@ -25,7 +25,8 @@ namespace drc_amd {
 // three-wave build (168 VGPRs, more spills) for models whose LDS plan lets a
 // CU hold more than the 8 waves the two-wave build can (FR3, UR5e); where the
 // plan allows only 8 it loses 1.6-3 % to the spills (profiles/r04j_ab_lds.jsonl)
-template <int PROBLEM, int WAVES = DRC_TASK_WAVES>
+// MESH: the build for models with convex-hull geometry (task_stage.hpp)
+template <int PROBLEM, int WAVES = DRC_TASK_WAVES, bool MESH = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
 task_kernel(const DevModel* __restrict__ M0, const KParams kp, const IO io) {
   extern __shared__ __attribute__((aligned(16))) double S[];
@@ -40,7 +41,7 @@ task_kernel(const DevModel* __restrict__ M0, const KParams kp, const IO io) {
     const int64_t b = hard_mode ? jj : io.ordered(jj);
     if (PROBLEM == 0) stage_stamp(io, ST_TASK0, io.b0 + b);
     if (PROBLEM == 0) stage_where(io, ST_WTASK, io.b0 + b);
-    task_instance<PROBLEM>(M0, kp, io, S, b);
+    task_instance<PROBLEM, MESH>(M0, kp, io, S, b);
     if (PROBLEM == 0) stage_stamp(io, ST_TASK1, io.b0 + b);
   }
 }
@@ -62,9 +63,13 @@ int task_waves_per_simd(int problem, size_t lds) {
 }
 
 int launch_task_kernel(int problem, unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
-                       const IO& io) {
+                       const IO& io, bool mesh) {
   const bool w3 = task_waves_per_simd(problem, lds) == 3 && DRC_TASK_WAVES != 3;
-  if (problem == 0 && w3)
+  if (mesh && problem == 0)  // (one build for hull models: the two-wave register budget)
+    hipLaunchKernelGGL((task_kernel<0, DRC_TASK_WAVES, true>), dim3(grid), dim3(64), lds, st, m, kp, io);
+  else if (mesh && problem == 1)
+    hipLaunchKernelGGL((task_kernel<1, DRC_TASK_WAVES, true>), dim3(grid), dim3(64), lds, st, m, kp, io);
+  else if (problem == 0 && w3)
     hipLaunchKernelGGL((task_kernel<0, 3>), dim3(grid), dim3(64), lds, st, m, kp, io);
   else if (problem == 0)
     hipLaunchKernelGGL(task_kernel<0>, dim3(grid), dim3(64), lds, st, m, kp, io);

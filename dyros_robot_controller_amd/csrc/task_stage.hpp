@@ -383,7 +383,9 @@ __device__ __noinline__ void closed_form_stage(const DevModel* M, const KParams&
 
 // One instance b of the task stage on this wave (S: the wave's LDS plan kp).
 // PROBLEM 0: QPIK stage data; 1: also the QPID extras; 2: closed-form CLIK / OSF.
-template <int PROBLEM>
+// MESH: the model has convex-hull geometry (GeomType kMesh).  A build of its
+// own, chosen at launch, so the kernels of mesh-free models carry none of it.
+template <int PROBLEM, bool MESH = false>
 __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, const KParams& kp, const IO& io, double* S,
                                               int64_t b) {
   const int l = lane_id();
@@ -689,12 +691,29 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   double ub = 1e300;
   // slots in type-class order (model.cpp pair_order): each round of 64 lanes
   // runs one or two pair types instead of all of them
+  // (MESH) a hull with its pose, for the whole wave; the broad phase takes a
+  // hull for its bounding box (gparam: a lower bound on the box holds for the
+  // hull inside it, penetration included)
+  [[maybe_unused]] auto hull_shape = [&](int g) {
+    return ShapeMT<lds_pose*, true>{M->gtype[g], (lds_pose*)(Tg + 12 * g), M->gparam[g][0], M->gparam[g][1],
+                                    M->gparam[g][2], M->mesh_verts + 3 * M->gmesh_first[g], M->gmesh_count[g]};
+  };
   for (int sl = l; sl < M->npairs; sl += 64) {
     const int p = M->pair_order[sl], ga = M->slot_a[sl], gb = M->slot_b[sl];
     ShapeL A{M->gtype[ga], (lds_pose*)(Tg + 12 * ga), M->gparam[ga][0], M->gparam[ga][1], M->gparam[ga][2]};
     ShapeL Bs{M->gtype[gb], (lds_pose*)(Tg + 12 * gb), M->gparam[gb][0], M->gparam[gb][1], M->gparam[gb][2]};
     V3 pA, pB;
     double d;
+    if constexpr (MESH) {
+      if (A.type == kMesh || Bs.type == kMesh) {  // bound on the bounding box(es); the narrow phase is gjk_wave
+        if (A.type == kMesh) A.type = kBox;
+        if (Bs.type == kMesh) Bs.type = kBox;
+        pd[p] = (A.type == kSphere || Bs.type == kSphere) ? sphere_pair(A, Bs, &pA, &pB)
+                                                          : pair_lower_bound(A, Bs, M->gbound[ga], M->gbound[gb]);
+        pf[p] = 0;
+        continue;
+      }
+    }
     const bool closed = (A.type == kSphere || Bs.type == kSphere)
                             ? (d = sphere_pair(A, Bs, &pA, &pB), true)
                             : (A.type == kCylinder && Bs.type == kCylinder && cyl_cyl_side(A, Bs, &d, &pA, &pB));
@@ -722,9 +741,17 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   {
     int* cand = reinterpret_cast<int*>(S + kp.kCand);
     int ncand = 0;
+    [[maybe_unused]] int nhull = 0;  // (MESH) pairs with a hull: a second list, from the buffer's end down
     for (int p0 = 0; p0 < M->npairs; p0 += 64) {
       const int p = p0 + l;
-      const bool c = p < M->npairs && pf[p] == 0 && pd[p] - 1e-9 <= ub;
+      bool c = p < M->npairs && pf[p] == 0 && pd[p] - 1e-9 <= ub;
+      if constexpr (MESH) {
+        const bool h = c && (M->gtype[M->pair_a[p]] == kMesh || M->gtype[M->pair_b[p]] == kMesh);
+        const unsigned long long mh = __ballot(h);
+        if (h) cand[M->npairs - 1 - (nhull + __popcll(mh & ((1ull << l) - 1)))] = p;
+        nhull += __popcll(mh);
+        c = c && !h;
+      }
       const unsigned long long m = __ballot(c);
       if (c) cand[ncand + __popcll(m & ((1ull << l) - 1))] = p;
       ncand += __popcll(m);
@@ -751,6 +778,43 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
           bhow = 1;
           bpA = g.pA;
           bpB = g.pB;
+        }
+      }
+    }
+    if constexpr (MESH) {
+      // pairs with a hull, one at a time on the whole wave (gjk_wave), in
+      // pair order.  Every distance found so far tightens the cut.  Lane
+      // p & 63 keeps the pair's result, as it does for EPA below.  A sphere
+      // is its centre here, with the radius taken off afterwards; a centre
+      // inside the hull goes to EPA like any overlap.  Two polytopes (hull,
+      // box, a sphere's centre) end exactly, with the repeated support point
+      // (tol 0); a hull against a cylinder stops like the primitives and is
+      // refined if it wins (refine_witness_hull).
+      ub = fmin(ub, -wave_max(-bestd));
+      for (int c = 0; c < nhull; ++c) {
+        const int p = cand[M->npairs - 1 - c];
+        const int ga = M->pair_a[p], gb = M->pair_b[p];
+        const auto A = hull_shape(ga), Bs = hull_shape(gb);
+        const double rs = A.type == kSphere ? A.p0 : (Bs.type == kSphere ? Bs.p0 : 0.0);
+        const bool poly = A.type != kCylinder && Bs.type != kCylinder;
+        const GjkDist g = gjk_wave(A, Bs, ub + 1e-9 + rs, poly ? 0.0 : kGjkTol, ews, p);
+        if (g.intersect) {
+          pen = true;
+          if (l == 0) pf[p] = 2;
+          continue;
+        }
+        if (l == 0) pf[p] = 1;
+        if (g.pruned) continue;
+        double d = g.dist;
+        V3 pA = g.pA, pB = g.pB;
+        if (rs > 0) sphere_hull_witness(A.type == kSphere, rs, &d, &pA, &pB);
+        ub = fmin(ub, d);
+        if (l == (p & 63) && (d < bestd || (d == bestd && p < besti))) {
+          bestd = d;
+          besti = p;
+          bhow = 1;
+          bpA = pA;
+          bpB = pB;
         }
       }
     }
@@ -791,7 +855,25 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       const ShapeL Bs{M->gtype[gb], (lds_pose*)(Tg + 12 * gb), M->gparam[gb][0], M->gparam[gb][1], M->gparam[gb][2]};
       PH_ONLY(epa_calls++; unsigned long long est[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};)
       const int sk = p == sp0 ? 0 : (p == sp1 ? 1 : -1);
-      const double dall = epa_run_wave(A, Bs, ews, ln, sk, sk == 0 ? sn0 : sn1 PH_ONLY(, est));
+      double dall_;
+      if constexpr (MESH) {  // the same EPA with the hulls' cooperative support
+        dall_ = epa_run_wave(hull_shape(ga), hull_shape(gb), ews, ln, sk, sk == 0 ? sn0 : sn1 PH_ONLY(, est));
+        const double rs = A.type == kSphere ? A.p0 : (Bs.type == kSphere ? Bs.p0 : 0.0);
+        if (rs > 0) {  // sphere centre inside a hull: the radius comes off, the sphere's witness moves out
+          wsync();
+          V3 wA = ld3(ews->out), wB = ld3(ews->out + 3);
+          sphere_hull_witness(A.type == kSphere, rs, &dall_, &wA, &wB);
+          wsync();
+          if (l == ln) {
+            st3(ews->out, wA);
+            st3(ews->out + 3, wB);
+          }
+          wsync();
+        }
+      } else {
+        dall_ = epa_run_wave(A, Bs, ews, ln, sk, sk == 0 ? sn0 : sn1 PH_ONLY(, est));
+      }
+      const double dall = dall_;
       if (ews->nv > kEpaStashV0) sp0 = sp1 = -1;  // grown into the stash slots
       PH_ONLY(epa_steps += est[0]; if (est[0] > epa_maxsteps) epa_maxsteps = est[0];
               epa_t[0] += est[1]; epa_t[1] += est[2]; epa_t[2] += est[3];
@@ -831,6 +913,16 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     const ShapeL Bs{M->gtype[gb], (lds_pose*)(Tg + 12 * gb), M->gparam[gb][0], M->gparam[gb][1], M->gparam[gb][2]};
     double dref = S[kp.oSc + SC_DIST];
     V3 rA = ld3(red), rB = ld3(red + 3);
+    if constexpr (MESH) {
+      if (A.type == kMesh || Bs.type == kMesh) {  // a pair with a hull (refine_witness_hull)
+        if (refine_witness_hull(serial_shape(hull_shape(ga)), serial_shape(hull_shape(gb)), &dref, &rA, &rB)) {
+          st3(red, rA);
+          st3(red + 3, rB);
+          S[kp.oSc + SC_DIST] = dref;
+        }
+        return;
+      }
+    }
 #ifdef DRC_NO_REFINE  // diagnostic build: the raw GJK / EPA witnesses
     if (false && refine_witness(A, Bs, &dref, &rA, &rB)) {
 #else

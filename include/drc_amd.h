@@ -121,7 +121,15 @@ typedef struct drc_model drc_model;     /* opaque; owns its device copy */
 
 /* Manipulator::RobotData(urdf, srdf, packages)  manipulator/robot_data.h:49,
  * robot_data.cpp:7-70 (model, collision pairs, limits).  `device` = HIP
- * device ordinal that receives the model constants. */
+ * device ordinal that receives the model constants.
+ * Collision geometry: sphere, cylinder, box, and <mesh filename= scale=>
+ * (binary / ASCII STL, OBJ), which becomes the convex hull of its vertices
+ * (drc_mesh_convex_hull).  packages_path: package://a/b.stl is read from
+ * <packages_path>/a/b.stl; file:// and absolute paths as given, relative
+ * paths against the URDF's directory.  NULL or "" is fine unless a
+ * package:// URI occurs.  A mesh file that is missing (DRC_ERR_FILE), of
+ * another format or degenerate (DRC_ERR_UNSUPPORTED) fails the build with the
+ * link and the file in drc_last_error(). */
 int drc_model_create_manipulator(const char* urdf_path, const char* srdf_path,
                                  const char* packages_path, int device, drc_model** out);
 
@@ -140,6 +148,28 @@ void drc_model_destroy(drc_model* model);
  * collision model size (geometries, active pairs). */
 int drc_model_info(const drc_model* model, int* dof, int* actuated_dof, int* mani_dof,
                    int* mobi_dof, int* n_geoms, int* n_pairs);
+
+/* Collision geometry `geom` (0 .. n_geoms-1): *type 0 sphere, 1 cylinder, 2 box,
+ * 3 mesh (convex hull); param: sphere r | cylinder r, h/2 | box half extents |
+ * mesh: half extents of the hull's bounding box; *n_vertices: hull vertices
+ * (0 for primitives); *hull_residual: 0 for a full hull, else what the
+ * 256-vertex cap left out (drc_mesh_convex_hull).  Outputs may be NULL. */
+int drc_model_geom_info(const drc_model* model, int geom, int* type, double param[3],
+                        int* n_vertices, double* hull_residual);
+
+/* What a collision mesh file turns into (host only, no device is touched; the
+ * model build calls the same code).  Reads a binary / ASCII STL or an OBJ
+ * (`v` lines), multiplies by scale (NULL: 1 1 1) and returns the vertices of
+ * the convex hull in file order: verts_out [cap][3], *n_out their number.
+ * max_vertices (<= 0: 256, the model's per-mesh cap; else >= 4): a hull with
+ * more vertices is cut short by stopping quickhull's farthest-point insertion
+ * there -- a subset of the hull's vertices, hence an inner approximation --
+ * and *residual_out is the largest distance of a left-out vertex from the
+ * reduced hull (0 otherwise).  DRC_ERR_FILE: missing / unreadable file;
+ * DRC_ERR_UNSUPPORTED: another format (Collada, ...) or fewer than four
+ * non-coplanar vertices; DRC_ERR_SIZE_MISMATCH: cap too small (*n_out set). */
+int drc_mesh_convex_hull(const char* path, const double scale[3], int max_vertices,
+                         double* verts_out, int cap, int* n_out, double* residual_out);
 
 /* getJointPositionLimit / getJointVelocityLimit (robot_data.h) — host arrays [dof] */
 int drc_model_limits(const drc_model* model, double* q_lb, double* q_ub, double* qdot_lb,
