@@ -60,6 +60,67 @@ def qpik_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=N
     return out, status
 
 
+ROLLOUT_FIELDS = ("qdot_traj", "iters_traj", "q_traj", "pose_traj", "dist_traj")
+
+
+class RolloutResult:
+    """Device tensors of one ``drc_qpik_rollout_batch`` call: ``q_final``,
+    ``qdot_final`` [dof][B], ``status_traj`` [steps][B], and those of
+    ``qdot_traj`` [steps][na][B], ``iters_traj`` [steps][B], ``q_traj``
+    [steps][dof][B], ``pose_traj`` [steps][12][B], ``dist_traj``
+    [steps][1+dof][B] that were asked for (None otherwise)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def qpik_rollout_batch(model, params, q, qdot, steps, dt, x_target=None, xdot_target=None, x_init=None,
+                       xdot_init=None, targets_per_step=False, want=("qdot_traj", "q_traj"), q_final=None,
+                       qdot_final=None, stream=None):
+    """Launch ``drc_qpik_rollout_batch`` on device tensors laid out [field][B]
+    (per-step targets: [steps][field][B]).  ``want``: the optional
+    trajectories to allocate and fill (ROLLOUT_FIELDS); ``q_final`` /
+    ``qdot_final`` may be given (``q`` / ``qdot`` themselves: in place)."""
+    torch = _torch()
+    dev = q.device
+    B = q.shape[1]
+    steps = int(steps)
+    nv, na = model.dof, model.actuated_dof
+    check_shapes(nv, B, q=q, qdot=qdot, x_init=x_init, xdot_init=xdot_init)
+    unknown = set(want) - set(ROLLOUT_FIELDS)
+    if unknown:
+        raise ValueError("unknown rollout outputs %s (know %s)" % (sorted(unknown), ROLLOUT_FIELDS))
+    if targets_per_step:
+        for name, t, rows in (("x_target", x_target, 12), ("xdot_target", xdot_target, 6)):
+            if t is not None and tuple(t.shape) != (steps, rows, B):
+                raise ValueError("%s must be [steps=%d][%d][B=%d], got %s" % (name, steps, rows, B, tuple(t.shape)))
+    else:
+        check_shapes(nv, B, x_target=x_target, xdot_target=xdot_target)
+    for name, t in (("q_final", q_final), ("qdot_final", qdot_final)):
+        if t is not None and (tuple(t.shape) != (nv, B) or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 [%d][B=%d] tensor" % (name, nv, B))
+    n = max(steps, 0)
+    f = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    res = RolloutResult(
+        q_final=f(nv, B) if q_final is None else q_final,
+        qdot_final=f(nv, B) if qdot_final is None else qdot_final,
+        status_traj=i(n, B),
+        qdot_traj=f(n, na, B) if "qdot_traj" in want else None,
+        iters_traj=i(n, B) if "iters_traj" in want else None,
+        q_traj=f(n, nv, B) if "q_traj" in want else None,
+        pose_traj=f(n, 12, B) if "pose_traj" in want else None,
+        dist_traj=f(n, 1 + nv, B) if "dist_traj" in want else None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(_capi.lib().drc_qpik_rollout_batch(
+        model.handle, C.byref(params), C.c_int64(B), C.c_int(steps), C.c_double(dt), _ptr(q), _ptr(qdot),
+        _ptr(x_target), _ptr(xdot_target), _ptr(x_init), _ptr(xdot_init), C.c_int(1 if targets_per_step else 0),
+        _ptr(res.q_final), _ptr(res.qdot_final), _ptr(res.qdot_traj), _ptr(res.status_traj), _ptr(res.iters_traj),
+        _ptr(res.q_traj), _ptr(res.pose_traj), _ptr(res.dist_traj), C.c_void_p(stream)))
+    return res
+
+
 def qpid_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
                qddot=None, tau=None, status=None, iters=None, stream=None):
     """Launch ``drc_qpid_batch``: returns (qddot [na][B],

@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "drc_default_qpid_params", "drc_qpid_batch", "drc_qpid_stages_batch", "drc_qpid_host",
     "drc_qpid_stages_host", "drc_clik_batch", "drc_osf_batch", "drc_closed_form_host",
     "drc_error_string", "drc_last_error", "drc_build_id", "drc_qpik_host_timed", "drc_kinematics_batch",
-    "drc_state_host", "drc_model_geom_info", "drc_mesh_convex_hull",
+    "drc_state_host", "drc_model_geom_info", "drc_mesh_convex_hull", "drc_qpik_rollout_batch",
 )
 
 
@@ -141,6 +141,9 @@ def _load():
     lib.drc_qpik_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.drc_qpik_stages_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "drc_qpik_rollout_batch"):  # absent from older A/B builds
+        lib.drc_qpik_rollout_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int, C.c_double,
+                                               vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.drc_debug_kernel_timing.argtypes = [vp, C.c_int]
     # diagnostics added in r05: bound only when present, so A/B runs can load
     # an older build (tests/test_capi_symbols.py checks the product exports them)
@@ -184,7 +187,7 @@ def _load():
     for name in EXPORTED_SYMBOLS:
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
                     "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info",
-                    "drc_mesh_convex_hull") and not hasattr(lib, name):
+                    "drc_mesh_convex_hull", "drc_qpik_rollout_batch") and not hasattr(lib, name):
             continue  # diagnostics an older A/B build may lack
         if name not in ("drc_model_destroy", "drc_error_string", "drc_last_error", "drc_build_id"):
             getattr(lib, name).restype = C.c_int

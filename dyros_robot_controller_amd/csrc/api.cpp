@@ -51,6 +51,8 @@ struct StreamCtx {
   int* d_queue = nullptr;
   int* dyn_list = nullptr;  // instances whose M_inv needs the serial COD
   int64_t dyn_list_cap = 0;
+  void* roll = nullptr;  // rollouts without qdot_traj: one step's eta [na][B]
+  int64_t roll_bytes = 0;
 };
 constexpr size_t kMaxStreamCtx = 8;
 
@@ -145,6 +147,9 @@ static void free_ctx(StreamCtx* c) {
   if (c->d_queue) (void)hipFree(c->d_queue);
   if (c->pool) (void)hipFree(c->pool);
   if (c->dyn_list) (void)hipFree(c->dyn_list);
+  if (c->roll) (void)hipFree(c->roll);
+  c->roll = nullptr;
+  c->roll_bytes = 0;
   c->d_queue = nullptr;
   c->pool = nullptr;
   c->dyn_list = nullptr;
@@ -660,13 +665,13 @@ static int make_kparams(const drc_model_impl* mm, const drc_qpik_params* p, int 
   return plan_layout(M, k, stages != 0);
 }
 
-static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int stages, int64_t B, const double* q,
-                  const double* qdot, const double* xt, const double* xdt, const double* xi, const double* xdi,
-                  double* out, int32_t* status, int32_t* iters, double* pose, double* jac, double* man,
-                  double* dist, int32_t* pair, double* xdd, void* stream, uint64_t* stamps = nullptr) {
-  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
-  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
-  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+// (the caller holds m->launch_mu: launch() for one call, the stepwise rollout
+// for its whole sequence of steps)
+static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int stages, int64_t B, const double* q,
+                         const double* qdot, const double* xt, const double* xdt, const double* xi,
+                         const double* xdi, double* out, int32_t* status, int32_t* iters, double* pose, double* jac,
+                         double* man, double* dist, int32_t* pair, double* xdd, void* stream,
+                         uint64_t* stamps = nullptr) {
   if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   if (B == 0) return DRC_OK;
   if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
@@ -925,6 +930,130 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
     std::vector<hipEvent_t> ev = S > 1 ? tev : std::vector<hipEvent_t>{t0e, t2e, t0e, t1e, t2e};
     std::lock_guard<std::mutex> g(m->mu);
     m->events.push_back({ev, S});
+  }
+  done_guard.ok = true;
+  return DRC_OK;
+}
+
+static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int stages, int64_t B, const double* q,
+                  const double* qdot, const double* xt, const double* xdt, const double* xi, const double* xdi,
+                  double* out, int32_t* status, int32_t* iters, double* pose, double* jac, double* man,
+                  double* dist, int32_t* pair, double* xdd, void* stream, uint64_t* stamps = nullptr) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  return launch_locked(m, params, stages, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, pose, jac, man, dist,
+                       pair, xdd, stream, stamps);
+}
+
+// t_k = t + k dt as a rounded product and a rounded sum (the persistent
+// kernel's rollout_time, rollout_kernel.hip)
+static double rollout_time(double t, int k, double dt) {
+  volatile double d = static_cast<double>(k) * dt;
+  return t + d;
+}
+
+// drc_qpik_rollout_batch: `steps` control cycles (QPIK*, then the state
+// update) enqueued on the caller's stream.  The compiled QP shapes up to
+// rollout_max instances run the persistent kernel (rollout_kernel.hip: one
+// launch, every instance's whole horizon on one wave); everything else runs
+// step by step: drc_qpik_batch's launch sequence (and, for pose_traj /
+// dist_traj, the stage launch) followed by the integrate kernel, q_final /
+// qdot_final carrying the state.  Same device functions either way: identical
+// bits (tests/test_gpu_rollout.py).
+static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int steps, double dt,
+                   const double* q0, const double* qdot0, const double* xt, const double* xdt, const double* xi,
+                   const double* xdi, int per_step, double* qf, double* vf, double* qdot_traj, int32_t* status_traj,
+                   int32_t* iters_traj, double* q_traj, double* pose_traj, double* dist_traj, void* stream) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  if (steps < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "steps must be at least 1");
+  if (!std::isfinite(dt) || !(dt > 0)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
+  if (per_step != 0 && per_step != 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "targets_per_step must be 0 or 1");
+  if (per_step && params->mode == DRC_MODE_QPIK_CUBIC)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "per-step targets with QPIKCubic: the time already moves the target");
+  if (!qf || !vf || !status_traj)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "q_final, qdot_final and status_traj are required");
+  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
+  if (B > 0) {
+    if (!q0 || !qdot0 || !xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0 and xdot_target are required");
+    if (params->mode != DRC_MODE_QPIK && !xt)
+      return set_err(DRC_ERR_INVALID_ARGUMENT, "x_target required for QPIKStep/QPIKCubic");
+    if (params->mode == DRC_MODE_QPIK_CUBIC && (!xi || !xdi))
+      return set_err(DRC_ERR_INVALID_ARGUMENT, "x_init/xdot_init required for QPIKCubic");
+  }
+  KParams kt, kq;
+  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
+  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (B == 0) return DRC_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DevModel& dm = m->hm.dev;
+  const int nv = dm.nv, na = kq.na;
+  // The fusion rule (launch_locked) selects the persistent kernel, up to the
+  // batch size where it was measured to beat the stepwise path at 32 steps
+  // (profiles/rollout_bench.json, DESIGN.md "Rollouts"): manipulators (FR3)
+  // through 4 096 instances -- from 8 192 on the stepwise path's fused calls
+  // with their EPA-first order win, 10.8 against 12.4 ms -- and whole-body
+  // robots (Husky-FR3) at every size measured, through 65 536 (92.8 against
+  // 133.2 ms).  DRC_ROLLOUT_MAX overrides (read per call, so that one process
+  // can measure both paths)
+  const int64_t rollout_max = env_int("DRC_ROLLOUT_MAX", dm.kind == 0 ? 4096 : 65536, 0);
+  const bool persistent = m->fused && m->lane_stage == 0 && B <= rollout_max && kQpGroup == 64 &&
+                          qp_compiled(kq.nx, kq.ng, kq.np);
+  StreamCtx* cx = nullptr;
+  DoneGuard done_guard{cx, st};
+  double* eta = qdot_traj;  // without qdot_traj: one step's eta in stream scratch
+  {
+    std::lock_guard<std::mutex> g(m->mu);
+    if (int r = stream_ctx(m, st, &cx)) return r;
+    if (!qdot_traj) {
+      const int64_t bytes = int64_t(na) * B * 8;
+      if (cx->roll_bytes < bytes) {
+        if (cx->roll) HIP_TRY(hipFree(cx->roll));  // synchronises: no launch still uses it
+        cx->roll = nullptr;
+        cx->roll_bytes = 0;
+        HIP_TRY(hipMalloc(&cx->roll, bytes));
+        cx->roll_bytes = bytes;
+      }
+      eta = static_cast<double*>(cx->roll);
+    }
+  }
+  const int64_t out_step = qdot_traj ? int64_t(na) * B : 0;
+  if (persistent) {
+    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
+    const int64_t grid = B < cap ? B : cap;
+    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
+    IO io{B, 0, B, q0, qdot0, xt, xdt, xi, xdi, eta, status_traj, iters_traj, nullptr, nullptr, nullptr, nullptr,
+          nullptr, nullptr, nullptr, 0};
+    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
+    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+    HIP_TRY(static_cast<hipError_t>(launch_rollout_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io,
+                                                          steps, per_step, dt, qf, vf, q_traj, pose_traj, dist_traj,
+                                                          out_step, dm.has_mesh != 0)));
+    done_guard.ok = true;
+    return DRC_OK;
+  }
+  for (int k = 0; k < steps; ++k) {
+    drc_qpik_params pk = *params;
+    pk.t = rollout_time(params->t, k, dt);
+    const double *qk = k ? qf : q0, *vk = k ? vf : qdot0;
+    const double* xt_k = per_step && xt ? xt + int64_t(k) * 12 * B : xt;
+    const double* xdt_k = per_step ? xdt + int64_t(k) * 6 * B : xdt;
+    double* eta_k = eta + k * out_step;
+    if (pose_traj || dist_traj)
+      if (int rc = launch_locked(m, &pk, 1, B, qk, vk, xt_k, xdt_k, xi, xdi, nullptr, nullptr, nullptr,
+                                 pose_traj ? pose_traj + int64_t(k) * 12 * B : nullptr, nullptr, nullptr,
+                                 dist_traj ? dist_traj + int64_t(k) * (1 + nv) * B : nullptr, nullptr, nullptr, stream))
+        return rc;
+    if (int rc = launch_locked(m, &pk, 0, B, qk, vk, xt_k, xdt_k, xi, xdi, eta_k, status_traj + int64_t(k) * B,
+                               iters_traj ? iters_traj + int64_t(k) * B : nullptr, nullptr, nullptr, nullptr, nullptr,
+                               nullptr, nullptr, stream))
+      return rc;
+    HIP_TRY(static_cast<hipError_t>(launch_rollout_integrate_kernel(
+        B, st, m->d_model, dt, qk, eta_k, qf, vf, q_traj ? q_traj + int64_t(k) * nv * B : nullptr)));
   }
   done_guard.ok = true;
   return DRC_OK;
@@ -1573,6 +1702,15 @@ int drc_qpik_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, cons
                    int32_t* status, int32_t* iters, void* stream) {
   return drc_amd::launch(m, p, 0, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, nullptr, nullptr, nullptr,
                          nullptr, nullptr, nullptr, stream);
+}
+
+int drc_qpik_rollout_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int steps, double dt,
+                           const double* q0, const double* qdot0, const double* xt, const double* xdt,
+                           const double* xi, const double* xdi, int targets_per_step, double* q_final,
+                           double* qdot_final, double* qdot_traj, int32_t* status_traj, int32_t* iters_traj,
+                           double* q_traj, double* pose_traj, double* dist_traj, void* stream) {
+  return drc_amd::rollout(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step, q_final, qdot_final,
+                          qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream);
 }
 
 int drc_qpik_stages_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,

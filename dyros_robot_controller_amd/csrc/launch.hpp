@@ -32,6 +32,20 @@ int launch_qpid_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel
 int launch_fused_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                         const KParams& kq, const IO& io, bool mesh = false);
 
+// persistent rollout kernel (rollout_kernel.hip; compiled QPIK shapes,
+// hipErrorInvalidValue otherwise): per instance `steps` times task stage, QP
+// and state update.  io as for launch_fused_kernel, with out / status / iters
+// the [steps][...] trajectories (out_step doubles between two steps' io.out);
+// qf / vf [dof][B] hold the state between steps; q_traj, pose_traj, dist_traj
+// may be NULL.  The LDS size follows from kt and kq
+int launch_rollout_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
+                          const IO& io, int steps, int per_step, double dt, double* qf, double* vf, double* q_traj,
+                          double* pose_traj, double* dist_traj, int64_t out_step, bool mesh);
+// one rollout step's state update for the stepwise path: v = S(q_in) eta,
+// qf = q_in + dt v (q_in may be qf), also into q_traj unless NULL
+int launch_rollout_integrate_kernel(int64_t B, hipStream_t st, const DevModel* m, double dt, const double* q_in,
+                                    const double* eta, double* qf, double* vf, double* q_traj);
+
 // queue order of one sub-batch (order_kernel.hip): penetration-prone
 // instances first (*hot_n zeroed; hot_list [B], hot_flag [B] scratch), then the
 // others in index order, into order[b0 .. b0 + B)

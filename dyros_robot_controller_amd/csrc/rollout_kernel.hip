@@ -1,0 +1,254 @@
+// Closed-loop QPIK rollouts (drc_qpik_rollout_batch): the reference's control
+// loop -- QPIK*, then q_desired = q + qdot_desired * dt
+// (examples/C++/src/fr3_controller.cpp:123-134) -- over a horizon of `steps`
+// cycles on the device.
+//
+// rollout_kernel: the persistent form for the compiled QP shapes, shaped like
+// fused_kernel.hip's kernel.  Each wave takes an instance from the work queue
+// and runs all its steps before the next: task stage (task_stage.hpp), QP
+// (qp_solver.hpp), state update.  The task record stays in LDS as in the fused
+// kernel; the state (q, v) lives in the caller's q_final / qdot_final arrays,
+// which task_instance reads through IO::q / IO::qdot from step 1 on: lane l
+// reads back the element lane l stored one step earlier (state_visible()).
+// Same device functions on the same values as drc_qpik_batch step by step, so
+// every step's result is bit-identical to it (tests/test_gpu_rollout.py).
+//
+// rollout_integrate_kernel: the state update alone, one thread per instance,
+// for the stepwise path (api.cpp: drc_qpik_batch's launch sequence per step,
+// then this kernel).  Both forms call rollout_velocity / rollout_advance, so
+// the two paths return identical bits.
+#include "task_stage.hpp"
+#include "qp_solver.hpp"
+#include "launch.hpp"
+
+namespace drc_amd {
+
+// v_{k+1} of joint row r.  Manipulator: eta.  Mobile manipulator: S(q_k) eta
+// with the selection matrix of mobile_manipulator/robot_data.cpp:22-25,115-120
+// -- identity on the arm and wheel rows, Rz(yaw) J_mobile on the virtual rows
+// (the products qp_assemble forms for J~ = J S).  eta(a): actuated entry a.
+template <class Eta>
+__device__ __forceinline__ double rollout_velocity(const DevModel* M, int r, double cy, double sy,
+                                                   const double (*Jm)[kMaxWheels], Eta eta) {
+  if (M->kind == 0) return eta(r);
+  const int a = r - M->mani_start, w = r - M->mobi_start, v = r - M->virtual_start;
+  if (a >= 0 && a < M->n_arm) return eta(M->act_mani_start + a);
+  if (w >= 0 && w < M->n_wheel) return eta(M->act_mobi_start + w);
+  if (v < 0 || v > 2) return 0.0;
+  double s = 0;
+  for (int c = 0; c < M->n_wheel; ++c) {
+    double sv;
+    if (v == 0) sv = cy * Jm[0][c] - sy * Jm[1][c];
+    else if (v == 1) sv = sy * Jm[0][c] + cy * Jm[1][c];
+    else sv = Jm[2][c];
+    s += sv * eta(M->act_mobi_start + c);
+  }
+  return s;
+}
+
+// q_{k+1} = q_k + dt v_{k+1}: a rounded product, then a rounded sum (never an
+// fma), so numpy's q + dt * v reproduces it bit for bit
+__device__ __forceinline__ double rollout_advance(double q, double dt, double v) {
+#pragma clang fp contract(off)
+  const double d = dt * v;
+  return q + d;
+}
+// t_k = t + k dt, rounded the same way (the host of the stepwise path: api.cpp)
+__device__ __forceinline__ double rollout_time(double t, int k, double dt) {
+#pragma clang fp contract(off)
+  const double d = static_cast<double>(k) * dt;
+  return t + d;
+}
+
+#ifndef DRC_ROLLOUT_MESH
+// Stepwise path: one thread per instance.  q_in may be qf (in place): the yaw
+// and the wheel positions are read before any row is written, and row r is
+// read before it is written.
+__global__ void __launch_bounds__(256)
+rollout_integrate_kernel(const DevModel* __restrict__ M, int64_t B, double dt, const double* q_in, const double* eta,
+                         double* qf, double* vf, double* q_traj) {
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (b >= B) return;
+  double Jm[3][kMaxWheels];
+  double cy = 1, sy = 0;
+  if (M->kind == 1) {
+    double wp[kMaxWheels];
+    for (int w = 0; w < kMaxWheels; ++w) wp[w] = w < M->n_wheel ? q_in[(M->mobi_start + w) * B + b] : 0.0;
+    mobile_fk(M, wp, Jm);
+    const double yaw = q_in[(M->virtual_start + 2) * B + b];
+    cy = cos(yaw);
+    sy = sin(yaw);
+  }
+  const auto e = [&](int a) { return eta[a * B + b]; };
+  for (int r = 0; r < M->nv; ++r) {
+    const double q = q_in[r * B + b];
+    const double v = rollout_velocity(M, r, cy, sy, Jm, e);
+    const double qn = rollout_advance(q, dt, v);
+    vf[r * B + b] = v;
+    qf[r * B + b] = qn;
+    if (q_traj) q_traj[r * B + b] = qn;
+  }
+}
+#endif
+
+// What the persistent kernel needs beyond IO
+struct Rollout {
+  int steps, per_step;  // per_step: targets are [steps][12 | 6][B]
+  double dt;
+  double *qf, *vf;  // q_final, qdot_final [dof][B]: the state between steps
+  double *q_traj, *pose_traj, *dist_traj;
+  int64_t out_step;  // doubles between two steps' eta in io.out (0: one scratch slot, no qdot_traj)
+};
+
+// LDS of the state update: q_k [nv], eta_k [na], J_mobile [3][kMaxWheels].
+// It lies at the start of the plan, not past it: once the QP has stored its
+// outputs nothing in the plan is live (the next task stage rewrites it from
+// the state arrays), so the kernel needs no more LDS than the fused kernel
+// and keeps its waves per CU (fused_rec_offset's comment).
+__host__ __device__ __forceinline__ int rollout_state_doubles(const KParams& kt, const KParams& kq) {
+  return ((kt.nv + 1) & ~1) + ((kq.na + 1) & ~1) + 3 * kMaxWheels;
+}
+
+// Orders this wave's global stores before its later loads of the same
+// addresses: the stores have completed when the wait returns, and a CU's
+// vector L1 is write-through, so the wave's own reload sees them.  (The IO
+// pointers are not __restrict__, so the compiler keeps the program order too.)
+__device__ __forceinline__ void state_visible() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+#ifndef DRC_FUSED_WAVES
+#define DRC_FUSED_WAVES 2
+#endif
+template <class QD, bool MESH = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
+rollout_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io, const Rollout ro) {
+  extern __shared__ __attribute__((aligned(16))) double S[];
+  PH_KSCOPE();
+  __shared__ KParams kpl;  // LDS copy of the QP parameters for the out-of-line ADMM blocks
+  {
+    static_assert(sizeof(KParams) % 8 == 0, "KParams copied as 8-byte words");
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(&kq);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&kpl);
+    for (int e = lane_id(); e < static_cast<int>(sizeof(KParams) / 8); e += 64) dst[e] = src[e];
+    wsync();
+  }
+  static_assert(QD::gs == 64, "the rollout kernel runs one instance per wave");
+  const int l = lane_id();
+  const int64_t B = io.B, LD = io.ld;
+  const int nv = kt.nv, na = kq.na;
+  IO iol = io;  // the record lives in LDS, as in fused_kernel
+  iol.rec = S + fused_rec_offset(kt, kq);
+  iol.rec_stride = 0;
+  double* qs = S;  // (rollout_state_doubles: dead plan space)
+  double* es = qs + ((nv + 1) & ~1);
+  double(*Jm)[kMaxWheels] = reinterpret_cast<double(*)[kMaxWheels]>(es + ((na + 1) & ~1));
+  const InstSeq seq(B, kq.xcd_map, io.queue);
+  for (int64_t j = seq.first(); j < seq.n; j = seq.next(j)) {
+    const int64_t b = seq.at(j);
+    if (b >= B) continue;
+    const int64_t gb = io.b0 + b;
+    for (int k = 0; k < ro.steps; ++k) {
+      IO is = iol;
+      if (k > 0) {
+        is.q = ro.qf;
+        is.qdot = ro.vf;
+      }
+      if (ro.per_step) {
+        if (is.xt) is.xt = io.xt + static_cast<int64_t>(k) * 12 * LD;
+        is.xdt = io.xdt + static_cast<int64_t>(k) * 6 * LD;
+      }
+      is.out = io.out + k * ro.out_step;
+      is.status = io.status + k * LD;
+      if (io.iters) is.iters = io.iters + k * LD;
+      KParams ktl = kt;  // this step's task parameters
+      ktl.t = rollout_time(kt.t, k, ro.dt);
+      task_instance<0, MESH>(M0, ktl, is, S, b);
+      wsync();
+      // stage outputs at q_k, in drc_qpik_stages_batch's layouts: the pose from
+      // the task plan (not overlaid before the QP starts), the distance from
+      // the record
+      if (ro.pose_traj && l < 12) {
+        const double* Te = S + kt.kTe;
+        ro.pose_traj[(static_cast<int64_t>(k) * 12 + l) * LD + gb] = l < 9 ? Te[(l % 3) * 3 + l / 3] : Te[l];
+      }
+      if (ro.dist_traj && l <= nv)
+        ro.dist_traj[(static_cast<int64_t>(k) * (1 + nv) + l) * LD + gb] = iol.rec[kt.rDist + l];
+      wsync();
+      qp_instance<QD>(M0, kq, kpl, is, S, b);
+      // ---------------- state update ----------------------------------------
+      state_visible();
+      const double qk = l < nv ? is.q[l * LD + gb] : 0.0;  // step 0: the caller's q0 (q_final may alias it)
+      if (l < nv) qs[l] = qk;
+      if (l < na) es[l] = is.out[l * LD + gb];
+      wsync();
+      const DevModel* M = opaque_model(M0);
+      double cy = 1, sy = 0;
+      if (M->kind == 1) {
+        if (l == 0) mobile_fk(M, qs + M->mobi_start, Jm);
+        const double yaw = qs[M->virtual_start + 2];
+        cy = cos(yaw);
+        sy = sin(yaw);
+        wsync();
+      }
+      if (l < nv) {
+        const double v = rollout_velocity(M, l, cy, sy, Jm, [&](int a) { return es[a]; });
+        const double qn = rollout_advance(qk, ro.dt, v);
+        ro.vf[l * LD + gb] = v;
+        ro.qf[l * LD + gb] = qn;
+        if (ro.q_traj) ro.q_traj[(static_cast<int64_t>(k) * nv + l) * LD + gb] = qn;
+      }
+      state_visible();
+      wsync();
+    }
+  }
+}
+
+template <bool MESH>
+static int launch_rollout(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                          const KParams& kq, const IO& io, const Rollout& ro) {
+  const dim3 g(grid), blk(64);
+  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
+    hipLaunchKernelGGL((rollout_kernel<Dims<23, 16, 7, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
+  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
+    hipLaunchKernelGGL((rollout_kernel<Dims<20, 14, 6, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
+  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
+    hipLaunchKernelGGL((rollout_kernel<Dims<9, 16, 9, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
+  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
+    hipLaunchKernelGGL((rollout_kernel<Dims<11, 16, 11, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
+  else
+    return hipErrorInvalidValue;  // not a compiled shape: the stepwise path runs it
+  return hipGetLastError();
+}
+
+// The builds for models with hulls are a translation unit of their own
+// (rollout_mesh_kernel.hip includes this file with DRC_ROLLOUT_MESH defined),
+// as fused_mesh_kernel.hip is for the fused kernel.
+#ifdef DRC_ROLLOUT_MESH
+int launch_rollout_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                               const KParams& kq, const IO& io, const Rollout& ro) {
+  return launch_rollout<true>(grid, lds, st, m, kt, kq, io, ro);
+}
+#else
+int launch_rollout_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                               const KParams& kq, const IO& io, const Rollout& ro);
+int launch_rollout_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
+                          const IO& io, int steps, int per_step, double dt, double* qf, double* vf, double* q_traj,
+                          double* pose_traj, double* dist_traj, int64_t out_step, bool mesh) {
+  const Rollout ro{steps, per_step, dt, qf, vf, q_traj, pose_traj, dist_traj, out_step};
+  const int plan = fused_lds_doubles(kt, kq), state = rollout_state_doubles(kt, kq);
+  const size_t lds = static_cast<size_t>(plan > state ? plan : state) * sizeof(double);
+  return mesh ? launch_rollout_mesh_kernel(grid, lds, st, m, kt, kq, io, ro)
+              : launch_rollout<false>(grid, lds, st, m, kt, kq, io, ro);
+}
+
+int launch_rollout_integrate_kernel(int64_t B, hipStream_t st, const DevModel* m, double dt, const double* q_in,
+                                    const double* eta, double* qf, double* vf, double* q_traj) {
+  hipLaunchKernelGGL(rollout_integrate_kernel, dim3(static_cast<unsigned>((B + 255) / 256)), dim3(256), 0, st, m, B,
+                     dt, q_in, eta, qf, vf, q_traj);
+  return hipGetLastError();
+}
+#endif
+
+}  // namespace drc_amd

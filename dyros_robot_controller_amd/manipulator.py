@@ -298,6 +298,22 @@ class QPIKParamsBuilder:
         return p
 
 
+ROLLOUT_MODES = {"qpik": _capi.MODE_QPIK, "step": _capi.MODE_QPIK_STEP, "cubic": _capi.MODE_QPIK_CUBIC}
+
+
+def _rollout(ctrl, kv, q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init, xdot_init, current_time,
+             init_time, duration, targets_per_step, want):
+    """QPIK_rollout_batch of both controllers (``kv``: the task Kv of its QPIK*)."""
+    if mode not in ROLLOUT_MODES:
+        raise ValueError("mode must be one of %s" % sorted(ROLLOUT_MODES))
+    p = ctrl._pb.params(link_name, ROLLOUT_MODES[mode], ctrl.Kp_task_, kv, current_time, init_time, duration)
+    dev = ctrl.robot_data_.device
+    a = lambda t: _batch.as_device(t, dev)
+    return _batch.qpik_rollout_batch(ctrl.robot_data_.model, p, a(q), a(qdot), steps, ctrl.dt_ if dt is None else dt,
+                                     None if mode == "qpik" else a(x_target), a(xdot_target), a(x_init), a(xdot_init),
+                                     targets_per_step=targets_per_step, want=want)
+
+
 class RobotController:
     """Manipulator::RobotController QPIK entries
     (src/manipulator/robot_controller.cpp:7-19,277-317).
@@ -409,6 +425,15 @@ class RobotController:
                          duration, link_name):
         return self._run(_capi.MODE_QPIK_CUBIC, link_name, q, qdot, x_target, xdot_target, x_init, xdot_init,
                          current_time, init_time, duration)
+
+    def QPIK_rollout_batch(self, q, qdot, x_target, xdot_target, link_name, steps, dt=None, mode="step",
+                           x_init=None, xdot_init=None, current_time=0, init_time=0, duration=1,
+                           targets_per_step=False, want=("qdot_traj", "q_traj")):
+        """``steps`` closed-loop cycles of QPIK / QPIKStep / QPIKCubic (``mode``
+        "qpik", "step", "cubic") with q += dt * qdot_desired between them
+        (fr3_controller.cpp:123-134), on the device: a _batch.RolloutResult."""
+        return _rollout(self, self.Kv_task_, q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init,
+                        xdot_init, current_time, init_time, duration, targets_per_step, want)
 
     # -- single-instance entries (reference signatures; B = 1 launches) -------
     def _one(self, out_status):

@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _batch, _capi
 from ._capi import C
-from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, pose_to12
+from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, _rollout, pose_to12
 
 
 class DriveType(IntEnum):
@@ -472,6 +472,17 @@ class RobotController:
                          duration, link_name):
         return self._run(_capi.MODE_QPIK_CUBIC, link_name, q, qdot, x_target, xdot_target, x_init, xdot_init,
                          current_time, init_time, duration)
+
+    def QPIK_rollout_batch(self, q, qdot, x_target, xdot_target, link_name, steps, dt=None, mode="step",
+                           x_init=None, xdot_init=None, current_time=0, init_time=0, duration=1,
+                           targets_per_step=False, want=("qdot_traj", "q_traj")):
+        """``steps`` closed-loop cycles of QPIK / QPIKStep / QPIKCubic (``mode``
+        "qpik", "step", "cubic") on the device: qdot = S(q) eta (the virtual
+        joints follow Rz(yaw) J_mobile, robot_data.cpp:115-120) and
+        q += dt * qdot between them.  Returns a _batch.RolloutResult
+        (``qdot_traj``: eta in ActuatorIndex order, as QPIK_step_batch)."""
+        return _rollout(self, np.zeros(6), q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init,
+                        xdot_init, current_time, init_time, duration, targets_per_step, want)
 
     def split_actuated(self, eta):
         """eta [A] -> (qdot_mobile [W], qdot_mani [n]) by ActuatorIndex."""

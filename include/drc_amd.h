@@ -217,6 +217,51 @@ int drc_qpik_batch(const drc_model* model, const drc_qpik_params* params, int64_
                    const double* xdot_target, const double* x_init, const double* xdot_init,
                    double* qdot_out, int32_t* status, int32_t* iters, void* stream);
 
+/* Closed-loop rollout: `steps` control cycles of drc_qpik_batch with the
+ * reference loop's integration q_desired = q + qdot_desired * dt between them
+ * (examples/C++/src/fr3_controller.cpp:123-134), enqueued on `stream` without
+ * host synchronisation.  For step k = 0 .. steps-1 on the state (q_k, v_k),
+ * (q_0, v_0) = (q0, qdot0) [dof][B]:
+ *   (eta_k, status_k, iters_k) are exactly drc_qpik_batch's results for
+ *       `params` with t = params->t + (double)k * dt (product rounded, then
+ *       the sum) on (q_k, v_k) and step k's targets; non-solved instances give
+ *       eta_k = 0 and stay where they are;
+ *   v_{k+1} = eta_k (manipulator), or S(q_k) eta_k (mobile manipulator: the
+ *       selection matrix of mobile_manipulator/robot_data.cpp:22-25,115-120,
+ *       virtual block Rz(yaw_k) J_mobile(wheel positions); arm and wheel rows
+ *       are eta's entries unchanged);
+ *   q_{k+1} = q_k + dt * v_{k+1}, a rounded product then a rounded sum.
+ * Targets as drc_qpik_batch; targets_per_step = 1: x_target [steps][12][B] and
+ * xdot_target [steps][6][B], one set per step (not with DRC_MODE_QPIK_CUBIC,
+ * where the time already moves the target); 0: one set for the horizon.
+ * Outputs: q_final, qdot_final [dof][B] = (q_steps, v_steps), required;
+ *   q_final may alias q0 and qdot_final qdot0 (no other input is written);
+ *   status_traj [steps][B] required; the others may be NULL:
+ *   qdot_traj [steps][na][B] = eta_k, iters_traj [steps][B],
+ *   q_traj [steps][dof][B] = q_{k+1},
+ *   pose_traj [steps][12][B], dist_traj [steps][1+dof][B] at q_k in the
+ *   layouts of drc_qpik_stages_batch.
+ * The QP shapes the library compiles (drc_set_fusion) run, up to 4 096
+ * instances of a manipulator and 65 536 of a mobile manipulator (where it was
+ * measured faster; DRC_ROLLOUT_MAX overrides), as one persistent kernel whose
+ * waves take an instance through its whole horizon; other models, larger
+ * batches and drc_set_fusion(model, 0) run step by step: drc_qpik_batch's
+ * launches and a state-update kernel per step.  Results are bit-identical
+ * either way, and to `steps` drc_qpik_batch calls with the update above.
+ * DRC_ERR_INVALID_ARGUMENT: steps < 1, dt not finite or not positive, a NULL
+ * required pointer, per-step targets with CUBIC; otherwise drc_qpik_batch's
+ * codes.  B = 0 returns DRC_OK.  (Reference: no counterpart, one robot.) */
+int drc_qpik_rollout_batch(const drc_model* model, const drc_qpik_params* params,
+                           int64_t B, int steps, double dt,
+                           const double* q0, const double* qdot0,
+                           const double* x_target, const double* xdot_target,
+                           const double* x_init, const double* xdot_init,
+                           int targets_per_step,
+                           double* q_final, double* qdot_final,
+                           double* qdot_traj, int32_t* status_traj, int32_t* iters_traj,
+                           double* q_traj, double* pose_traj, double* dist_traj,
+                           void* stream);
+
 /* Stage outputs of the same kernel for parity checks: per instance
  *   pose [12][B]  (getPose with the pose at the current q — SURVEY Q1),
  *   jac  [6*dof][B] row-major (getJacobian, LWA),
