@@ -76,6 +76,7 @@ struct drc_model_impl {
   HostModel hm;
   DevModel* d_model = nullptr;
   double* d_mesh = nullptr;  // hull vertices of the collision meshes (DevModel::mesh_verts)
+  double* d_pair_tab = nullptr;  // per-pair records of the task stage (DevModel::pair_tab)
   int device = 0;
   drc_kinematic_param kparam{};
   drc_joint_index jidx{};
@@ -397,6 +398,12 @@ static int upload(drc_model_impl* m) {
     HIP_TRY(hipMalloc(&m->d_mesh, bytes));
     HIP_TRY(hipMemcpy(m->d_mesh, m->hm.mesh_verts.data(), bytes, hipMemcpyHostToDevice));
     m->hm.dev.mesh_verts = m->d_mesh;
+  }
+  {  // the task stage's per-pair records (model.cpp build_stage_tables)
+    const size_t bytes = m->hm.pair_tab.size() * sizeof(double);
+    HIP_TRY(hipMalloc(&m->d_pair_tab, bytes));
+    HIP_TRY(hipMemcpy(m->d_pair_tab, m->hm.pair_tab.data(), bytes, hipMemcpyHostToDevice));
+    m->hm.dev.pair_tab = m->d_pair_tab;
   }
   HIP_TRY(hipMalloc(&m->d_model, sizeof(DevModel)));
   HIP_TRY(hipMemcpy(m->d_model, &m->hm.dev, sizeof(DevModel), hipMemcpyHostToDevice));
@@ -1508,6 +1515,7 @@ void drc_model_destroy(drc_model* m) {
   drc_amd::free_lanes(&m->ln);
   if (m->d_model) (void)hipFree(m->d_model);
   if (m->d_mesh) (void)hipFree(m->d_mesh);
+  if (m->d_pair_tab) (void)hipFree(m->d_pair_tab);
   if (m->d_order) (void)hipFree(m->d_order);
   if (m->hstream) (void)hipStreamSynchronize(m->hstream), (void)hipStreamDestroy(m->hstream);
   if (m->stage) (void)hipFree(m->stage);

@@ -542,7 +542,38 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
       ++m.ncand_slots;
     }
   }
+  build_stage_tables(out);
   return DRC_OK;
+}
+
+void build_stage_tables(HostModel* hm) {
+  DevModel& m = hm->dev;
+  m.rev_mask = 0;
+  for (int w = 0; w < 4; ++w) m.anc_bits[w] = 0;
+  for (int j = 1; j <= m.nv; ++j) {
+    if (m.jtype[j] == kRevolute) m.rev_mask |= 1u << (j - 1);
+    for (int k = 1; k <= m.nv; ++k)
+      if (m.anc[j] & (1u << (k - 1))) {
+        const int bit = 16 * (j - 1) + (k - 1);
+        m.anc_bits[bit >> 6] |= 1ull << (bit & 63);
+      }
+  }
+  // one record per broad-phase slot (see DevModel::pair_tab)
+  m.pair_ld = (m.npairs + 63) / 64 * 64;  // whole rounds of 64 lanes
+  hm->pair_tab.assign(static_cast<size_t>(kPairFields) * std::max(m.pair_ld, 1), 0.0);
+  for (int sl = 0; sl < m.npairs; ++sl) {
+    const int p = m.pair_order[sl], ga = m.pair_a[p], gb = m.pair_b[p];
+    double* rec = hm->pair_tab.data() + sl;
+    const uint64_t meta = static_cast<uint64_t>(p) | static_cast<uint64_t>(ga) << 16 | static_cast<uint64_t>(gb) << 24 |
+                          static_cast<uint64_t>(m.gtype[ga]) << 32 | static_cast<uint64_t>(m.gtype[gb]) << 36;
+    std::memcpy(rec + kPairMeta * m.pair_ld, &meta, sizeof(meta));
+    for (int k = 0; k < 3; ++k) {
+      rec[(kPairParamA + k) * m.pair_ld] = m.gparam[ga][k];
+      rec[(kPairParamB + k) * m.pair_ld] = m.gparam[gb][k];
+    }
+    rec[kPairBoundA * m.pair_ld] = m.gbound[ga];
+    rec[kPairBoundB * m.pair_ld] = m.gbound[gb];
+  }
 }
 
 }  // namespace drc_amd

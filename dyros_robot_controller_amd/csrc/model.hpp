@@ -62,7 +62,19 @@ struct DevModel {
   int has_mesh;
   int gmesh_first[kMaxGeoms], gmesh_count[kMaxGeoms];
   const double* mesh_verts;        // device buffer [n][3] (model-owned), null without meshes
+  // tables of the wave task stage, built once with the model (build_stage_tables)
+  // so that no stage gathers model constants through dependent loads per instance:
+  uint32_t rev_mask;               // bit (j-1) set iff joint j is revolute
+  uint64_t anc_bits[4];            // bit 16 (j-1) + (k-1) set iff joint k supports joint j: anc[] as one bit table
+  // per-slot broad-phase records, field-major: field f of slot sl of
+  // pair_order (the broad phase's lane order) at pair_tab[f * pair_ld + sl].
+  // Fields: kPairMeta (pair | ga << 16 | gb << 24 | type a << 32 | type b << 36,
+  // the double's bits), gparam of a (3), gparam of b (3), gbound of a, of b.
+  const double* pair_tab;          // device buffer (model-owned)
+  int pair_ld;
 };
+constexpr int kPairFields = 9;
+constexpr int kPairMeta = 0, kPairParamA = 1, kPairParamB = 4, kPairBoundA = 7, kPairBoundB = 8;
 
 struct HostModel {
   DevModel dev{};
@@ -77,6 +89,7 @@ struct HostModel {
   std::vector<int> mesh_first, mesh_count;  // per geometry (count 0: primitive)
   std::vector<double> mesh_residual;        // per geometry: what a reduced hull leaves out (mesh.hpp)
   std::vector<std::string> mesh_files;      // per geometry: the resolved file
+  std::vector<double> pair_tab;             // DevModel::pair_tab, [kPairFields][dev.pair_ld]
   bool has_mesh() const { return !mesh_verts.empty(); }
 };
 
@@ -84,5 +97,8 @@ struct HostModel {
 // packages_path: where package://a/b mesh URIs are looked up (<packages_path>/a/b).
 int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_path,
                           const std::string& packages_path, HostModel* out, std::string* err);
+// Fills rev_mask / anc_bits and the per-slot pair records from the model's
+// jtype / anc / pair / geometry arrays (called by build_model_from_urdf).
+void build_stage_tables(HostModel* hm);
 
 }  // namespace drc_amd

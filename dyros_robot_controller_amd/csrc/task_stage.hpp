@@ -381,6 +381,58 @@ __device__ __noinline__ void closed_form_stage(const DevModel* M, const KParams&
   wsync();
 }
 
+// Model tables of the wave task stage (model.cpp build_stage_tables): what the
+// stages would otherwise gather per instance through dependent loads
+// (pair_order -> slot_a / slot_b -> gtype / gparam -> gbound; jtype / anc by a
+// lane's joint index, each feeding a branch).
+#ifdef __HIP_DEVICE_COMPILE__
+typedef __attribute__((address_space(1))) const double glb_cdouble;
+#else
+typedef const double glb_cdouble;
+#endif
+struct PairTab {
+  glb_cdouble* t;
+  int ld;
+};
+__device__ __forceinline__ PairTab pair_tab(const DevModel* M) { return PairTab{(glb_cdouble*)M->pair_tab, M->pair_ld}; }
+struct PairRec {
+  int p, ga, gb, ta, tb;
+  double pa[3], pb[3], ba, bb;
+};
+// record of slot sl of pair_order: nine independent loads, consecutive lanes
+// on consecutive addresses
+__device__ __forceinline__ PairRec pair_rec(const PairTab& pt, int i) {
+  glb_cdouble* t = pt.t + i;
+  PairRec r;
+  const unsigned long long m = static_cast<unsigned long long>(__double_as_longlong(t[kPairMeta * pt.ld]));
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    r.pa[k] = t[(kPairParamA + k) * pt.ld];
+    r.pb[k] = t[(kPairParamB + k) * pt.ld];
+  }
+  r.ba = t[kPairBoundA * pt.ld];
+  r.bb = t[kPairBoundB * pt.ld];
+  r.p = static_cast<int>(m & 0xffffu);
+  r.ga = static_cast<int>((m >> 16) & 0xffu);
+  r.gb = static_cast<int>((m >> 24) & 0xffu);
+  r.ta = static_cast<int>((m >> 32) & 0xfu);
+  r.tb = static_cast<int>((m >> 36) & 0xfu);
+  return r;
+}
+// joint k supports joint j (anc[j] bit k - 1), from DevModel::anc_bits held in SGPRs
+struct AncBits {
+  uint64_t w[4];
+};
+__device__ __forceinline__ AncBits anc_bits(const DevModel* M) {
+  return AncBits{{M->anc_bits[0], M->anc_bits[1], M->anc_bits[2], M->anc_bits[3]}};
+}
+__device__ __forceinline__ bool supports(const AncBits& ab, int k, int j) {
+  const int bit = 16 * (j - 1) + (k - 1), w = bit >> 6;
+  const uint64_t x = w == 0 ? ab.w[0] : (w == 1 ? ab.w[1] : (w == 2 ? ab.w[2] : ab.w[3]));
+  return (x >> (bit & 63)) & 1u;
+}
+__device__ __forceinline__ bool revolute(uint32_t rev_mask, int j) { return (rev_mask >> (j - 1)) & 1u; }
+
 // One instance b of the task stage on this wave (S: the wave's LDS plan kp).
 // PROBLEM 0: QPIK stage data; 1: also the QPID extras; 2: closed-form CLIK / OSF.
 // MESH: the model has convex-hull geometry (GeomType kMesh).  A build of its
@@ -409,6 +461,16 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   // task targets, one value per lane (lanes 0-11 x_target, 12-17 xdot_target,
   // 18-29 x_init, 30-35 xdot_init): issued here so their latency overlaps the
   // FK; the task-velocity stage reads them by v_readlane
+  // model constants of this lane's joint (and, before the chain, of its
+  // geometry: kMaxGeoms = 64, one per lane), issued with the state loads so
+  // that one memory latency covers them; lane 0 and the lanes past nv / ngeom
+  // read entry 0 and drop it
+  const uint32_t rev_mask = M->rev_mask;
+  const int jm = l <= nv ? l : 0, gm = l < M->ngeom ? l : 0;
+  double jpl[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) jpl[i] = M->jplace[jm][i];
+  const V3 axl = ld3(M->axis[jm]);
   double tgt = 0.0;
   if (PROBLEM == 2 && kp.cf == 3) {
     // kinematics only (drc_kinematics_batch): no task targets
@@ -428,10 +490,12 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   if (l >= 1 && l <= nv) {
     const int j = l;
     double Mj[12];
-    const double* ax = M->axis[j];
+    const double ax[3] = {axl.x, axl.y, axl.z};
     const double qq = qv[j - 1];
-    if (M->jtype[j] == kRevolute) {
-      double c = cos(qq), s = sin(qq), C = 1 - c, x = ax[0], y = ax[1], z = ax[2];
+    if (revolute(rev_mask, j)) {
+      double c, s;
+      sincos(qq, &s, &c);
+      double C = 1 - c, x = ax[0], y = ax[1], z = ax[2];
       Mj[0] = c + x * x * C; Mj[1] = x * y * C - z * s; Mj[2] = x * z * C + y * s;
       Mj[3] = y * x * C + z * s; Mj[4] = c + y * y * C; Mj[5] = y * z * C - x * s;
       Mj[6] = z * x * C - y * s; Mj[7] = z * y * C + x * s; Mj[8] = c + z * z * C;
@@ -442,10 +506,15 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       Mj[9] = ax[0] * qq; Mj[10] = ax[1] * qq; Mj[11] = ax[2] * qq;
     }
     double Lj[12];
-    tmul(M->jplace[j], Mj, Lj);
+    tmul(jpl, Mj, Lj);
     for (int i = 0; i < 12; ++i) loc[(j - 1) * 12 + i] = Lj[i];
   }
   wsync();
+  // this lane's geometry placement: in flight while the chain below runs
+  double gpl[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) gpl[i] = M->gplace[gm][i];
+  const int gpar = M->gparent[gm];
   for (int j = 1; j <= nv; ++j) {  // oMi[j] = oMi[parent] * local[j]; 12 lanes
     const double* a = T + M->parent[j] * 12;
     const double* bb = loc + (j - 1) * 12;
@@ -462,15 +531,15 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     wsync();
   }
   double* Te = S + kp.kTe;
-  if (l >= 1 && l <= nv) st3(Zw + 3 * l, rot(T + 12 * l, ld3(M->axis[l])));
+  if (l >= 1 && l <= nv) st3(Zw + 3 * l, rot(T + 12 * l, axl));
   if (l == 0) tmul(T + 12 * kp.frame_joint, kp.frame_place, Te);
   wsync();
   // geometry poses
   double* Tg = S + kp.kTg;
-  for (int g = l; g < M->ngeom; g += 64) {
+  if (l < M->ngeom) {
     double out[12];
-    tmul(T + 12 * M->gparent[g], M->gplace[g], out);
-    for (int i = 0; i < 12; ++i) Tg[g * 12 + i] = out[i];
+    tmul(T + 12 * gpar, gpl, out);
+    for (int i = 0; i < 12; ++i) Tg[l * 12 + i] = out[i];
   }
   PH(0);
   // ---------------- frame Jacobian (LWA), 6 x nv row-major -------------
@@ -482,7 +551,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     V3 lin = v3(0, 0, 0), ang = v3(0, 0, 0);
     if (anc_e & (1u << l)) {
       V3 z = ld3(Zw + 3 * j);
-      if (M->jtype[j] == kRevolute) {
+      if (revolute(rev_mask, j)) {
         lin = cross(z, pe - v3(T[12 * j + 9], T[12 * j + 10], T[12 * j + 11]));
         ang = z;
       } else {
@@ -644,6 +713,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   }
   wsync();
   double* part = S + kp.kPart;
+  const AncBits ancb = anc_bits(M);
   for (int e = l; e < narm * narm; e += 64) {
     const int kk = e / narm, c = e % narm;
     const int jk = c0 + kk + 1, ji = c0 + c + 1;  // joint ids of q_k and column i
@@ -652,13 +722,13 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       V3 zk = ld3(Zw + 3 * jk), zi = ld3(Zw + 3 * ji);
       V3 pk_ = v3(T[12 * jk + 9], T[12 * jk + 10], T[12 * jk + 11]);
       V3 pi_ = v3(T[12 * ji + 9], T[12 * ji + 10], T[12 * ji + 11]);
-      const bool krev = M->jtype[jk] == kRevolute;
+      const bool krev = revolute(rev_mask, jk);
       V3 dpe = krev ? cross(zk, pe - pk_) : zk;
-      const bool moves_i = jk != ji && (M->anc[ji] & (1u << (jk - 1)));
+      const bool moves_i = jk != ji && supports(ancb, jk, ji);
       V3 dzi = (moves_i && krev) ? cross(zk, zi) : v3(0, 0, 0);
       V3 dpi = moves_i ? (krev ? cross(zk, pi_ - pk_) : zk) : v3(0, 0, 0);
       V3 lin, ang;
-      if (M->jtype[ji] == kRevolute) {
+      if (revolute(rev_mask, ji)) {
         lin = cross(dzi, pe - pi_) + cross(zi, dpe - dpi);
         ang = dzi;
       } else {
@@ -698,10 +768,12 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     return ShapeMT<lds_pose*, true>{M->gtype[g], (lds_pose*)(Tg + 12 * g), M->gparam[g][0], M->gparam[g][1],
                                     M->gparam[g][2], M->mesh_verts + 3 * M->gmesh_first[g], M->gmesh_count[g]};
   };
+  const PairTab ptab = pair_tab(M);
   for (int sl = l; sl < M->npairs; sl += 64) {
-    const int p = M->pair_order[sl], ga = M->slot_a[sl], gb = M->slot_b[sl];
-    ShapeL A{M->gtype[ga], (lds_pose*)(Tg + 12 * ga), M->gparam[ga][0], M->gparam[ga][1], M->gparam[ga][2]};
-    ShapeL Bs{M->gtype[gb], (lds_pose*)(Tg + 12 * gb), M->gparam[gb][0], M->gparam[gb][1], M->gparam[gb][2]};
+    const PairRec pr = pair_rec(ptab, sl);  // the slot's record: one level of loads
+    const int p = pr.p;
+    ShapeL A{pr.ta, (lds_pose*)(Tg + 12 * pr.ga), pr.pa[0], pr.pa[1], pr.pa[2]};
+    ShapeL Bs{pr.tb, (lds_pose*)(Tg + 12 * pr.gb), pr.pb[0], pr.pb[1], pr.pb[2]};
     V3 pA, pB;
     double d;
     if constexpr (MESH) {
@@ -709,7 +781,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
         if (A.type == kMesh) A.type = kBox;
         if (Bs.type == kMesh) Bs.type = kBox;
         pd[p] = (A.type == kSphere || Bs.type == kSphere) ? sphere_pair(A, Bs, &pA, &pB)
-                                                          : pair_lower_bound(A, Bs, M->gbound[ga], M->gbound[gb]);
+                                                          : pair_lower_bound(A, Bs, pr.ba, pr.bb);
         pf[p] = 0;
         continue;
       }
@@ -728,7 +800,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
         bpB = pB;
       }
     } else {  // swept-core / separating-axis lower bound
-      pd[p] = pair_lower_bound(A, Bs, M->gbound[ga], M->gbound[gb]);
+      pd[p] = pair_lower_bound(A, Bs, pr.ba, pr.bb);
       pf[p] = 0;
     }
   }
@@ -942,7 +1014,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       n = (1.0 / sqrt(dot(n, n))) * n;
       const int j = l + 1;
       V3 z = ld3(Zw + 3 * j), pj = v3(T[12 * j + 9], T[12 * j + 10], T[12 * j + 11]);
-      const bool rev = M->jtype[j] == kRevolute;
+      const bool rev = revolute(rev_mask, j);
       V3 cA = v3(0, 0, 0), cB = v3(0, 0, 0);
       if (jA > 0 && (M->anc[jA] & (1u << l))) cA = rev ? cross(z, pA - pj) : z;
       if (jB > 0 && (M->anc[jB] & (1u << l))) cB = rev ? cross(z, pB - pj) : z;
