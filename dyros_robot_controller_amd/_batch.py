@@ -40,9 +40,28 @@ def check_shapes(dof, B, **fields):
             raise ValueError("%s must be [%d][B=%d] (field-major SoA), got %s" % (k, rows, B, tuple(v.shape)))
 
 
+def obstacle_poses(model, obstacle_pose, B, device, steps=None):
+    """The obstacle-pose argument of the ``*_obstacles_batch`` entries:
+    (device tensor, obstacle_ld, per_step).  Accepts [n][12] (one set shared by
+    the batch, ld 0) or [n][12][B] (a set per instance), n the model's obstacle
+    slots, each pose R column-major then p as ``x_target``; with ``steps`` also
+    a leading [steps] axis (per_step True)."""
+    n = model.n_obstacles
+    t = as_device(obstacle_pose, device)
+    shape = tuple(t.shape)
+    cores = ((n, 12), (n, 12, B))
+    per_step = shape not in cores and steps is not None and shape[:1] == (steps,) and shape[1:] in cores
+    core = shape[1:] if per_step else shape
+    if core in cores:
+        return t, (0 if len(core) == 2 else B), per_step
+    raise ValueError("obstacle_pose must be [n=%d][12] or [n=%d][12][B=%d]%s, got %s"
+                     % (n, n, B, "" if steps is None else ", optionally with a leading [steps=%d]" % steps, shape))
+
+
 def qpik_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
-               out=None, status=None, iters=None, stream=None):
-    """Launch ``drc_qpik_batch`` on device tensors laid out [field][B]."""
+               out=None, status=None, iters=None, stream=None, obstacle_pose=None):
+    """Launch ``drc_qpik_batch`` on device tensors laid out [field][B]
+    (``drc_qpik_obstacles_batch`` with ``obstacle_pose``, see obstacle_poses)."""
     torch = _torch()
     dev = q.device
     B = q.shape[1]
@@ -54,6 +73,13 @@ def qpik_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=N
         status = torch.empty(B, dtype=torch.int32, device=dev)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
+    if obstacle_pose is not None:
+        op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
+        _capi.check(_capi.lib().drc_qpik_obstacles_batch(
+            model.handle, C.byref(params), C.c_int64(B), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target),
+            _ptr(x_init), _ptr(xdot_init), _ptr(op), C.c_int64(ld), _ptr(out), _ptr(status), _ptr(iters),
+            C.c_void_p(stream)))
+        return out, status
     _capi.check(_capi.lib().drc_qpik_batch(
         model.handle, C.byref(params), C.c_int64(B), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target),
         _ptr(x_init), _ptr(xdot_init), _ptr(out), _ptr(status), _ptr(iters), C.c_void_p(stream)))
@@ -76,9 +102,11 @@ class RolloutResult:
 
 def qpik_rollout_batch(model, params, q, qdot, steps, dt, x_target=None, xdot_target=None, x_init=None,
                        xdot_init=None, targets_per_step=False, want=("qdot_traj", "q_traj"), q_final=None,
-                       qdot_final=None, stream=None):
+                       qdot_final=None, stream=None, obstacle_pose=None):
     """Launch ``drc_qpik_rollout_batch`` on device tensors laid out [field][B]
-    (per-step targets: [steps][field][B]).  ``want``: the optional
+    (per-step targets: [steps][field][B]); with ``obstacle_pose`` (see
+    obstacle_poses; a leading [steps] axis moves the obstacles)
+    ``drc_qpik_rollout_obstacles_batch``.  ``want``: the optional
     trajectories to allocate and fill (ROLLOUT_FIELDS); ``q_final`` /
     ``qdot_final`` may be given (``q`` / ``qdot`` themselves: in place)."""
     torch = _torch()
@@ -113,6 +141,15 @@ def qpik_rollout_batch(model, params, q, qdot, steps, dt, x_target=None, xdot_ta
         dist_traj=f(n, 1 + nv, B) if "dist_traj" in want else None)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
+    if obstacle_pose is not None:
+        op, ld, per_step = obstacle_poses(model, obstacle_pose, B, dev, steps=steps)
+        _capi.check(_capi.lib().drc_qpik_rollout_obstacles_batch(
+            model.handle, C.byref(params), C.c_int64(B), C.c_int(steps), C.c_double(dt), _ptr(q), _ptr(qdot),
+            _ptr(x_target), _ptr(xdot_target), _ptr(x_init), _ptr(xdot_init), C.c_int(1 if targets_per_step else 0),
+            _ptr(op), C.c_int64(ld), C.c_int(1 if per_step else 0),
+            _ptr(res.q_final), _ptr(res.qdot_final), _ptr(res.qdot_traj), _ptr(res.status_traj),
+            _ptr(res.iters_traj), _ptr(res.q_traj), _ptr(res.pose_traj), _ptr(res.dist_traj), C.c_void_p(stream)))
+        return res
     _capi.check(_capi.lib().drc_qpik_rollout_batch(
         model.handle, C.byref(params), C.c_int64(B), C.c_int(steps), C.c_double(dt), _ptr(q), _ptr(qdot),
         _ptr(x_target), _ptr(xdot_target), _ptr(x_init), _ptr(xdot_init), C.c_int(1 if targets_per_step else 0),
@@ -165,8 +202,10 @@ def qpid_stages_batch(model, params, q, qdot, x_target=None, xdot_target=None, x
                 man_graddot=gdv[:model.mani_dof], dist_graddot=gdv[model.mani_dof:])
 
 
-def stages_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None):
-    """Stage outputs (pose, J, manipulability, min distance, task velocity)."""
+def stages_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
+                 obstacle_pose=None):
+    """Stage outputs (pose, J, manipulability, min distance, task velocity);
+    with ``obstacle_pose`` (see obstacle_poses) ``drc_qpik_stages_obstacles_batch``."""
     torch = _torch()
     dev = q.device
     B = q.shape[1]
@@ -176,6 +215,13 @@ def stages_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init
     pose, jac, man, dist, xdd = f(12), f(6 * nv), f(1 + mani), f(1 + nv), f(6)
     pair = torch.zeros(B, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if obstacle_pose is not None:
+        op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
+        _capi.check(_capi.lib().drc_qpik_stages_obstacles_batch(
+            model.handle, C.byref(params), C.c_int64(B), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target),
+            _ptr(x_init), _ptr(xdot_init), _ptr(op), C.c_int64(ld), _ptr(pose), _ptr(jac), _ptr(man), _ptr(dist),
+            _ptr(pair), _ptr(xdd), C.c_void_p(stream)))
+        return dict(pose=pose, jac=jac, man=man, dist=dist, pair=pair, xdot_des=xdd)
     _capi.check(_capi.lib().drc_qpik_stages_batch(
         model.handle, C.byref(params), C.c_int64(B), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target),
         _ptr(x_init), _ptr(xdot_init), _ptr(pose), _ptr(jac), _ptr(man), _ptr(dist), _ptr(pair), _ptr(xdd),

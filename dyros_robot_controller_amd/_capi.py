@@ -45,7 +45,14 @@ EXPORTED_SYMBOLS = (
     "drc_qpid_stages_host", "drc_clik_batch", "drc_osf_batch", "drc_closed_form_host",
     "drc_error_string", "drc_last_error", "drc_build_id", "drc_qpik_host_timed", "drc_kinematics_batch",
     "drc_state_host", "drc_model_geom_info", "drc_mesh_convex_hull", "drc_qpik_rollout_batch",
+    "drc_model_set_obstacles", "drc_qpik_obstacles_batch", "drc_qpik_stages_obstacles_batch",
+    "drc_qpik_rollout_obstacles_batch",
 )
+# the obstacle-slot entries (absent from older A/B builds)
+OBSTACLE_SYMBOLS = ("drc_model_set_obstacles", "drc_qpik_obstacles_batch", "drc_qpik_stages_obstacles_batch",
+                    "drc_qpik_rollout_obstacles_batch")
+# drc_model_geom_info type codes
+GEOM_SPHERE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH, GEOM_HALFSPACE = 0, 1, 2, 3, 4
 
 
 class TimeDuration(C.Structure):
@@ -144,6 +151,15 @@ def _load():
     if hasattr(lib, "drc_qpik_rollout_batch"):  # absent from older A/B builds
         lib.drc_qpik_rollout_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int, C.c_double,
                                                vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "drc_model_set_obstacles"):  # obstacle slots: absent from older A/B builds
+        lib.drc_model_set_obstacles.argtypes = [vp, C.c_int, ip, dp, C.POINTER(C.c_char_p), C.c_int]
+        lib.drc_qpik_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, vp, vp, vp, vp, vp, vp,
+                                                 vp, C.c_int64, vp, vp, vp, vp]
+        lib.drc_qpik_stages_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, vp, vp, vp, vp, vp, vp,
+                                                        vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+        lib.drc_qpik_rollout_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int, C.c_double,
+                                                         vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
+                                                         vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.drc_debug_kernel_timing.argtypes = [vp, C.c_int]
     # diagnostics added in r05: bound only when present, so A/B runs can load
     # an older build (tests/test_capi_symbols.py checks the product exports them)
@@ -187,7 +203,7 @@ def _load():
     for name in EXPORTED_SYMBOLS:
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
                     "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info",
-                    "drc_mesh_convex_hull", "drc_qpik_rollout_batch") and not hasattr(lib, name):
+                    "drc_mesh_convex_hull", "drc_qpik_rollout_batch") + OBSTACLE_SYMBOLS and not hasattr(lib, name):
             continue  # diagnostics an older A/B build may lack
         if name not in ("drc_model_destroy", "drc_error_string", "drc_last_error", "drc_build_id"):
             getattr(lib, name).restype = C.c_int

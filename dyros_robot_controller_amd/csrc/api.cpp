@@ -391,9 +391,19 @@ static int mobile_ik_jacobian(const drc_kinematic_param& p, const double* wheel_
 static const char kMeshStageMsg[] =
     "the model has collision meshes: the lane-per-instance debug stage handles sphere, cylinder and box geometry only";
 
+// Obstacle poses of a call (drc_qpik_*obstacles_batch): [n][12][ld] in
+// x_target's layout, ld = 0 one set shared by the batch (kernel_common.hpp)
+using Obst = ObstIn;
+static const char kSlotsPlainMsg[] =
+    "the model has obstacle slots: pass their poses through drc_qpik_obstacles_batch, "
+    "drc_qpik_stages_obstacles_batch or drc_qpik_rollout_obstacles_batch";
+static const char kSlotsUnsupportedMsg[] =
+    "the model has obstacle slots: only the drc_qpik_*obstacles_batch entries take their poses "
+    "(drc_model_set_obstacles with n = 0 removes the slots)";
+
 static int upload(drc_model_impl* m) {
   HIP_TRY(hipSetDevice(m->device));
-  if (m->hm.has_mesh()) {  // the hulls' vertices: one model-owned buffer
+  if (m->hm.has_mesh() && !m->d_mesh) {  // the hulls' vertices: one model-owned buffer
     const size_t bytes = m->hm.mesh_verts.size() * sizeof(double);
     HIP_TRY(hipMalloc(&m->d_mesh, bytes));
     HIP_TRY(hipMemcpy(m->d_mesh, m->hm.mesh_verts.data(), bytes, hipMemcpyHostToDevice));
@@ -401,11 +411,13 @@ static int upload(drc_model_impl* m) {
   }
   {  // the task stage's per-pair records (model.cpp build_stage_tables)
     const size_t bytes = m->hm.pair_tab.size() * sizeof(double);
+    if (m->d_pair_tab) HIP_TRY(hipFree(m->d_pair_tab));  // a re-upload (drc_model_set_obstacles)
+    m->d_pair_tab = nullptr;
     HIP_TRY(hipMalloc(&m->d_pair_tab, bytes));
     HIP_TRY(hipMemcpy(m->d_pair_tab, m->hm.pair_tab.data(), bytes, hipMemcpyHostToDevice));
     m->hm.dev.pair_tab = m->d_pair_tab;
   }
-  HIP_TRY(hipMalloc(&m->d_model, sizeof(DevModel)));
+  if (!m->d_model) HIP_TRY(hipMalloc(&m->d_model, sizeof(DevModel)));
   HIP_TRY(hipMemcpy(m->d_model, &m->hm.dev, sizeof(DevModel), hipMemcpyHostToDevice));
   return DRC_OK;
 }
@@ -678,8 +690,14 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
                          const double* qdot, const double* xt, const double* xdt, const double* xi,
                          const double* xdi, double* out, int32_t* status, int32_t* iters, double* pose, double* jac,
                          double* man, double* dist, int32_t* pair, double* xdd, void* stream,
-                         uint64_t* stamps = nullptr) {
+                         uint64_t* stamps = nullptr, const Obst* ob = nullptr) {
   if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  const bool slots = m->hm.dev.nobst > 0;
+  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsPlainMsg);
+  if (!slots && ob)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "the model has no obstacle slots (drc_model_set_obstacles declares them)");
+  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
   if (B == 0) return DRC_OK;
   if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
   if (!q || !qdot || !xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, "q, qdot and xdot_target are required");
@@ -712,7 +730,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
   // (DESIGN.md), and stage and QPIK calls then see the same GJK witnesses)
   const int ls = m->lane_stage;
   const bool lane = (ls == 1 || ls == 2 || (ls == 3 && stages)) && (dm.nv == 6 || dm.nv == 7) &&
-                    dm.ncand_slots <= kMaxCandSlots && !dm.has_mesh;
+                    dm.ncand_slots <= kMaxCandSlots && !dm.has_mesh && !slots;
   // fused up to 16 Ki instances: there a call is a few instances per wave, its
   // makespan the tail the fused kernel and the EPA-first order below shorten;
   // at full batch the overlapped sub-batch pipeline wins.  Measured at
@@ -737,7 +755,8 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
   static const int64_t order_max = env_int("DRC_ORDER_MAX", 8192, 0);
   static const int64_t order_min = env_int("DRC_ORDER_MIN", 2049, 0);
   const bool dbg_order = m->d_order && m->order_n == B;
-  const bool auto_order = !stages && !lane && !dbg_order && B >= order_min && (B <= order_max || fuse) &&
+  // (not with obstacle slots: the order kernel's predictor knows no poses)
+  const bool auto_order = !stages && !lane && !dbg_order && !slots && B >= order_min && (B <= order_max || fuse) &&
                           dm.kind == 0 && dm.ncand_slots > 0 && dm.ncand_slots <= kMaxCandSlots;
   int32_t* order_buf = nullptr;
   {
@@ -841,6 +860,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
           rec ? rec + b0 * stride : nullptr, stride};
     io.stamps = stages ? nullptr : stamps;
     io.order = (!stages && !lane && dbg_order) ? m->d_order : nullptr;
+    const ObstIn obin = ob ? *ob : ObstIn();
     int* qc = cx->d_queue + c * StreamCtx::kSlotInts;  // c < 16 (drc_set_concurrency)
     // the whole slot (128 B, one aligned fill; 17 ints took two fill kernels)
     HIP_TRY(hipMemsetAsync(qc, 0, StreamCtx::kSlotInts * sizeof(int), cs));
@@ -865,8 +885,12 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     const size_t lds_t = static_cast<size_t>(kt_c.lds_doubles) * sizeof(double);
     const size_t lds_q = stages ? 0 : static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
     auto launch_task = [&](hipStream_t sm) -> int {
-      HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io,
-                                                         dm.has_mesh != 0)));
+      if (slots)
+        HIP_TRY(static_cast<hipError_t>(
+            launch_task_obstacle_kernel(static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io, obin)));
+      else
+        HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c,
+                                                           io, dm.has_mesh != 0)));
       return DRC_OK;
     };
     auto launch_qp = [&]() -> int {
@@ -890,7 +914,9 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
           sizeof(double);
       io.queue = qc;
       HIP_TRY(static_cast<hipError_t>(
-          launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, dm.has_mesh != 0)));
+          slots ? launch_fused_obstacle_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin)
+                : launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io,
+                                      dm.has_mesh != 0)));
       if (timed_c) HIP_TRY(hipEventRecord(e1, cs));
     } else if (!lane) {  // wave-per-instance task kernel on every instance, then the QP
       if (int r = launch_task(cs)) return r;
@@ -945,12 +971,13 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
 static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int stages, int64_t B, const double* q,
                   const double* qdot, const double* xt, const double* xdt, const double* xi, const double* xdi,
                   double* out, int32_t* status, int32_t* iters, double* pose, double* jac, double* man,
-                  double* dist, int32_t* pair, double* xdd, void* stream, uint64_t* stamps = nullptr) {
+                  double* dist, int32_t* pair, double* xdd, void* stream, uint64_t* stamps = nullptr,
+                  const Obst* ob = nullptr) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
   return launch_locked(m, params, stages, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, pose, jac, man, dist,
-                       pair, xdd, stream, stamps);
+                       pair, xdd, stream, stamps, ob);
 }
 
 // t_k = t + k dt as a rounded product and a rounded sum (the persistent
@@ -971,10 +998,19 @@ static double rollout_time(double t, int k, double dt) {
 static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int steps, double dt,
                    const double* q0, const double* qdot0, const double* xt, const double* xdt, const double* xi,
                    const double* xdi, int per_step, double* qf, double* vf, double* qdot_traj, int32_t* status_traj,
-                   int32_t* iters_traj, double* q_traj, double* pose_traj, double* dist_traj, void* stream) {
+                   int32_t* iters_traj, double* q_traj, double* pose_traj, double* dist_traj, void* stream,
+                   const Obst* ob = nullptr, int ob_per_step = 0) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  const bool slots = m->hm.dev.nobst > 0;
+  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsPlainMsg);
+  if (!slots && ob)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "the model has no obstacle slots (drc_model_set_obstacles declares them)");
+  if (ob_per_step != 0 && ob_per_step != 1)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacles_per_step must be 0 or 1");
+  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
   if (steps < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "steps must be at least 1");
   if (!std::isfinite(dt) || !(dt > 0)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
   if (per_step != 0 && per_step != 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "targets_per_step must be 0 or 1");
@@ -1008,8 +1044,9 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   // 133.2 ms).  DRC_ROLLOUT_MAX overrides (read per call, so that one process
   // can measure both paths)
   const int64_t rollout_max = env_int("DRC_ROLLOUT_MAX", dm.kind == 0 ? 4096 : 65536, 0);
+  // (models with obstacle slots: the stepwise path; no persistent build takes poses)
   const bool persistent = m->fused && m->lane_stage == 0 && B <= rollout_max && kQpGroup == 64 &&
-                          qp_compiled(kq.nx, kq.ng, kq.np);
+                          qp_compiled(kq.nx, kq.ng, kq.np) && !slots;
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
   double* eta = qdot_traj;  // without qdot_traj: one step's eta in stream scratch
@@ -1050,14 +1087,19 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     const double* xt_k = per_step && xt ? xt + int64_t(k) * 12 * B : xt;
     const double* xdt_k = per_step ? xdt + int64_t(k) * 6 * B : xdt;
     double* eta_k = eta + k * out_step;
+    Obst ob_k{nullptr, 0};
+    if (ob)  // this step's pose set: [n][12][ld], or the shared [n][12]
+      ob_k = Obst{ob->pose + (ob_per_step ? int64_t(k) * dm.nobst * 12 * (ob->ld ? ob->ld : 1) : 0), ob->ld};
+    const Obst* obp = ob ? &ob_k : nullptr;
     if (pose_traj || dist_traj)
       if (int rc = launch_locked(m, &pk, 1, B, qk, vk, xt_k, xdt_k, xi, xdi, nullptr, nullptr, nullptr,
                                  pose_traj ? pose_traj + int64_t(k) * 12 * B : nullptr, nullptr, nullptr,
-                                 dist_traj ? dist_traj + int64_t(k) * (1 + nv) * B : nullptr, nullptr, nullptr, stream))
+                                 dist_traj ? dist_traj + int64_t(k) * (1 + nv) * B : nullptr, nullptr, nullptr, stream,
+                                 nullptr, obp))
         return rc;
     if (int rc = launch_locked(m, &pk, 0, B, qk, vk, xt_k, xdt_k, xi, xdi, eta_k, status_traj + int64_t(k) * B,
                                iters_traj ? iters_traj + int64_t(k) * B : nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, stream))
+                               nullptr, nullptr, stream, nullptr, obp))
       return rc;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_integrate_kernel(
         B, st, m->d_model, dt, qk, eta_k, qf, vf, q_traj ? q_traj + int64_t(k) * nv * B : nullptr)));
@@ -1078,6 +1120,7 @@ static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, 
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  if (m->hm.dev.nobst > 0) return set_err(DRC_ERR_UNSUPPORTED, kSlotsUnsupportedMsg);
   if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   if (B == 0) return DRC_OK;
   if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");
@@ -1152,6 +1195,7 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  if (cf != 3 && m->hm.dev.nobst > 0) return set_err(DRC_ERR_UNSUPPORTED, kSlotsUnsupportedMsg);
   if (cf == 3) {  // kinematics only (drc_kinematics_batch): any model kind, no task targets
     if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
     if (B == 0) return DRC_OK;
@@ -1362,6 +1406,7 @@ int drc_debug_lane_stage(drc_model* m, int enable) {
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
   if (enable && m->hm.has_mesh()) return drc_amd::set_err(DRC_ERR_UNSUPPORTED, drc_amd::kMeshStageMsg);
   std::lock_guard<std::mutex> g(m->launch_mu);
+  if (m->hm.dev.nobst > 0) return drc_amd::set_err(DRC_ERR_UNSUPPORTED, drc_amd::kSlotsUnsupportedMsg);
   m->lane_stage = enable < 0 ? 0 : (enable > 3 ? 3 : enable);
   return DRC_OK;
 }
@@ -1551,8 +1596,9 @@ int drc_model_geom_info(const drc_model* m, int geom, int* type, double param[3]
   if (type) *type = d.gtype[geom];
   if (param)
     for (int i = 0; i < 3; ++i) param[i] = d.gparam[geom][i];
-  if (n_vertices) *n_vertices = m->hm.mesh_count[geom];
-  if (hull_residual) *hull_residual = m->hm.mesh_residual[geom];
+  const bool urdf_geom = geom < static_cast<int>(m->hm.mesh_count.size());  // (obstacle slots: primitives)
+  if (n_vertices) *n_vertices = urdf_geom ? m->hm.mesh_count[geom] : 0;
+  if (hull_residual) *hull_residual = urdf_geom ? m->hm.mesh_residual[geom] : 0.0;
   return DRC_OK;
 }
 
@@ -1729,6 +1775,65 @@ int drc_qpik_stages_batch(const drc_model* m, const drc_qpik_params* p, int64_t 
                          pair, xdd, stream);
 }
 
+// ---- obstacle slots ------------------------------------------------------------
+int drc_model_set_obstacles(drc_model* m, int n, const int* type, const double* param, const char* const* links,
+                            int n_links) {
+  using drc_amd::set_err;
+  if (!m) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  std::string err;
+  drc_amd::HostModel hm = m->hm;  // built aside: a refused call leaves the model as it was
+  if (int rc = drc_amd::set_obstacles(&hm, n, type, param, links, n_links, &err)) return set_err(rc, err);
+  HIP_TRY(hipSetDevice(m->device));
+  // the model's outstanding work (every stream that ran it) reads the old tables
+  HIP_TRY(hipDeviceSynchronize());
+  const drc_amd::HostModel old = m->hm;
+  m->hm = hm;
+  drc_qpik_params pp;
+  int rc = drc_default_qpik_params(m, 1, &pp);
+  if (!rc) {  // the task stage's LDS plan with the new geometry and pair counts
+    drc_amd::KParams kt;
+    pp.frame_id = -1;
+    rc = drc_amd::make_kparams(m, &pp, 1, &kt);
+  }
+  if (rc) {
+    m->hm = old;
+    return rc;
+  }
+  return drc_amd::upload(m);
+}
+
+int drc_qpik_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
+                             const double* qdot, const double* xt, const double* xdt, const double* xi,
+                             const double* xdi, const double* obstacle_pose, int64_t obstacle_ld, double* out,
+                             int32_t* status, int32_t* iters, void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  return drc_amd::launch(m, p, 0, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, stream, nullptr, &ob);
+}
+
+int drc_qpik_stages_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
+                                    const double* qdot, const double* xt, const double* xdt, const double* xi,
+                                    const double* xdi, const double* obstacle_pose, int64_t obstacle_ld,
+                                    double* pose, double* jac, double* man, double* dist, int32_t* pair, double* xdd,
+                                    void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  return drc_amd::launch(m, p, 1, B, q, qdot, xt, xdt, xi, xdi, nullptr, nullptr, nullptr, pose, jac, man, dist,
+                         pair, xdd, stream, nullptr, &ob);
+}
+
+int drc_qpik_rollout_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int steps, double dt,
+                                     const double* q0, const double* qdot0, const double* xt, const double* xdt,
+                                     const double* xi, const double* xdi, int targets_per_step,
+                                     const double* obstacle_pose, int64_t obstacle_ld, int obstacles_per_step,
+                                     double* q_final, double* qdot_final, double* qdot_traj, int32_t* status_traj,
+                                     int32_t* iters_traj, double* q_traj, double* pose_traj, double* dist_traj,
+                                     void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  return drc_amd::rollout(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step, q_final, qdot_final,
+                          qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream, &ob,
+                          obstacles_per_step);
+}
 
 // ---- QPID -------------------------------------------------
 int drc_default_qpid_params(const drc_model* m, int exact, drc_qpik_params* p) {
@@ -2290,6 +2395,7 @@ int drc_joint_torque_step_batch(drc_model* m, int64_t B, const double* q, const 
                                 const double* kv, double* tau, void* stream) {
   using drc_amd::set_err;
   if (!m) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  if (m->hm.dev.nobst > 0) return set_err(DRC_ERR_UNSUPPORTED, drc_amd::kSlotsUnsupportedMsg);
   if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   if (B == 0) return DRC_OK;
   if (!q || !tau) return set_err(DRC_ERR_INVALID_ARGUMENT, "q and tau are required");
@@ -2315,6 +2421,7 @@ int drc_joint_torque_step_host(drc_model* m, int64_t B, const double* q, const d
                                const double* kv, double* tau) {
   using drc_amd::set_err;
   if (!m) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  if (m->hm.dev.nobst > 0) return set_err(DRC_ERR_UNSUPPORTED, drc_amd::kSlotsUnsupportedMsg);
   if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   if (!q || !tau) return set_err(DRC_ERR_INVALID_ARGUMENT, "q and tau are required");
   const drc_amd::DevModel& d = m->hm.dev;

@@ -22,9 +22,12 @@ namespace drc_amd {
 #define DRC_FUSED_WAVES 2
 #endif
 // MESH: the build for models with convex-hull geometry (task_stage.hpp)
-template <class QD, bool MESH = false>
+// OB: empty, or one ObstIn: the build for models with obstacle slots and the
+// call's poses (task_stage.hpp OBST).  A pack, so that the kernels without
+// obstacles keep their four arguments
+template <class QD, bool MESH = false, class... OB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
-fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io) {
+fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io, const OB... ob) {
   extern __shared__ __attribute__((aligned(16))) double S[];
   PH_KSCOPE();
   __shared__ KParams kpl;  // LDS copy of the QP parameters for the out-of-line ADMM blocks
@@ -36,6 +39,7 @@ fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     wsync();
   }
   static_assert(QD::gs == 64, "the fused kernel runs one instance per wave");
+  static_assert(sizeof...(OB) <= 1, "at most one set of obstacle poses");
   const int64_t B = io.B;
   IO iol = io;  // the record lives in LDS: one slot, reused by every instance of the wave
   iol.rec = S + fused_rec_offset(kt, kq);  // (kernel_common.hpp: past the QP plan, in the task plan's dead overlay)
@@ -47,7 +51,7 @@ fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     const int64_t b = io.ordered(jj);
     stage_stamp(io, ST_TASK0, io.b0 + b);
     stage_where(io, ST_WTASK, io.b0 + b);
-    task_instance<0, MESH>(M0, kt, iol, S, b);
+    task_instance<0, MESH, sizeof...(OB) != 0>(M0, kt, iol, S, b, ob...);
     wsync();
     stage_stamp(io, ST_TASK1, io.b0 + b);
     qp_instance<QD>(M0, kq, kpl, iol, S, b);
@@ -73,8 +77,25 @@ static int launch_fused(unsigned grid, size_t lds, hipStream_t st, const DevMode
 
 // The builds for models with hulls are a translation unit of their own
 // (fused_mesh_kernel.hip includes this file with DRC_FUSED_MESH defined), so
-// this unit compiles to what it was without them.
-#ifdef DRC_FUSED_MESH
+// this unit compiles to what it was without them.  Likewise the builds for
+// models with obstacle slots (fused_obstacle_kernel.hip, DRC_FUSED_OBST).
+#if defined(DRC_FUSED_OBST)
+int launch_fused_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                                 const KParams& kq, const IO& io, const ObstIn& ob) {
+  const dim3 g(grid), blk(64);
+  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // the compiled shapes of launch_fused
+    hipLaunchKernelGGL((fused_kernel<Dims<23, 16, 7, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
+  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)
+    hipLaunchKernelGGL((fused_kernel<Dims<20, 14, 6, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
+  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)
+    hipLaunchKernelGGL((fused_kernel<Dims<9, 16, 9, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
+  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)
+    hipLaunchKernelGGL((fused_kernel<Dims<11, 16, 11, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+#elif defined(DRC_FUSED_MESH)
 int launch_fused_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                              const KParams& kq, const IO& io) {
   return launch_fused<true>(grid, lds, st, m, kt, kq, io);

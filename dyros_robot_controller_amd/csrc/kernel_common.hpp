@@ -420,6 +420,16 @@ struct IO {
   const int32_t* order = nullptr;
   __device__ __forceinline__ int64_t ordered(int64_t j) const { return order ? int64_t(order[b0 + j]) - b0 : j; }
 };
+// Poses of the model's obstacle slots for one call: pose [nobst][12][ld] (R
+// column-major, then p, as x_target; instance b0 + b at column b0 + b), ld = 0:
+// one [nobst][12] set for every instance.  An argument of its own of the
+// obstacle builds (task_obstacle_kernel.hip, fused_obstacle_kernel.hip), so
+// that IO -- which the out-of-line stages of the other kernels take by
+// reference, in memory -- keeps its size.
+struct ObstIn {
+  const double* pose = nullptr;
+  int64_t ld = 0;
+};
 // six clock stamps, then where the task and the QP stage ran (stage_where)
 constexpr int kTimeStamps = 6, kStamps = 8;
 enum { ST_TASK0 = 0, ST_TASK1 = 1, ST_QP0 = 2, ST_ASM = 3, ST_SOLVED = 4, ST_OUT = 5, ST_WTASK = 6, ST_WQP = 7 };

@@ -31,6 +31,13 @@ int launch_qpid_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel
 // mesh: the build with the hull narrow phase, as for launch_task_kernel
 int launch_fused_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                         const KParams& kq, const IO& io, bool mesh = false);
+// the builds for models with obstacle slots (task_obstacle_kernel.hip,
+// fused_obstacle_kernel.hip): the QPIK stage and the fused kernel with
+// task_instance<0, false, OBST = true>, ob the call's poses
+int launch_task_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                                const IO& io, const ObstIn& ob);
+int launch_fused_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                                 const KParams& kq, const IO& io, const ObstIn& ob);
 
 // persistent rollout kernel (rollout_kernel.hip; compiled QPIK shapes,
 // hipErrorInvalidValue otherwise): per instance `steps` times task stage, QP

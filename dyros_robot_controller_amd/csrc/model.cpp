@@ -512,18 +512,28 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
     m.pair_a[p] = static_cast<int16_t>(pairs[p].first);
     m.pair_b[p] = static_cast<int16_t>(pairs[p].second);
   }
+  out->geom_link = b.geom_link;
+  out->base_pairs = m.npairs;
+  m.nobst = 0;
+  m.obst0 = m.ngeom;
+  build_pair_tables(out);
+  return DRC_OK;
+}
+
+void build_pair_tables(HostModel* hm) {
+  DevModel& m = hm->dev;
   // pair order of the wave kernel's closed-form / bound pass: by type class
   // (sphere-sphere, sphere-cylinder, sphere-box, cylinder-cylinder,
-  // cylinder-box, box-box, then every pair with a mesh), pair index order
-  // within a class
+  // cylinder-box, box-box, then every pair with a mesh, then every pair with a
+  // half-space), pair index order within a class
   {
     int n = 0;
-    for (int cls = 0; cls < 7; ++cls)
+    for (int cls = 0; cls < 8; ++cls)
       for (int p = 0; p < m.npairs; ++p) {
         int ta = m.gtype[m.pair_a[p]], tb = m.gtype[m.pair_b[p]];
         if (ta > tb) std::swap(ta, tb);
-        // (0,0)0 (0,1)1 (0,2)2 (1,1)3 (1,2)4 (2,2)5 (*,mesh)6
-        const int c = tb == kMesh ? 6 : (ta == 0 ? tb : (ta == 1 ? 2 + tb : 5));
+        // (0,0)0 (0,1)1 (0,2)2 (1,1)3 (1,2)4 (2,2)5 (*,mesh)6 (*,half-space)7
+        const int c = tb == kHalfSpace ? 7 : (tb == kMesh ? 6 : (ta == 0 ? tb : (ta == 1 ? 2 + tb : 5)));
         if (c == cls) m.pair_order[n++] = static_cast<int16_t>(p);
       }
     for (int sl = 0; sl < m.npairs; ++sl) {
@@ -532,17 +542,119 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
     }
   }
   // GJK candidate slots of the lane-per-instance task stage: the pairs with
-  // no sphere (no closed form), numbered in pair order
+  // no sphere and no half-space (no closed form), numbered in pair order
   m.ncand_slots = 0;
   for (int p = 0; p < m.npairs; ++p) {
     m.cand_slot[p] = -1;
-    if (m.gtype[m.pair_a[p]] != kSphere && m.gtype[m.pair_b[p]] != kSphere) {
+    if (m.gtype[m.pair_a[p]] != kSphere && m.gtype[m.pair_b[p]] != kSphere && m.gtype[m.pair_b[p]] != kHalfSpace) {
       if (m.ncand_slots < kMaxCandSlots) m.cand_pair[m.ncand_slots] = static_cast<int16_t>(p);
       m.cand_slot[p] = static_cast<int16_t>(m.ncand_slots < kMaxCandSlots ? m.ncand_slots : -1);
       ++m.ncand_slots;
     }
   }
-  build_stage_tables(out);
+  build_stage_tables(hm);
+}
+
+int set_obstacles(HostModel* hm, int n, const int* type, const double* param, const char* const* links, int n_links,
+                  std::string* err) {
+  DevModel& m = hm->dev;
+  const int g0 = m.obst0;  // geometries of the URDF
+  if (n < 0 || n_links < 0 || (n > 0 && !type) || (n_links > 0 && !links)) {
+    *err = "set_obstacles: negative count or missing array";
+    return DRC_ERR_INVALID_ARGUMENT;
+  }
+  if (n > 0 && hm->has_mesh()) {
+    *err = "the model has collision meshes: obstacle slots are not built for hull models";
+    return DRC_ERR_UNSUPPORTED;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (type[i] == kMesh) {
+      *err = "obstacle " + std::to_string(i) + ": mesh obstacles are not supported";
+      return DRC_ERR_UNSUPPORTED;
+    }
+    if (type[i] != kSphere && type[i] != kCylinder && type[i] != kBox && type[i] != kHalfSpace) {
+      *err = "obstacle " + std::to_string(i) + ": unknown geometry type " + std::to_string(type[i]);
+      return DRC_ERR_INVALID_ARGUMENT;
+    }
+    if (type[i] != kHalfSpace && !param) {
+      *err = "set_obstacles: param is required for sphere, cylinder and box obstacles";
+      return DRC_ERR_INVALID_ARGUMENT;
+    }
+    const int np = type[i] == kSphere ? 1 : (type[i] == kCylinder ? 2 : (type[i] == kBox ? 3 : 0));
+    for (int k = 0; k < np; ++k)
+      if (!(param[3 * i + k] > 0) || !std::isfinite(param[3 * i + k])) {
+        *err = "obstacle " + std::to_string(i) + ": parameters must be finite and positive";
+        return DRC_ERR_INVALID_ARGUMENT;
+      }
+  }
+  // the geometries each obstacle is paired with
+  std::vector<int> with;
+  if (n_links == 0) {
+    for (int g = 0; g < g0; ++g)
+      if (m.gparent[g] > 0) with.push_back(g);
+  } else {
+    std::set<std::string> named;
+    for (int k = 0; k < n_links; ++k) {
+      if (!links[k] || std::find(hm->frame_names.begin(), hm->frame_names.end(), links[k]) == hm->frame_names.end()) {
+        *err = std::string("set_obstacles: unknown link '") + (links[k] ? links[k] : "(null)") + "'";
+        return DRC_ERR_UNKNOWN_LINK;
+      }
+      named.insert(links[k]);
+    }
+    for (int g = 0; g < g0; ++g)
+      if (named.count(hm->geom_link[g])) with.push_back(g);
+  }
+  if (g0 + n > kMaxGeoms) {
+    *err = "obstacle slots: more than " + std::to_string(kMaxGeoms) + " collision geometries";
+    return DRC_ERR_UNSUPPORTED;
+  }
+  if (hm->base_pairs + static_cast<int64_t>(n) * static_cast<int64_t>(with.size()) > kMaxPairs) {
+    *err = "obstacle slots: more than " + std::to_string(kMaxPairs) + " collision pairs";
+    return DRC_ERR_UNSUPPORTED;
+  }
+  // back to the URDF's model: what a fresh build leaves past its geometries and pairs is zero
+  for (int g = g0; g < kMaxGeoms; ++g) {
+    m.gparent[g] = m.gtype[g] = 0;
+    m.gbound[g] = 0;
+    std::memset(m.gplace[g], 0, sizeof(m.gplace[g]));
+    std::memset(m.gparam[g], 0, sizeof(m.gparam[g]));
+  }
+  for (int p = hm->base_pairs; p < kMaxPairs; ++p) m.pair_a[p] = m.pair_b[p] = 0;
+  std::memset(m.pair_order, 0, sizeof(m.pair_order));
+  std::memset(m.slot_a, 0, sizeof(m.slot_a));
+  std::memset(m.slot_b, 0, sizeof(m.slot_b));
+  std::memset(m.cand_slot, 0, sizeof(m.cand_slot));
+  std::memset(m.cand_pair, 0, sizeof(m.cand_pair));
+  hm->geom_names.resize(g0);
+  m.ngeom = g0 + n;
+  m.nobst = n;
+  m.npairs = hm->base_pairs;
+  for (int i = 0; i < n; ++i) {
+    const int g = g0 + i;
+    m.gparent[g] = 0;
+    m.gtype[g] = type[i];
+    const SE3 eye;
+    put12(eye, m.gplace[g]);
+    const double* pr = param + 3 * i;
+    if (type[i] == kSphere) {
+      m.gparam[g][0] = pr[0];
+      m.gbound[g] = pr[0];
+    } else if (type[i] == kCylinder) {
+      m.gparam[g][0] = pr[0];
+      m.gparam[g][1] = pr[1];
+      m.gbound[g] = pr[0];  // capsule core = axis segment
+    } else if (type[i] == kBox) {
+      for (int k = 0; k < 3; ++k) m.gparam[g][k] = pr[k];
+      m.gbound[g] = std::sqrt(pr[0] * pr[0] + pr[1] * pr[1] + pr[2] * pr[2]);
+    }
+    hm->geom_names.push_back("obstacle_" + std::to_string(i));
+    for (int a : with) {  // obstacle-major, the link geometries in index order
+      m.pair_a[m.npairs] = static_cast<int16_t>(a);
+      m.pair_b[m.npairs] = static_cast<int16_t>(g);
+      ++m.npairs;
+    }
+  }
+  build_pair_tables(hm);
   return DRC_OK;
 }
 

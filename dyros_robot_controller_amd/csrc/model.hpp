@@ -17,7 +17,9 @@ constexpr int kMaxWheels = 8;
 constexpr int kMaxCandSlots = 128;  // non-sphere pairs the lane-per-instance task stage tracks
 
 enum JointType : int { kRevolute = 0, kPrismatic = 1 };
-enum GeomType : int { kSphere = 0, kCylinder = 1, kBox = 2, kMesh = 3 };  // kMesh: convex hull of a mesh's vertices
+enum GeomType : int { kSphere = 0, kCylinder = 1, kBox = 2, kMesh = 3, kHalfSpace = 4 };
+// kMesh: convex hull of a mesh's vertices; kHalfSpace: obstacle slots only, the
+// solid {x : (x - p) . R e_z <= 0} of the slot's pose (R, p) (halfspace.hpp)
 enum DriveKind : int { kDriveDifferential = 0, kDriveMecanum = 1, kDriveCaster = 2 };  // DRC_DRIVE_*
 
 // Flat, POD model image in HBM.  Transforms are 12 doubles: R row-major, p.
@@ -72,6 +74,10 @@ struct DevModel {
   // the double's bits), gparam of a (3), gparam of b (3), gbound of a, of b.
   const double* pair_tab;          // device buffer (model-owned)
   int pair_ld;
+  // obstacle slots (set_obstacles; appended, as the hull fields were):
+  // geometries [obst0, obst0 + nobst) have parent 0 and a pose that is an input
+  // of each call, not gplace (which holds the identity)
+  int nobst, obst0;
 };
 constexpr int kPairFields = 9;
 constexpr int kPairMeta = 0, kPairParamA = 1, kPairParamB = 4, kPairBoundA = 7, kPairBoundB = 8;
@@ -90,6 +96,8 @@ struct HostModel {
   std::vector<double> mesh_residual;        // per geometry: what a reduced hull leaves out (mesh.hpp)
   std::vector<std::string> mesh_files;      // per geometry: the resolved file
   std::vector<double> pair_tab;             // DevModel::pair_tab, [kPairFields][dev.pair_ld]
+  std::vector<std::string> geom_link;       // per geometry of the URDF: its link
+  int base_pairs = 0;                       // pairs of the URDF / SRDF (the obstacle pairs follow them)
   bool has_mesh() const { return !mesh_verts.empty(); }
 };
 
@@ -100,5 +108,17 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
 // Fills rev_mask / anc_bits and the per-slot pair records from the model's
 // jtype / anc / pair / geometry arrays (called by build_model_from_urdf).
 void build_stage_tables(HostModel* hm);
+// Fills pair_order / slot_a / slot_b, the candidate slots and the stage tables
+// from the geometry and pair arrays (called by build_model_from_urdf and
+// set_obstacles).
+void build_pair_tables(HostModel* hm);
+// Declares n obstacle slots (replacing any earlier ones; n = 0 removes them and
+// leaves the model what build_model_from_urdf made): geometries ngeom .. with
+// parent 0, identity placement, type[i] (kSphere, kCylinder, kBox, kHalfSpace)
+// and param[i][3], each paired with every geometry of the named links
+// (n_links = 0: of every link that a joint moves).  The host tables only: the
+// caller uploads them.  Returns 0 or DRC_ERR_*, the model unchanged on error.
+int set_obstacles(HostModel* hm, int n, const int* type, const double* param, const char* const* links, int n_links,
+                  std::string* err);
 
 }  // namespace drc_amd

@@ -10,6 +10,7 @@
 //   QPID stage data, CLIK / OSF    robot_data.cpp:109,476-512, robot_controller.cpp:150-260
 #pragma once
 
+#include "halfspace.hpp"
 #include "kernel_common.hpp"
 
 namespace drc_amd {
@@ -437,9 +438,12 @@ __device__ __forceinline__ bool revolute(uint32_t rev_mask, int j) { return (rev
 // PROBLEM 0: QPIK stage data; 1: also the QPID extras; 2: closed-form CLIK / OSF.
 // MESH: the model has convex-hull geometry (GeomType kMesh).  A build of its
 // own, chosen at launch, so the kernels of mesh-free models carry none of it.
-template <int PROBLEM, bool MESH = false>
+// OBST: the model has obstacle slots (DevModel::nobst): geometries whose pose is
+// an input of the call (ob), among them half-spaces, which pass 1 decides
+// in closed form (halfspace.hpp).  A build of its own again; not with MESH.
+template <int PROBLEM, bool MESH = false, bool OBST = false>
 __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, const KParams& kp, const IO& io, double* S,
-                                              int64_t b) {
+                                              int64_t b, [[maybe_unused]] const ObstIn ob = ObstIn()) {
   const int l = lane_id();
   const int nv = kp.nv;
   EpaPoly* ews = reinterpret_cast<EpaPoly*>(S + kp.kEpa);  // LDS-resident polytope
@@ -480,6 +484,21 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     tgt = io.xdt[(l - 12) * LD + gb];
   } else if (l < 36 && kp.mode == DRC_MODE_QPIK_CUBIC) {
     tgt = l < 30 ? io.xi[(l - 18) * LD + gb] : io.xdi[(l - 30) * LD + gb];
+  }
+  // (OBST) the lane of an obstacle geometry: its pose's 12 values, issued with
+  // the loads above so that the FK chain hides them.  Field-major like
+  // x_target (consecutive instances on consecutive addresses); ld = 0 is
+  // one pose set for the whole batch
+  static_assert(!(MESH && OBST), "no obstacle build for hull models");
+  [[maybe_unused]] double opl[12];
+  [[maybe_unused]] const int obst0 = OBST ? M->obst0 : 0;
+  if constexpr (OBST) {
+    if (l >= obst0 && l < M->ngeom) {
+      const int64_t os = ob.ld ? ob.ld : 1;
+      const double* op = ob.pose + (int64_t)(l - obst0) * 12 * os + (ob.ld ? gb : 0);
+#pragma unroll
+      for (int i = 0; i < 12; ++i) opl[i] = op[i * os];
+    }
   }
   wsync();
   // ---------------- FK: local joint transforms, then the chain ------------
@@ -537,9 +556,21 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   // geometry poses
   double* Tg = S + kp.kTg;
   if (l < M->ngeom) {
-    double out[12];
-    tmul(T + 12 * gpar, gpl, out);
-    for (int i = 0; i < 12; ++i) Tg[l * 12 + i] = out[i];
+    bool slot = false;
+    if constexpr (OBST) {
+      if (l >= obst0) {  // the call's pose is the geometry's row (R column-major -> row-major): no tmul
+        slot = true;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Tg[l * 12 + i] = opl[(i % 3) * 3 + i / 3];
+#pragma unroll
+        for (int i = 9; i < 12; ++i) Tg[l * 12 + i] = opl[i];
+      }
+    }
+    if (!slot) {
+      double out[12];
+      tmul(T + 12 * gpar, gpl, out);
+      for (int i = 0; i < 12; ++i) Tg[l * 12 + i] = out[i];
+    }
   }
   PH(0);
   // ---------------- frame Jacobian (LWA), 6 x nv row-major -------------
@@ -786,9 +817,19 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
         continue;
       }
     }
-    const bool closed = (A.type == kSphere || Bs.type == kSphere)
-                            ? (d = sphere_pair(A, Bs, &pA, &pB), true)
-                            : (A.type == kCylinder && Bs.type == kCylinder && cyl_cyl_side(A, Bs, &d, &pA, &pB));
+    bool hs = false;
+    if constexpr (OBST) {
+      if (Bs.type == kHalfSpace) {  // exact by closed form: never a GJK candidate (an obstacle is a pair's b)
+        double ws[3], wp[3];
+        d = halfspace_distance(A.type, A.T, A.p0, A.p1, A.p2, Bs.T, ws, wp);
+        pA = ld3(ws);
+        pB = ld3(wp);
+        hs = true;
+      }
+    }
+    const bool closed = hs || ((A.type == kSphere || Bs.type == kSphere)
+                                   ? (d = sphere_pair(A, Bs, &pA, &pB), true)
+                                   : (A.type == kCylinder && Bs.type == kCylinder && cyl_cyl_side(A, Bs, &d, &pA, &pB)));
     if (closed) {
       pf[p] = 1;
       ub = fmin(ub, d);

@@ -54,10 +54,34 @@ class _ModelHandle:
     def __init__(self, handle, device):
         self.handle = handle
         self.device = device
+        self.n_obstacles = 0
+        self._read_info()
+
+    def _read_info(self):
         dof, act, mani, mobi, ng, npair = (C.c_int() for _ in range(6))
-        _capi.check(_capi.lib().drc_model_info(handle, *(C.byref(v) for v in (dof, act, mani, mobi, ng, npair))))
+        _capi.check(_capi.lib().drc_model_info(self.handle, *(C.byref(v) for v in (dof, act, mani, mobi, ng, npair))))
         self.dof, self.actuated_dof, self.mani_dof, self.mobi_dof = dof.value, act.value, mani.value, mobi.value
         self.n_geoms, self.n_pairs = ng.value, npair.value
+
+    def set_obstacles(self, types, params=None, links=None):
+        """``drc_model_set_obstacles``: declares len(types) obstacle slots
+        (replacing earlier ones; none removes them).  ``types``: 0 sphere,
+        1 cylinder, 2 box, 4 half-space (_capi.GEOM_*); ``params`` [n][3]: r |
+        r, h/2 | half extents (ignored for a half-space); ``links``: the links
+        whose collision geometry each obstacle is paired with (None: every
+        link that a joint moves).  The slots' poses are the ``obstacle_pose``
+        argument of the QPIK batch entries."""
+        types = [int(t) for t in types]
+        n = len(types)
+        prm = np.zeros((max(n, 1), 3))
+        if params is not None and n:
+            prm[:n] = np.asarray(params, dtype=np.float64).reshape(n, 3)
+        names = [s.encode() for s in (links or [])]
+        _capi.check(_capi.lib().drc_model_set_obstacles(
+            self.handle, C.c_int(n), (C.c_int * max(n, 1))(*types), prm.ctypes.data_as(C.POINTER(C.c_double)),
+            (C.c_char_p * max(len(names), 1))(*names) if names else None, C.c_int(len(names))))
+        self.n_obstacles = n
+        self._read_info()
 
     def frame_id(self, link_name):
         fid = C.c_int()
@@ -93,6 +117,13 @@ class RobotData:
         self.q_ = np.zeros(n)
         self.qdot_ = np.zeros(n)
         self._dyn_cache = None
+
+    def set_obstacles(self, types, params=None, links=None):
+        """Obstacle slots of the distance stage (_ModelHandle.set_obstacles):
+        world geometry whose poses are passed to QPIK_batch, QPIK_step_batch,
+        QPIK_cubic_batch and QPIK_rollout_batch as ``obstacle_pose``.
+        Reference: no counterpart."""
+        self.model.set_obstacles(types, params, links)
 
     # -- state ---------------------------------------------------------------
     def updateState(self, q, qdot):
@@ -302,7 +333,7 @@ ROLLOUT_MODES = {"qpik": _capi.MODE_QPIK, "step": _capi.MODE_QPIK_STEP, "cubic":
 
 
 def _rollout(ctrl, kv, q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init, xdot_init, current_time,
-             init_time, duration, targets_per_step, want):
+             init_time, duration, targets_per_step, want, obstacle_pose=None):
     """QPIK_rollout_batch of both controllers (``kv``: the task Kv of its QPIK*)."""
     if mode not in ROLLOUT_MODES:
         raise ValueError("mode must be one of %s" % sorted(ROLLOUT_MODES))
@@ -311,7 +342,7 @@ def _rollout(ctrl, kv, q, qdot, x_target, xdot_target, link_name, steps, dt, mod
     a = lambda t: _batch.as_device(t, dev)
     return _batch.qpik_rollout_batch(ctrl.robot_data_.model, p, a(q), a(qdot), steps, ctrl.dt_ if dt is None else dt,
                                      None if mode == "qpik" else a(x_target), a(xdot_target), a(x_init), a(xdot_init),
-                                     targets_per_step=targets_per_step, want=want)
+                                     targets_per_step=targets_per_step, want=want, obstacle_pose=obstacle_pose)
 
 
 class RobotController:
@@ -408,32 +439,38 @@ class RobotController:
 
     # -- batched entries (device tensors, [field][B]) --------------------------
     def _run(self, mode, link_name, q, qdot, x_target, xdot_target, x_init=None, xdot_init=None,
-             t=0.0, t0=0.0, duration=1.0, iters=None):
+             t=0.0, t0=0.0, duration=1.0, iters=None, obstacle_pose=None):
         p = self._pb.params(link_name, mode, self.Kp_task_, self.Kv_task_, t, t0, duration)
         dev = self.robot_data_.device
         return _batch.qpik_batch(self.robot_data_.model, p, _batch.as_device(q, dev), _batch.as_device(qdot, dev),
                                  _batch.as_device(x_target, dev), _batch.as_device(xdot_target, dev),
-                                 _batch.as_device(x_init, dev), _batch.as_device(xdot_init, dev), iters=iters)
+                                 _batch.as_device(x_init, dev), _batch.as_device(xdot_init, dev), iters=iters,
+                                 obstacle_pose=obstacle_pose)
 
-    def QPIK_batch(self, q, qdot, xdot_target, link_name):
-        return self._run(_capi.MODE_QPIK, link_name, q, qdot, None, xdot_target)
+    # (obstacle_pose: the poses of the model's obstacle slots, RobotData.set_obstacles:
+    # [n][12] shared by the batch or [n][12][B], each R column-major then p)
+    def QPIK_batch(self, q, qdot, xdot_target, link_name, obstacle_pose=None):
+        return self._run(_capi.MODE_QPIK, link_name, q, qdot, None, xdot_target, obstacle_pose=obstacle_pose)
 
-    def QPIK_step_batch(self, q, qdot, x_target, xdot_target, link_name, iters=None):
-        return self._run(_capi.MODE_QPIK_STEP, link_name, q, qdot, x_target, xdot_target, iters=iters)
+    def QPIK_step_batch(self, q, qdot, x_target, xdot_target, link_name, iters=None, obstacle_pose=None):
+        return self._run(_capi.MODE_QPIK_STEP, link_name, q, qdot, x_target, xdot_target, iters=iters,
+                         obstacle_pose=obstacle_pose)
 
     def QPIK_cubic_batch(self, q, qdot, x_target, xdot_target, x_init, xdot_init, current_time, init_time,
-                         duration, link_name):
+                         duration, link_name, obstacle_pose=None):
         return self._run(_capi.MODE_QPIK_CUBIC, link_name, q, qdot, x_target, xdot_target, x_init, xdot_init,
-                         current_time, init_time, duration)
+                         current_time, init_time, duration, obstacle_pose=obstacle_pose)
 
     def QPIK_rollout_batch(self, q, qdot, x_target, xdot_target, link_name, steps, dt=None, mode="step",
                            x_init=None, xdot_init=None, current_time=0, init_time=0, duration=1,
-                           targets_per_step=False, want=("qdot_traj", "q_traj")):
+                           targets_per_step=False, want=("qdot_traj", "q_traj"), obstacle_pose=None):
         """``steps`` closed-loop cycles of QPIK / QPIKStep / QPIKCubic (``mode``
         "qpik", "step", "cubic") with q += dt * qdot_desired between them
-        (fr3_controller.cpp:123-134), on the device: a _batch.RolloutResult."""
+        (fr3_controller.cpp:123-134), on the device: a _batch.RolloutResult.
+        ``obstacle_pose`` as for QPIK_step_batch, or with a leading [steps]
+        axis for obstacles that move."""
         return _rollout(self, self.Kv_task_, q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init,
-                        xdot_init, current_time, init_time, duration, targets_per_step, want)
+                        xdot_init, current_time, init_time, duration, targets_per_step, want, obstacle_pose)
 
     # -- single-instance entries (reference signatures; B = 1 launches) -------
     def _one(self, out_status):

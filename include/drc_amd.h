@@ -149,8 +149,9 @@ void drc_model_destroy(drc_model* model);
 int drc_model_info(const drc_model* model, int* dof, int* actuated_dof, int* mani_dof,
                    int* mobi_dof, int* n_geoms, int* n_pairs);
 
-/* Collision geometry `geom` (0 .. n_geoms-1): *type 0 sphere, 1 cylinder, 2 box,
- * 3 mesh (convex hull); param: sphere r | cylinder r, h/2 | box half extents |
+/* Collision geometry `geom` (0 .. n_geoms-1, the obstacle slots of
+ * drc_model_set_obstacles last): *type 0 sphere, 1 cylinder, 2 box,
+ * 3 mesh (convex hull), 4 half-space (an obstacle slot; param zero); param: sphere r | cylinder r, h/2 | box half extents |
  * mesh: half extents of the hull's bounding box; *n_vertices: hull vertices
  * (0 for primitives); *hull_residual: 0 for a full hull, else what the
  * 256-vertex cap left out (drc_mesh_convex_hull).  Outputs may be NULL. */
@@ -276,6 +277,86 @@ int drc_qpik_stages_batch(const drc_model* model, const drc_qpik_params* params,
                           const double* xdot_target, const double* x_init,
                           const double* xdot_init, double* pose, double* jac, double* man,
                           double* dist, int32_t* pair, double* xdot_des, void* stream);
+
+/* Obstacle slots: world geometry in the distance stage of QPIK, with poses that
+ * are inputs of each call (a table, a floor, a wall, a moving object; one
+ * scene per instance if wanted).  Declares n slots, replacing any declared
+ * before; they are the model's geometries n_geoms .. n_geoms + n - 1 (n_geoms of
+ * the URDF), parent joint 0, identity placement.  A slot's shape is a model
+ * constant:
+ *   type [n]      0 sphere, 1 cylinder, 2 box as drc_model_geom_info, or
+ *                 4 half-space: for a pose (R, p) the solid
+ *                 {x : (x - p) . R e_z <= 0} (floor, table top, wall);
+ *                 3 (mesh) is refused with DRC_ERR_UNSUPPORTED;
+ *   param [n][3]  sphere r | cylinder r, h/2 | box half extents, finite and
+ *                 positive; ignored for a half-space (may be NULL if all are).
+ * Each slot is paired with every collision geometry of the links named in
+ * links [n_links] (DRC_ERR_UNKNOWN_LINK for a name the URDF lacks); links =
+ * NULL, n_links = 0: of every link that a joint moves.  The new pairs follow the
+ * model's own, slot by slot, the geometries in index order, so pair indices
+ * reported by the stage entries stay those of the URDF for the self pairs.
+ * There are no obstacle-obstacle pairs.  Name the links: a floor under a
+ * fixed-base arm is a constant few centimetres from the first link and would
+ * win every minimum.
+ * A half-space pair is decided exactly, in closed form on both sides of the
+ * plane (d < 0: penetration depth); primitive obstacles go through the same
+ * narrow phase as the robot's own geometry.
+ * n = 0 removes the slots: the model is then bit for bit what its build made.
+ * The call waits for the model's outstanding work and replaces its device
+ * tables; it must not run concurrently with other calls on the model.
+ * DRC_ERR_UNSUPPORTED: more than 64 geometries or 1024 pairs in all, a mesh
+ * obstacle, or a model with collision meshes (hull models take no obstacles).
+ * While a model has slots, the plain drc_qpik_batch / drc_qpik_stages_batch /
+ * drc_qpik_rollout_batch and their host forms return DRC_ERR_INVALID_ARGUMENT
+ * (they have no poses to give), and drc_qpid_*, drc_clik_batch, drc_osf_batch,
+ * drc_closed_form_host, drc_joint_torque_step_* and drc_debug_lane_stage return
+ * DRC_ERR_UNSUPPORTED; kinematics and dynamics entries are unaffected.
+ * (Reference: no counterpart; its getMinDistance is a self-collision query.) */
+int drc_model_set_obstacles(drc_model* model, int n, const int* type, const double* param,
+                            const char* const* links, int n_links);
+
+/* drc_qpik_batch / drc_qpik_stages_batch on a model with obstacle slots.
+ *   obstacle_pose [n][12][obstacle_ld]: slot k's pose in x_target's layout (R
+ *       column-major, then p), world frame, field-major;
+ *   obstacle_ld: the row stride, >= B: a pose set per instance; 0: one [n][12]
+ *       set shared by the batch.
+ * Everything else as the plain entries; results do not depend on fusion, on
+ * the batch split, or on whether shared poses are passed shared or replicated.
+ * DRC_ERR_INVALID_ARGUMENT on a model without slots.
+ * (Reference: no counterpart.) */
+int drc_qpik_obstacles_batch(const drc_model* model, const drc_qpik_params* params, int64_t B,
+                             const double* q, const double* qdot, const double* x_target,
+                             const double* xdot_target, const double* x_init,
+                             const double* xdot_init, const double* obstacle_pose,
+                             int64_t obstacle_ld, double* qdot_out, int32_t* status,
+                             int32_t* iters, void* stream);
+int drc_qpik_stages_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                    int64_t B, const double* q, const double* qdot,
+                                    const double* x_target, const double* xdot_target,
+                                    const double* x_init, const double* xdot_init,
+                                    const double* obstacle_pose, int64_t obstacle_ld,
+                                    double* pose, double* jac, double* man, double* dist,
+                                    int32_t* pair, double* xdot_des, void* stream);
+
+/* drc_qpik_rollout_batch on a model with obstacle slots: obstacle_pose and
+ * obstacle_ld as above; obstacles_per_step = 0: one pose set for the horizon,
+ * 1: obstacle_pose [steps][n][12][obstacle_ld] (or [steps][n][12] with
+ * obstacle_ld = 0), one set per step: moving obstacles, as targets_per_step
+ * does for targets.  Runs step by step (no persistent kernel takes poses):
+ * bit-identical to `steps` drc_qpik_obstacles_batch calls with the state update
+ * of drc_qpik_rollout_batch.  (Reference: no counterpart.) */
+int drc_qpik_rollout_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                     int64_t B, int steps, double dt,
+                                     const double* q0, const double* qdot0,
+                                     const double* x_target, const double* xdot_target,
+                                     const double* x_init, const double* xdot_init,
+                                     int targets_per_step,
+                                     const double* obstacle_pose, int64_t obstacle_ld,
+                                     int obstacles_per_step,
+                                     double* q_final, double* qdot_final,
+                                     double* qdot_traj, int32_t* status_traj, int32_t* iters_traj,
+                                     double* q_traj, double* pose_traj, double* dist_traj,
+                                     void* stream);
 
 /* Host-buffer forms of drc_qpik_batch / drc_qpik_stages_batch: same
  * arguments, but every array is a HOST array ([field][B], row stride B).  The
