@@ -158,6 +158,73 @@ def qpik_rollout_batch(model, params, q, qdot, steps, dt, x_target=None, xdot_ta
     return res
 
 
+REACH_FIELDS = ("status_last", "iters_total", "err_final", "dist_final")
+
+
+def reach_thresholds(pos_tol, rot_tol):
+    """``drc_reach_thresholds``: (tau_p, tau_R), the numbers ``drc_qpik_reach_batch``
+    compares ``err_final``'s two rows with."""
+    out = (C.c_double * 2)()
+    _capi.check(_capi.lib().drc_reach_thresholds(C.c_double(pos_tol), C.c_double(rot_tol), out))
+    return float(out[0]), float(out[1])
+
+
+class ReachResult:
+    """Device tensors of one ``drc_qpik_reach_batch`` call: ``q_final``,
+    ``qdot_final`` [dof][B], ``result`` [B] (REACHED, BUDGET or QP_FAILED),
+    ``steps_used`` [B], and those of ``status_last`` [B], ``iters_total`` [B],
+    ``err_final`` [2][B] (e_p, e_R), ``dist_final`` [1+dof][B] that were asked
+    for (None otherwise); ``thresholds``: (tau_p, tau_R) on the host."""
+    REACHED, BUDGET, QP_FAILED = _capi.REACH_REACHED, _capi.REACH_BUDGET, _capi.REACH_QP_FAILED
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def qpik_reach_batch(model, params, q, qdot, x_target, xdot_target, max_steps, dt, pos_tol=1e-4, rot_tol=1e-3,
+                     want=REACH_FIELDS, q_final=None, qdot_final=None, stream=None, obstacle_pose=None):
+    """Launch ``drc_qpik_reach_batch`` on device tensors laid out [field][B]
+    (``drc_qpik_reach_obstacles_batch`` with ``obstacle_pose``, see
+    obstacle_poses: one pose set for the horizon).  ``want``: the optional
+    outputs to allocate and fill (REACH_FIELDS); ``q_final`` / ``qdot_final``
+    may be given (``q`` / ``qdot`` themselves: in place)."""
+    torch = _torch()
+    dev = q.device
+    B = q.shape[1]
+    nv = model.dof
+    check_shapes(nv, B, q=q, qdot=qdot, x_target=x_target, xdot_target=xdot_target)
+    unknown = set(want) - set(REACH_FIELDS)
+    if unknown:
+        raise ValueError("unknown reach outputs %s (know %s)" % (sorted(unknown), REACH_FIELDS))
+    for name, t in (("q_final", q_final), ("qdot_final", qdot_final)):
+        if t is not None and (tuple(t.shape) != (nv, B) or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 [%d][B=%d] tensor" % (name, nv, B))
+    f = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    res = ReachResult(
+        q_final=f(nv, B) if q_final is None else q_final,
+        qdot_final=f(nv, B) if qdot_final is None else qdot_final,
+        result=i(B), steps_used=i(B),
+        status_last=i(B) if "status_last" in want else None,
+        iters_total=i(B) if "iters_total" in want else None,
+        err_final=f(2, B) if "err_final" in want else None,
+        dist_final=f(1 + nv, B) if "dist_final" in want else None,
+        thresholds=None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    head = (model.handle, C.byref(params), C.c_int64(B), C.c_int(int(max_steps)), C.c_double(dt),
+            C.c_double(pos_tol), C.c_double(rot_tol), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target))
+    tail = (_ptr(res.q_final), _ptr(res.qdot_final), _ptr(res.result), _ptr(res.steps_used), _ptr(res.status_last),
+            _ptr(res.iters_total), _ptr(res.err_final), _ptr(res.dist_final), C.c_void_p(stream))
+    if obstacle_pose is not None:
+        op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
+        _capi.check(_capi.lib().drc_qpik_reach_obstacles_batch(*head, _ptr(op), C.c_int64(ld), *tail))
+    else:
+        _capi.check(_capi.lib().drc_qpik_reach_batch(*head, *tail))
+    res.thresholds = reach_thresholds(pos_tol, rot_tol)
+    return res
+
+
 def qpid_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
                qddot=None, tau=None, status=None, iters=None, stream=None):
     """Launch ``drc_qpid_batch``: returns (qddot [na][B],

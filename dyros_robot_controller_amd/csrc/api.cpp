@@ -23,6 +23,7 @@
 #include "kernel_common.hpp"
 #include "launch.hpp"
 #include "mesh.hpp"
+#include "reach.hpp"
 
 // ==========================================================================
 // host side: the C-ABI (include/drc_amd.h)
@@ -981,7 +982,7 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
 }
 
 // t_k = t + k dt as a rounded product and a rounded sum (the persistent
-// kernel's rollout_time, rollout_kernel.hip)
+// kernel's rollout_time, rollout_update.hpp)
 static double rollout_time(double t, int k, double dt) {
   volatile double d = static_cast<double>(k) * dt;
   return t + d;
@@ -1103,6 +1104,128 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
       return rc;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_integrate_kernel(
         B, st, m->d_model, dt, qk, eta_k, qf, vf, q_traj ? q_traj + int64_t(k) * nv * B : nullptr)));
+  }
+  done_guard.ok = true;
+  return DRC_OK;
+}
+
+static const char kSlotsReachMsg[] =
+    "the model has obstacle slots: pass their poses through drc_qpik_reach_obstacles_batch";
+
+static bool finite_positive(double x) { return std::isfinite(x) && x > 0; }
+
+// drc_qpik_reach_batch: the QPIKStep loop towards x_target with per-instance
+// stopping (include/drc_amd.h), enqueued on the caller's stream.  The compiled
+// QP shapes without hulls or slots, up to reach_max instances, run the
+// persistent kernel (reach_kernel.hip: a wave leaves an instance when it stops
+// and takes the next).  Everything else runs step by step: the stage launch
+// (pose, d, grad d at the state), drc_qpik_batch's launch sequence and the
+// update kernel, which skips the instances that have stopped.  That path
+// cannot end early -- no host synchronisation, so the host does not know who
+// is still active: it enqueues max_steps steps, then one more stage launch
+// and update that settle the instances still active.  Same device functions
+// either way: identical bits (tests/test_gpu_reach.py).
+static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int max_steps, double dt,
+                 double pos_tol, double rot_tol, const double* q0, const double* qdot0, const double* xt,
+                 const double* xdt, double* qf, double* vf, int32_t* result, int32_t* steps_used,
+                 int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final, void* stream,
+                 const Obst* ob = nullptr) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  const bool slots = m->hm.dev.nobst > 0;
+  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsReachMsg);
+  if (!slots && ob)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "the model has no obstacle slots (drc_model_set_obstacles declares them)");
+  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
+  if (params->mode != DRC_MODE_QPIK_STEP)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_batch runs DRC_MODE_QPIK_STEP only");
+  if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
+  if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
+  if (!finite_positive(pos_tol) || !finite_positive(rot_tol))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  if (!qf || !vf || !result || !steps_used)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "q_final, qdot_final, result and steps_used are required");
+  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
+  if (B > 0 && (!q0 || !qdot0 || !xt || !xdt))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_target and xdot_target are required");
+  KParams kt, kq;
+  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
+  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (B == 0) return DRC_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DevModel& dm = m->hm.dev;
+  const int nv = dm.nv, na = kq.na;
+  double tau[2];
+  reach_thresholds(pos_tol, rot_tol, tau);
+  // The rollout's rule, up to the largest batch at which the persistent kernel
+  // was measured to beat the stepwise path at 32 steps -- every size measured,
+  // through 65 536, for both kinds (FR3 556 against 1 674 ms, Husky-FR3 43.9
+  // against 151.7 ms; profiles/reach_bench.json, DESIGN.md "Reach"): unlike a
+  // rollout's, a reach call's stepwise path pays the horizon for every
+  // instance.  DRC_REACH_MAX overrides (read per call, so that one process can
+  // measure both paths).  No persistent build has the hull narrow phase or
+  // takes obstacle poses
+  const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
+  const bool persistent = m->fused && m->lane_stage == 0 && B <= reach_max && kQpGroup == 64 &&
+                          qp_compiled(kq.nx, kq.ng, kq.np) && !slots && !dm.has_mesh;
+  StreamCtx* cx = nullptr;
+  DoneGuard done_guard{cx, st};
+  // one step's scratch: eta [na][B], then (stepwise) pose [12][B] and dist
+  // [1+nv][B], then status [B] and iters [B]
+  const int64_t n_dbl = int64_t(na) * B + (persistent ? 0 : int64_t(12 + 1 + nv) * B);
+  {
+    std::lock_guard<std::mutex> g(m->mu);
+    if (int r = stream_ctx(m, st, &cx)) return r;
+    const int64_t bytes = n_dbl * 8 + 2 * B * 4;
+    if (cx->roll_bytes < bytes) {
+      if (cx->roll) HIP_TRY(hipFree(cx->roll));  // synchronises: no launch still uses it
+      cx->roll = nullptr;
+      cx->roll_bytes = 0;
+      HIP_TRY(hipMalloc(&cx->roll, bytes));
+      cx->roll_bytes = bytes;
+    }
+  }
+  double* eta = static_cast<double*>(cx->roll);
+  double* s_pose = eta + int64_t(na) * B;
+  double* s_dist = s_pose + 12 * B;
+  int32_t* s_status = reinterpret_cast<int32_t*>(eta + n_dbl);
+  int32_t* s_iters = s_status + B;
+  const ReachArgs re{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
+                     err_final, dist_final};
+  if (persistent) {
+    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
+    const int64_t grid = B < cap ? B : cap;
+    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
+    IO io{B, 0, B, q0, qdot0, xt, xdt, nullptr, nullptr, eta, s_status, s_iters, nullptr, nullptr, nullptr, nullptr,
+          nullptr, nullptr, nullptr, 0};
+    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
+    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+    HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, re)));
+    done_guard.ok = true;
+    return DRC_OK;
+  }
+  // the finals carry the state from the start; every instance active
+  const size_t state_bytes = size_t(nv) * B * 8;
+  if (qf != q0) HIP_TRY(hipMemcpyAsync(qf, q0, state_bytes, hipMemcpyDeviceToDevice, st));
+  if (vf != qdot0) HIP_TRY(hipMemcpyAsync(vf, qdot0, state_bytes, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetAsync(result, 0xff, size_t(B) * 4, st));  // kReachActive
+  if (status_last) HIP_TRY(hipMemsetAsync(status_last, 0, size_t(B) * 4, st));
+  if (iters_total) HIP_TRY(hipMemsetAsync(iters_total, 0, size_t(B) * 4, st));
+  for (int k = 0; k <= max_steps; ++k) {
+    const int last = k == max_steps;
+    if (int rc = launch_locked(m, params, 1, B, qf, vf, xt, xdt, nullptr, nullptr, nullptr, nullptr, nullptr, s_pose,
+                               nullptr, nullptr, s_dist, nullptr, nullptr, stream, nullptr, ob))
+      return rc;
+    if (!last)
+      if (int rc = launch_locked(m, params, 0, B, qf, vf, xt, xdt, nullptr, nullptr, eta, s_status, s_iters, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, stream, nullptr, ob))
+        return rc;
+    HIP_TRY(static_cast<hipError_t>(launch_reach_update_kernel(B, st, m->d_model, k, last, re, xt, s_pose, s_dist, eta,
+                                                               s_status, s_iters)));
   }
   done_guard.ok = true;
   return DRC_OK;
@@ -1833,6 +1956,36 @@ int drc_qpik_rollout_obstacles_batch(const drc_model* m, const drc_qpik_params* 
   return drc_amd::rollout(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step, q_final, qdot_final,
                           qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream, &ob,
                           obstacles_per_step);
+}
+
+// ---- goal-reaching rollouts ------------------------------------------------------
+int drc_qpik_reach_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int max_steps, double dt,
+                         double pos_tol, double rot_tol, const double* q0, const double* qdot0, const double* xt,
+                         const double* xdt, double* q_final, double* qdot_final, int32_t* result,
+                         int32_t* steps_used, int32_t* status_last, int32_t* iters_total, double* err_final,
+                         double* dist_final, void* stream) {
+  return drc_amd::reach(m, p, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt, q_final, qdot_final, result,
+                        steps_used, status_last, iters_total, err_final, dist_final, stream);
+}
+
+int drc_qpik_reach_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int max_steps, double dt,
+                                   double pos_tol, double rot_tol, const double* q0, const double* qdot0,
+                                   const double* xt, const double* xdt, const double* obstacle_pose,
+                                   int64_t obstacle_ld, double* q_final, double* qdot_final, int32_t* result,
+                                   int32_t* steps_used, int32_t* status_last, int32_t* iters_total,
+                                   double* err_final, double* dist_final, void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  return drc_amd::reach(m, p, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt, q_final, qdot_final, result,
+                        steps_used, status_last, iters_total, err_final, dist_final, stream, &ob);
+}
+
+int drc_reach_thresholds(double pos_tol, double rot_tol, double out[2]) {
+  using drc_amd::set_err;
+  if (!out) return set_err(DRC_ERR_INVALID_ARGUMENT, "out is required");
+  if (!drc_amd::finite_positive(pos_tol) || !drc_amd::finite_positive(rot_tol))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  drc_amd::reach_thresholds(pos_tol, rot_tol, out);
+  return DRC_OK;
 }
 
 // ---- QPID -------------------------------------------------

@@ -53,6 +53,34 @@ int launch_rollout_kernel(unsigned grid, hipStream_t st, const DevModel* m, cons
 int launch_rollout_integrate_kernel(int64_t B, hipStream_t st, const DevModel* m, double dt, const double* q_in,
                                     const double* eta, double* qf, double* vf, double* q_traj);
 
+// drc_qpik_reach_batch (reach_kernel.hip): what its kernels need beyond IO.
+// tau_p, tau_r: the thresholds of reach.hpp; qf / vf [dof][B] hold the state;
+// result / steps_used [B]; status_last, iters_total [B], err_final [2][B] and
+// dist_final [1+dof][B] may be NULL
+struct ReachArgs {
+  int max_steps;
+  double dt, tau_p, tau_r;
+  double *qf, *vf;
+  int32_t *result, *steps_used, *status_last, *iters_total;
+  double *err_final, *dist_final;
+};
+// `result` of an instance that has not stopped yet (stepwise path; every byte 0xff)
+constexpr int32_t kReachActive = -1;
+// persistent reach kernel (compiled QPIK shapes without hulls or obstacle
+// slots, hipErrorInvalidValue otherwise): per instance task stage, verdict, QP
+// and state update until it stops.  io as for launch_fused_kernel, with out /
+// status / iters one step's scratch (all three required) and xt the target.
+// The LDS size follows from kt and kq
+int launch_reach_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
+                        const IO& io, const ReachArgs& re);
+// step k of the stepwise path: the verdict of every instance still active from
+// the stage outputs pose [12][B] / dist [1+dof][B] at the state in re.qf /
+// re.vf, then (last = 0) the step's status and the state update from eta
+// [na][B]; last = 1: k = max_steps, no QP ran (eta, status, iters unused)
+int launch_reach_update_kernel(int64_t B, hipStream_t st, const DevModel* m, int k, int last, const ReachArgs& re,
+                               const double* xt, const double* pose, const double* dist, const double* eta,
+                               const int32_t* status, const int32_t* iters);
+
 // queue order of one sub-batch (order_kernel.hip): penetration-prone
 // instances first (*hot_n zeroed; hot_list [B], hot_flag [B] scratch), then the
 // others in index order, into order[b0 .. b0 + B)

@@ -15,50 +15,14 @@
 //
 // rollout_integrate_kernel: the state update alone, one thread per instance,
 // for the stepwise path (api.cpp: drc_qpik_batch's launch sequence per step,
-// then this kernel).  Both forms call rollout_velocity / rollout_advance, so
-// the two paths return identical bits.
+// then this kernel).  Both forms call rollout_velocity / rollout_advance
+// (rollout_update.hpp), so the two paths return identical bits.
 #include "task_stage.hpp"
 #include "qp_solver.hpp"
 #include "launch.hpp"
+#include "rollout_update.hpp"
 
 namespace drc_amd {
-
-// v_{k+1} of joint row r.  Manipulator: eta.  Mobile manipulator: S(q_k) eta
-// with the selection matrix of mobile_manipulator/robot_data.cpp:22-25,115-120
-// -- identity on the arm and wheel rows, Rz(yaw) J_mobile on the virtual rows
-// (the products qp_assemble forms for J~ = J S).  eta(a): actuated entry a.
-template <class Eta>
-__device__ __forceinline__ double rollout_velocity(const DevModel* M, int r, double cy, double sy,
-                                                   const double (*Jm)[kMaxWheels], Eta eta) {
-  if (M->kind == 0) return eta(r);
-  const int a = r - M->mani_start, w = r - M->mobi_start, v = r - M->virtual_start;
-  if (a >= 0 && a < M->n_arm) return eta(M->act_mani_start + a);
-  if (w >= 0 && w < M->n_wheel) return eta(M->act_mobi_start + w);
-  if (v < 0 || v > 2) return 0.0;
-  double s = 0;
-  for (int c = 0; c < M->n_wheel; ++c) {
-    double sv;
-    if (v == 0) sv = cy * Jm[0][c] - sy * Jm[1][c];
-    else if (v == 1) sv = sy * Jm[0][c] + cy * Jm[1][c];
-    else sv = Jm[2][c];
-    s += sv * eta(M->act_mobi_start + c);
-  }
-  return s;
-}
-
-// q_{k+1} = q_k + dt v_{k+1}: a rounded product, then a rounded sum (never an
-// fma), so numpy's q + dt * v reproduces it bit for bit
-__device__ __forceinline__ double rollout_advance(double q, double dt, double v) {
-#pragma clang fp contract(off)
-  const double d = dt * v;
-  return q + d;
-}
-// t_k = t + k dt, rounded the same way (the host of the stepwise path: api.cpp)
-__device__ __forceinline__ double rollout_time(double t, int k, double dt) {
-#pragma clang fp contract(off)
-  const double d = static_cast<double>(k) * dt;
-  return t + d;
-}
 
 #ifndef DRC_ROLLOUT_MESH
 // Stepwise path: one thread per instance.  q_in may be qf (in place): the yaw
@@ -99,24 +63,6 @@ struct Rollout {
   double *q_traj, *pose_traj, *dist_traj;
   int64_t out_step;  // doubles between two steps' eta in io.out (0: one scratch slot, no qdot_traj)
 };
-
-// LDS of the state update: q_k [nv], eta_k [na], J_mobile [3][kMaxWheels].
-// It lies at the start of the plan, not past it: once the QP has stored its
-// outputs nothing in the plan is live (the next task stage rewrites it from
-// the state arrays), so the kernel needs no more LDS than the fused kernel
-// and keeps its waves per CU (fused_rec_offset's comment).
-__host__ __device__ __forceinline__ int rollout_state_doubles(const KParams& kt, const KParams& kq) {
-  return ((kt.nv + 1) & ~1) + ((kq.na + 1) & ~1) + 3 * kMaxWheels;
-}
-
-// Orders this wave's global stores before its later loads of the same
-// addresses: the stores have completed when the wait returns, and a CU's
-// vector L1 is write-through, so the wave's own reload sees them.  (The IO
-// pointers are not __restrict__, so the compiler keeps the program order too.)
-__device__ __forceinline__ void state_visible() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
 
 #ifndef DRC_FUSED_WAVES
 #define DRC_FUSED_WAVES 2

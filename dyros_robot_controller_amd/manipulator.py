@@ -345,6 +345,22 @@ def _rollout(ctrl, kv, q, qdot, x_target, xdot_target, link_name, steps, dt, mod
                                      targets_per_step=targets_per_step, want=want, obstacle_pose=obstacle_pose)
 
 
+def _reach(ctrl, kv, q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol, xdot_target, w_reg,
+           obstacle_pose, want):
+    """QPIK_reach_batch of both controllers (``kv``: the task Kv of its QPIKStep)."""
+    p = ctrl._pb.params(link_name, _capi.MODE_QPIK_STEP, ctrl.Kp_task_, kv)
+    if w_reg is not None:
+        p.w_reg = float(w_reg)
+    dev = ctrl.robot_data_.device
+    q = _batch.as_device(q, dev)
+    if xdot_target is None:
+        xdot_target = np.zeros((6, q.shape[1]))
+    return _batch.qpik_reach_batch(ctrl.robot_data_.model, p, q, _batch.as_device(qdot, dev),
+                                   _batch.as_device(x_target, dev), _batch.as_device(xdot_target, dev), max_steps,
+                                   ctrl.dt_ if dt is None else dt, pos_tol, rot_tol, want=want,
+                                   obstacle_pose=obstacle_pose)
+
+
 class RobotController:
     """Manipulator::RobotController QPIK entries
     (src/manipulator/robot_controller.cpp:7-19,277-317).
@@ -471,6 +487,18 @@ class RobotController:
         axis for obstacles that move."""
         return _rollout(self, self.Kv_task_, q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init,
                         xdot_init, current_time, init_time, duration, targets_per_step, want, obstacle_pose)
+
+    def QPIK_reach_batch(self, q, qdot, x_target, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
+                         xdot_target=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_FIELDS):
+        """Closed-loop QPIKStep towards the pose ``x_target`` [12][B], on the
+        device, until each instance is within ``pos_tol`` metres and ``rot_tol``
+        radians of it (REACHED), has taken ``max_steps`` steps (BUDGET) or meets
+        a QP that is not solved (QP_FAILED): a _batch.ReachResult.
+        ``xdot_target`` None: zeros; ``w_reg`` None: the default regulariser.
+        The default gains are those of a 1 kHz tracker: to converge within tens
+        of steps use e.g. Kp 100, Kv 0, w_reg 0.01 at dt 5 ms (DESIGN.md "Reach")."""
+        return _reach(self, self.Kv_task_, q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol,
+                      xdot_target, w_reg, obstacle_pose, want)
 
     # -- single-instance entries (reference signatures; B = 1 launches) -------
     def _one(self, out_status):

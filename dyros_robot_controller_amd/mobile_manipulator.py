@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _batch, _capi
 from ._capi import C
-from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, _rollout, pose_to12
+from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, _reach, _rollout, pose_to12
 
 
 class DriveType(IntEnum):
@@ -493,6 +493,18 @@ class RobotController:
         (``qdot_traj``: eta in ActuatorIndex order, as QPIK_step_batch)."""
         return _rollout(self, np.zeros(6), q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init,
                         xdot_init, current_time, init_time, duration, targets_per_step, want, obstacle_pose)
+
+    def QPIK_reach_batch(self, q, qdot, x_target, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
+                         xdot_target=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_FIELDS):
+        """Closed-loop QPIKStep towards the pose ``x_target`` [12][B] on the
+        device (the state update of QPIK_rollout_batch) until each instance is
+        within ``pos_tol`` metres and ``rot_tol`` radians of it (REACHED), has
+        taken ``max_steps`` steps (BUDGET) or meets a QP that is not solved
+        (QP_FAILED): a _batch.ReachResult.  ``xdot_target`` None: zeros;
+        ``w_reg`` None: the default.  Kp 400 wants dt 1 ms: at 5 ms Kp dt = 2
+        does not settle (DESIGN.md "Reach")."""
+        return _reach(self, np.zeros(6), q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol, xdot_target,
+                      w_reg, obstacle_pose, want)
 
     def split_actuated(self, eta):
         """eta [A] -> (qdot_mobile [W], qdot_mani [n]) by ActuatorIndex."""

@@ -307,7 +307,7 @@ int drc_qpik_stages_batch(const drc_model* model, const drc_qpik_params* params,
  * DRC_ERR_UNSUPPORTED: more than 64 geometries or 1024 pairs in all, a mesh
  * obstacle, or a model with collision meshes (hull models take no obstacles).
  * While a model has slots, the plain drc_qpik_batch / drc_qpik_stages_batch /
- * drc_qpik_rollout_batch and their host forms return DRC_ERR_INVALID_ARGUMENT
+ * drc_qpik_rollout_batch / drc_qpik_reach_batch and their host forms return DRC_ERR_INVALID_ARGUMENT
  * (they have no poses to give), and drc_qpid_*, drc_clik_batch, drc_osf_batch,
  * drc_closed_form_host, drc_joint_torque_step_* and drc_debug_lane_stage return
  * DRC_ERR_UNSUPPORTED; kinematics and dynamics entries are unaffected.
@@ -357,6 +357,87 @@ int drc_qpik_rollout_obstacles_batch(const drc_model* model, const drc_qpik_para
                                      double* qdot_traj, int32_t* status_traj, int32_t* iters_traj,
                                      double* q_traj, double* pose_traj, double* dist_traj,
                                      void* stream);
+
+/* ---- goal-reaching rollouts: how an instance of drc_qpik_reach_batch stopped */
+enum {
+    DRC_REACH_REACHED = 0,       /* pose within pos_tol and rot_tol of x_target        */
+    DRC_REACH_BUDGET = 1,        /* max_steps steps taken and still outside them       */
+    DRC_REACH_QP_FAILED = 2      /* a step's QP was not solved; the state is unchanged */
+};
+
+/* Goal-reaching rollout: the closed loop of drc_qpik_rollout_batch in mode
+ * DRC_MODE_QPIK_STEP towards one pose x_target [12][B], where every instance
+ * stops on its own.  For each instance, with (q_0, v_0) = (q0, qdot0) and k = 0:
+ *   1. the task stage of drc_qpik_batch at (q_k, v_k) gives the pose of the
+ *      task frame (and d, grad d).  Its error against x_target is two numbers,
+ *      every product and sum rounded (no fma), in this order:
+ *        e_p = (dx*dx + dy*dy) + dz*dz, d = x_target[9..11] - pose[9..11];
+ *        e_R = sum over i = 0 .. 8, from 0 upward, of (pose[i] - x_target[i])^2
+ *            = |R - R_t|_F^2 = 8 sin^2(theta / 2);
+ *   2. e_p <= tau_p and e_R <= tau_R: DRC_REACH_REACHED, stop (a NaN fails
+ *      both comparisons and goes on to the QP);
+ *   3. k == max_steps: DRC_REACH_BUDGET, stop;
+ *   4. the step's QP gives (eta_k, status_k, iters_k), exactly drc_qpik_batch's
+ *      results on (q_k, v_k).  status_k != DRC_STATUS_SOLVED:
+ *      DRC_REACH_QP_FAILED, stop, the state unchanged (eta_k = 0: a fixed
+ *      horizon would solve the same failing QP at every remaining step).
+ *      Otherwise the state update of drc_qpik_rollout_batch (the same bits),
+ *      k += 1, back to 1.
+ * tau_p = pos_tol * pos_tol, tau_R = 8 * (s * s) with s = sin(0.5 * rot_tol),
+ * computed once on the host: drc_reach_thresholds returns the very numbers.
+ * params->t is not advanced (QPIKStep does not read it).
+ * Outputs, [..][B] field-major:
+ *   q_final, qdot_final [dof][B]: the state where the instance stopped, always
+ *       written (k = 0: the inputs); may alias q0 / qdot0; required;
+ *   result [B] (DRC_REACH_*), steps_used [B] (the k at the stop); required;
+ *   status_last [B]: the status of the last QP that ran, 0 if none ran;
+ *   iters_total [B]: the sum of the ADMM iterations;
+ *   err_final [2][B]: e_p, e_R at q_final;
+ *   dist_final [1+dof][B]: d, grad d at q_final, drc_qpik_stages_batch's layout;
+ *       these four may be NULL.
+ * A call takes at most max_steps QP solves and max_steps + 1 task stages per
+ * instance; max_steps = 0 only checks the error.
+ * The QP shapes the library compiles (drc_set_fusion), on a model without
+ * collision meshes or obstacle slots and up to DRC_REACH_MAX instances
+ * (default 65 536, the largest batch measured: the persistent kernel was
+ * faster at every size, DESIGN.md "Reach"), run as one persistent kernel
+ * whose waves leave an instance when it stops and take the next.  Everything
+ * else runs step by step: per step the stage launch, drc_qpik_batch's launches
+ * and an update kernel that skips the instances that have stopped.  That path
+ * cannot end early: it enqueues max_steps steps for the whole batch, and the
+ * stopped instances still run through the launches, their results ignored.
+ * Results are bit-identical either way.
+ * DRC_ERR_INVALID_ARGUMENT: a mode other than DRC_MODE_QPIK_STEP,
+ * max_steps < 0, dt / pos_tol / rot_tol not finite or not positive, a NULL
+ * required pointer, a model with obstacle slots (drc_qpik_reach_obstacles_batch
+ * takes their poses).  B = 0 returns DRC_OK.  Asynchronous on `stream`, no host
+ * synchronisation.  (Reference: no counterpart.) */
+int drc_qpik_reach_batch(const drc_model* model, const drc_qpik_params* params,
+                         int64_t B, int max_steps, double dt, double pos_tol, double rot_tol,
+                         const double* q0, const double* qdot0,
+                         const double* x_target, const double* xdot_target,
+                         double* q_final, double* qdot_final,
+                         int32_t* result, int32_t* steps_used,
+                         int32_t* status_last, int32_t* iters_total,
+                         double* err_final, double* dist_final, void* stream);
+
+/* drc_qpik_reach_batch on a model with obstacle slots: obstacle_pose and
+ * obstacle_ld as for drc_qpik_obstacles_batch, one pose set for the horizon.
+ * Runs step by step.  DRC_ERR_INVALID_ARGUMENT on a model without slots. */
+int drc_qpik_reach_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                   int64_t B, int max_steps, double dt, double pos_tol,
+                                   double rot_tol, const double* q0, const double* qdot0,
+                                   const double* x_target, const double* xdot_target,
+                                   const double* obstacle_pose, int64_t obstacle_ld,
+                                   double* q_final, double* qdot_final,
+                                   int32_t* result, int32_t* steps_used,
+                                   int32_t* status_last, int32_t* iters_total,
+                                   double* err_final, double* dist_final, void* stream);
+
+/* The thresholds of drc_qpik_reach_batch (host only, no device is touched):
+ * out[0] = tau_p, out[1] = tau_R.  DRC_ERR_INVALID_ARGUMENT: a tolerance that
+ * is not finite and positive, out NULL. */
+int drc_reach_thresholds(double pos_tol, double rot_tol, double out[2]);
 
 /* Host-buffer forms of drc_qpik_batch / drc_qpik_stages_batch: same
  * arguments, but every array is a HOST array ([field][B], row stride B).  The
