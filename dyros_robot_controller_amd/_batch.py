@@ -225,6 +225,70 @@ def qpik_reach_batch(model, params, q, qdot, x_target, xdot_target, max_steps, d
     return res
 
 
+REACH_PATH_FIELDS = REACH_FIELDS + ("dist_min", "steps_at")
+
+
+class ReachPathResult(ReachResult):
+    """Device tensors of one ``drc_qpik_reach_path_batch`` call: those of a
+    ReachResult (``steps_used`` the total over the call, ``err_final`` against
+    the waypoint the instance stopped at), ``waypoints_reached`` [B] (0 .. W),
+    and those of ``dist_min`` [B], ``steps_at`` [W][B] (-1: never reached) that
+    were asked for (None otherwise)."""
+
+
+def qpik_reach_path_batch(model, params, q, qdot, x_path, xdot_path, max_steps, dt, pos_tol=1e-4, rot_tol=1e-3,
+                          want=REACH_PATH_FIELDS, q_final=None, qdot_final=None, stream=None, obstacle_pose=None):
+    """Launch ``drc_qpik_reach_path_batch`` on device tensors: ``q`` / ``qdot``
+    [dof][B], ``x_path`` [W][12][B], ``xdot_path`` [W][6][B]
+    (``drc_qpik_reach_path_obstacles_batch`` with ``obstacle_pose``, see
+    obstacle_poses: one pose set for the call).  ``max_steps`` is the budget of
+    one segment.  ``want``: the optional outputs to allocate and fill
+    (REACH_PATH_FIELDS); ``q_final`` / ``qdot_final`` may be given (``q`` /
+    ``qdot`` themselves: in place)."""
+    torch = _torch()
+    dev = q.device
+    B = q.shape[1]
+    nv = model.dof
+    check_shapes(nv, B, q=q, qdot=qdot)
+    W = x_path.shape[0] if x_path.dim() == 3 else -1
+    for name, t, rows in (("x_path", x_path, 12), ("xdot_path", xdot_path, 6)):
+        if t.dim() != 3 or tuple(t.shape) != (W, rows, B):
+            raise ValueError("%s must be [W][%d][B=%d], got %s" % (name, rows, B, tuple(t.shape)))
+    unknown = set(want) - set(REACH_PATH_FIELDS)
+    if unknown:
+        raise ValueError("unknown reach path outputs %s (know %s)" % (sorted(unknown), REACH_PATH_FIELDS))
+    for name, t in (("q_final", q_final), ("qdot_final", qdot_final)):
+        if t is not None and (tuple(t.shape) != (nv, B) or t.dtype != torch.float64 or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float64 [%d][B=%d] tensor" % (name, nv, B))
+    f = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    res = ReachPathResult(
+        q_final=f(nv, B) if q_final is None else q_final,
+        qdot_final=f(nv, B) if qdot_final is None else qdot_final,
+        result=i(B), waypoints_reached=i(B), steps_used=i(B),
+        status_last=i(B) if "status_last" in want else None,
+        iters_total=i(B) if "iters_total" in want else None,
+        err_final=f(2, B) if "err_final" in want else None,
+        dist_final=f(1 + nv, B) if "dist_final" in want else None,
+        dist_min=f(B) if "dist_min" in want else None,
+        steps_at=i(W, B) if "steps_at" in want else None,
+        thresholds=None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    head = (model.handle, C.byref(params), C.c_int64(B), C.c_int(W), C.c_int(int(max_steps)), C.c_double(dt),
+            C.c_double(pos_tol), C.c_double(rot_tol), _ptr(q), _ptr(qdot), _ptr(x_path), _ptr(xdot_path))
+    tail = (_ptr(res.q_final), _ptr(res.qdot_final), _ptr(res.result), _ptr(res.waypoints_reached),
+            _ptr(res.steps_used), _ptr(res.status_last), _ptr(res.iters_total), _ptr(res.err_final),
+            _ptr(res.dist_final), _ptr(res.dist_min), _ptr(res.steps_at), C.c_void_p(stream))
+    if obstacle_pose is not None:
+        op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
+        _capi.check(_capi.lib().drc_qpik_reach_path_obstacles_batch(*head, _ptr(op), C.c_int64(ld), *tail))
+    else:
+        _capi.check(_capi.lib().drc_qpik_reach_path_batch(*head, *tail))
+    res.thresholds = reach_thresholds(pos_tol, rot_tol)
+    return res
+
+
 def qpid_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
                qddot=None, tau=None, status=None, iters=None, stream=None):
     """Launch ``drc_qpid_batch``: returns (qddot [na][B],

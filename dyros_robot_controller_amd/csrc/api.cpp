@@ -24,6 +24,7 @@
 #include "launch.hpp"
 #include "mesh.hpp"
 #include "reach.hpp"
+#include "reach_path.hpp"
 
 // ==========================================================================
 // host side: the C-ABI (include/drc_amd.h)
@@ -1231,6 +1232,147 @@ static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_
   return DRC_OK;
 }
 
+static const char kSlotsReachPathMsg[] =
+    "the model has obstacle slots: pass their poses through drc_qpik_reach_path_obstacles_batch";
+
+// drc_qpik_reach_path_batch: the loop of reach() through W waypoints
+// (include/drc_amd.h), enqueued on the caller's stream.  The compiled QP
+// shapes without hulls, up to reach_max instances, run the persistent kernel
+// (reach_path_kernel.hip); models with obstacle slots too, through its ObstIn
+// builds (reach_path_obstacle_kernel.hip).  Everything else runs in rounds of
+// the stage launch at every instance's current target (stream scratch, gathered
+// by the update kernel when the instance advances), drc_qpik_batch's launch
+// sequence and the update kernel.  An active instance steps or advances in
+// every round, at most W max_steps + W - 1 times, so W (max_steps + 1) rounds
+// stop every instance; one more stage launch and update without a QP settle
+// whatever is left.  Same device functions either way: identical bits
+// (tests/test_gpu_reach_path.py).
+static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int W, int max_steps,
+                      double dt, double pos_tol, double rot_tol, const double* q0, const double* qdot0,
+                      const double* x_path, const double* xdot_path, double* qf, double* vf, int32_t* result,
+                      int32_t* waypoints_reached, int32_t* steps_used, int32_t* status_last, int32_t* iters_total,
+                      double* err_final, double* dist_final, double* dist_min, int32_t* steps_at, void* stream,
+                      const Obst* ob = nullptr) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  const bool slots = m->hm.dev.nobst > 0;
+  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsReachPathMsg);
+  if (!slots && ob)
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   "the model has no obstacle slots (drc_model_set_obstacles declares them): "
+                   "drc_qpik_reach_path_batch runs it");
+  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
+  if (params->mode != DRC_MODE_QPIK_STEP)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_path_batch runs DRC_MODE_QPIK_STEP only");
+  if (W < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints must be at least 1");
+  if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
+  if (int64_t(W) * (int64_t(max_steps) + 1) > 0x7ffffff0)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints * (max_steps + 1) too large");  // 32-bit step counters
+  if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
+  if (!finite_positive(pos_tol) || !finite_positive(rot_tol))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  if (!qf || !vf || !result || !waypoints_reached || !steps_used)
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   "q_final, qdot_final, result, waypoints_reached and steps_used are required");
+  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
+  if (B > 0 && (!q0 || !qdot0 || !x_path || !xdot_path))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_path and xdot_path are required");
+  KParams kt, kq;
+  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
+  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (B == 0) return DRC_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DevModel& dm = m->hm.dev;
+  const int nv = dm.nv, na = kq.na;
+  double tau[2];
+  reach_thresholds(pos_tol, rot_tol, tau);
+  // reach()'s rule and its DRC_REACH_MAX (read per call), with the slots let in:
+  // the persistent kernel has builds that take their poses.  The default stays
+  // 65 536: the persistent kernel beat the stepwise path at every size measured
+  // through it, with 3 waypoints of 32 steps (FR3 1 191 against 8 654 ms,
+  // Husky-FR3 129 against 570 ms) and with four slots and one waypoint (FR3 565
+  // against 1 786 ms; profiles/reach_path_bench.json, DESIGN.md "Reach paths")
+  const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
+  const bool persistent = m->fused && m->lane_stage == 0 && B <= reach_max && kQpGroup == 64 &&
+                          qp_compiled(kq.nx, kq.ng, kq.np) && !dm.has_mesh;
+  StreamCtx* cx = nullptr;
+  DoneGuard done_guard{cx, st};
+  // scratch: one step's eta [na][B], then (stepwise) pose [12][B], dist
+  // [1+nv][B] and the current targets [12][B], [6][B]; then status [B], iters
+  // [B] and (stepwise) the segment counters [B]
+  const int64_t n_dbl = int64_t(na) * B + (persistent ? 0 : int64_t(12 + 1 + nv + 12 + 6) * B);
+  {
+    std::lock_guard<std::mutex> g(m->mu);
+    if (int r = stream_ctx(m, st, &cx)) return r;
+    const int64_t bytes = n_dbl * 8 + 3 * B * 4;
+    if (cx->roll_bytes < bytes) {
+      if (cx->roll) HIP_TRY(hipFree(cx->roll));  // synchronises: no launch still uses it
+      cx->roll = nullptr;
+      cx->roll_bytes = 0;
+      HIP_TRY(hipMalloc(&cx->roll, bytes));
+      cx->roll_bytes = bytes;
+    }
+  }
+  double* eta = static_cast<double*>(cx->roll);
+  double* s_pose = eta + int64_t(na) * B;
+  double* s_dist = s_pose + 12 * B;
+  double* s_xt = s_dist + int64_t(1 + nv) * B;
+  double* s_xdt = s_xt + 12 * B;
+  int32_t* s_status = reinterpret_cast<int32_t*>(eta + n_dbl);
+  int32_t* s_iters = s_status + B;
+  int32_t* s_seg = s_iters + B;
+  const ReachPathArgs rp{{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
+                          err_final, dist_final},
+                         W, x_path, xdot_path, waypoints_reached, dist_min, steps_at, s_xt, s_xdt, s_seg};
+  if (persistent) {
+    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
+    const int64_t grid = B < cap ? B : cap;
+    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
+    IO io{B, 0, B, q0, qdot0, x_path, xdot_path, nullptr, nullptr, eta, s_status, s_iters, nullptr, nullptr, nullptr,
+          nullptr, nullptr, nullptr, nullptr, 0};
+    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
+    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+    HIP_TRY(static_cast<hipError_t>(
+        slots ? launch_reach_path_obstacle_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rp, *ob)
+              : launch_reach_path_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rp)));
+    done_guard.ok = true;
+    return DRC_OK;
+  }
+  // the finals carry the state from the start; every instance active, at
+  // waypoint 0 with no step taken
+  const size_t state_bytes = size_t(nv) * B * 8;
+  if (qf != q0) HIP_TRY(hipMemcpyAsync(qf, q0, state_bytes, hipMemcpyDeviceToDevice, st));
+  if (vf != qdot0) HIP_TRY(hipMemcpyAsync(vf, qdot0, state_bytes, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s_xt, x_path, size_t(12) * B * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s_xdt, xdot_path, size_t(6) * B * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetAsync(result, 0xff, size_t(B) * 4, st));  // kReachActive
+  HIP_TRY(hipMemsetAsync(waypoints_reached, 0, size_t(B) * 4, st));
+  HIP_TRY(hipMemsetAsync(steps_used, 0, size_t(B) * 4, st));
+  HIP_TRY(hipMemsetAsync(s_seg, 0, size_t(B) * 4, st));
+  if (status_last) HIP_TRY(hipMemsetAsync(status_last, 0, size_t(B) * 4, st));
+  if (iters_total) HIP_TRY(hipMemsetAsync(iters_total, 0, size_t(B) * 4, st));
+  if (steps_at) HIP_TRY(hipMemsetAsync(steps_at, 0xff, size_t(W) * B * 4, st));  // -1: never reached
+  const int64_t rounds = int64_t(W) * (int64_t(max_steps) + 1);
+  for (int64_t r = 0; r <= rounds; ++r) {
+    const int last = r == rounds;
+    if (int rc = launch_locked(m, params, 1, B, qf, vf, s_xt, s_xdt, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               s_pose, nullptr, nullptr, s_dist, nullptr, nullptr, stream, nullptr, ob))
+      return rc;
+    if (!last)
+      if (int rc = launch_locked(m, params, 0, B, qf, vf, s_xt, s_xdt, nullptr, nullptr, eta, s_status, s_iters,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, nullptr, ob))
+        return rc;
+    HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, s_pose, s_dist,
+                                                                    eta, s_status, s_iters)));
+  }
+  done_guard.ok = true;
+  return DRC_OK;
+}
+
 // QPID pipeline for one call: dynamics launch(es) -> task kernel (QPID stage
 // data into the records) -> QPID kernel; or, with stages, the task kernel
 // writing the stage outputs.  Model-owned scratch holds the records and the
@@ -1977,6 +2119,31 @@ int drc_qpik_reach_obstacles_batch(const drc_model* m, const drc_qpik_params* p,
   const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
   return drc_amd::reach(m, p, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt, q_final, qdot_final, result,
                         steps_used, status_last, iters_total, err_final, dist_final, stream, &ob);
+}
+
+int drc_qpik_reach_path_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int waypoints, int max_steps,
+                              double dt, double pos_tol, double rot_tol, const double* q0, const double* qdot0,
+                              const double* x_path, const double* xdot_path, double* q_final, double* qdot_final,
+                              int32_t* result, int32_t* waypoints_reached, int32_t* steps_used, int32_t* status_last,
+                              int32_t* iters_total, double* err_final, double* dist_final, double* dist_min,
+                              int32_t* steps_at, void* stream) {
+  return drc_amd::reach_path(m, p, B, waypoints, max_steps, dt, pos_tol, rot_tol, q0, qdot0, x_path, xdot_path,
+                             q_final, qdot_final, result, waypoints_reached, steps_used, status_last, iters_total,
+                             err_final, dist_final, dist_min, steps_at, stream);
+}
+
+int drc_qpik_reach_path_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int waypoints,
+                                        int max_steps, double dt, double pos_tol, double rot_tol, const double* q0,
+                                        const double* qdot0, const double* x_path, const double* xdot_path,
+                                        const double* obstacle_pose, int64_t obstacle_ld, double* q_final,
+                                        double* qdot_final, int32_t* result, int32_t* waypoints_reached,
+                                        int32_t* steps_used, int32_t* status_last, int32_t* iters_total,
+                                        double* err_final, double* dist_final, double* dist_min, int32_t* steps_at,
+                                        void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  return drc_amd::reach_path(m, p, B, waypoints, max_steps, dt, pos_tol, rot_tol, q0, qdot0, x_path, xdot_path,
+                             q_final, qdot_final, result, waypoints_reached, steps_used, status_last, iters_total,
+                             err_final, dist_final, dist_min, steps_at, stream, &ob);
 }
 
 int drc_reach_thresholds(double pos_tol, double rot_tol, double out[2]) {

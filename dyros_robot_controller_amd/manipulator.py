@@ -361,6 +361,23 @@ def _reach(ctrl, kv, q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_t
                                    obstacle_pose=obstacle_pose)
 
 
+def _reach_path(ctrl, kv, q, qdot, x_path, link_name, max_steps, dt, pos_tol, rot_tol, xdot_path, w_reg,
+                obstacle_pose, want):
+    """QPIK_reach_path_batch of both controllers (``kv``: the task Kv of its QPIKStep)."""
+    p = ctrl._pb.params(link_name, _capi.MODE_QPIK_STEP, ctrl.Kp_task_, kv)
+    if w_reg is not None:
+        p.w_reg = float(w_reg)
+    dev = ctrl.robot_data_.device
+    q = _batch.as_device(q, dev)
+    x_path = _batch.as_device(x_path, dev)
+    if xdot_path is None:
+        xdot_path = np.zeros((x_path.shape[0], 6, q.shape[1]))
+    return _batch.qpik_reach_path_batch(ctrl.robot_data_.model, p, q, _batch.as_device(qdot, dev), x_path,
+                                        _batch.as_device(xdot_path, dev), max_steps,
+                                        ctrl.dt_ if dt is None else dt, pos_tol, rot_tol, want=want,
+                                        obstacle_pose=obstacle_pose)
+
+
 class RobotController:
     """Manipulator::RobotController QPIK entries
     (src/manipulator/robot_controller.cpp:7-19,277-317).
@@ -499,6 +516,17 @@ class RobotController:
         of steps use e.g. Kp 100, Kv 0, w_reg 0.01 at dt 5 ms (DESIGN.md "Reach")."""
         return _reach(self, self.Kv_task_, q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol,
                       xdot_target, w_reg, obstacle_pose, want)
+
+    def QPIK_reach_path_batch(self, q, qdot, x_path, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
+                              xdot_path=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_PATH_FIELDS):
+        """QPIK_reach_batch through the waypoints ``x_path`` [W][12][B] in turn,
+        in one device call: an instance within the tolerances of waypoint w goes
+        on to waypoint w + 1 with a fresh budget of ``max_steps`` steps, and
+        stops after the last one (REACHED), out of budget (BUDGET) or at a QP
+        that is not solved (QP_FAILED): a _batch.ReachPathResult.
+        ``xdot_path`` None: zeros (DESIGN.md "Reach paths")."""
+        return _reach_path(self, self.Kv_task_, q, qdot, x_path, link_name, max_steps, dt, pos_tol, rot_tol,
+                           xdot_path, w_reg, obstacle_pose, want)
 
     # -- single-instance entries (reference signatures; B = 1 launches) -------
     def _one(self, out_status):

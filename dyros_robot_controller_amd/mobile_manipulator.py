@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _batch, _capi
 from ._capi import C
-from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, _reach, _rollout, pose_to12
+from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, _reach, _reach_path, _rollout, pose_to12
 
 
 class DriveType(IntEnum):
@@ -505,6 +505,17 @@ class RobotController:
         does not settle (DESIGN.md "Reach")."""
         return _reach(self, np.zeros(6), q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol, xdot_target,
                       w_reg, obstacle_pose, want)
+
+    def QPIK_reach_path_batch(self, q, qdot, x_path, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
+                              xdot_path=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_PATH_FIELDS):
+        """QPIK_reach_batch through the waypoints ``x_path`` [W][12][B] in turn,
+        in one device call: an instance within the tolerances of waypoint w goes
+        on to waypoint w + 1 with a fresh budget of ``max_steps`` steps, and
+        stops after the last one (REACHED), out of budget (BUDGET) or at a QP
+        that is not solved (QP_FAILED): a _batch.ReachPathResult.
+        ``xdot_path`` None: zeros (DESIGN.md "Reach paths")."""
+        return _reach_path(self, np.zeros(6), q, qdot, x_path, link_name, max_steps, dt, pos_tol, rot_tol, xdot_path,
+                           w_reg, obstacle_pose, want)
 
     def split_actuated(self, eta):
         """eta [A] -> (qdot_mobile [W], qdot_mani [n]) by ActuatorIndex."""

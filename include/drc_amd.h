@@ -423,7 +423,9 @@ int drc_qpik_reach_batch(const drc_model* model, const drc_qpik_params* params,
 
 /* drc_qpik_reach_batch on a model with obstacle slots: obstacle_pose and
  * obstacle_ld as for drc_qpik_obstacles_batch, one pose set for the horizon.
- * Runs step by step.  DRC_ERR_INVALID_ARGUMENT on a model without slots. */
+ * Runs step by step (drc_qpik_reach_path_obstacles_batch with one waypoint
+ * gives the same results from a persistent kernel).
+ * DRC_ERR_INVALID_ARGUMENT on a model without slots. */
 int drc_qpik_reach_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
                                    int64_t B, int max_steps, double dt, double pos_tol,
                                    double rot_tol, const double* q0, const double* qdot0,
@@ -433,6 +435,83 @@ int drc_qpik_reach_obstacles_batch(const drc_model* model, const drc_qpik_params
                                    int32_t* result, int32_t* steps_used,
                                    int32_t* status_last, int32_t* iters_total,
                                    double* err_final, double* dist_final, void* stream);
+
+/* Goal-reaching rollout through waypoints: the loop of drc_qpik_reach_batch
+ * towards W = `waypoints` poses in turn.  x_path [W][12][B] and xdot_path
+ * [W][6][B] are laid out as the per-step targets of drc_qpik_rollout_batch.
+ * Mode DRC_MODE_QPIK_STEP only.  For each instance, with (q_0, v_0) =
+ * (q0, qdot0), the total step count k = 0, the segment step count s = 0, the
+ * waypoint index w = 0 and dist_min = +inf:
+ *   1. the task stage of drc_qpik_batch at (q_k, v_k) with waypoint w as the
+ *      target gives the pose, d and grad d.  d < dist_min: dist_min = d (a NaN
+ *      is never taken);
+ *   2. (e_p, e_R) against x_path[w], formed and compared exactly as in
+ *      drc_qpik_reach_batch (drc_reach_thresholds).  Within: steps_at[w] = k,
+ *      w += 1, s = 0; w == W: DRC_REACH_REACHED, stop; otherwise back to 1 at
+ *      the same state with the new target (the pose and d do not depend on the
+ *      target, the task record the QP reads does);
+ *   3. s == max_steps: DRC_REACH_BUDGET, stop -- the budget is per segment;
+ *   4. the step's QP, exactly drc_qpik_batch on (q_k, v_k) towards x_path[w] /
+ *      xdot_path[w].  Not solved: DRC_REACH_QP_FAILED, stop, the state
+ *      unchanged.  Otherwise the state update of drc_qpik_rollout_batch (the
+ *      same bits), k += 1, s += 1, back to 1.
+ * This is, bit for bit, W chained drc_qpik_reach_batch calls, each starting
+ * from the previous q_final / qdot_final, where an instance goes on to the
+ * next call only if its previous result is DRC_REACH_REACHED; W = 1 is
+ * drc_qpik_reach_batch itself.
+ * Outputs, [..][B] field-major:
+ *   q_final, qdot_final [dof][B]: may alias q0 / qdot0; result [B]
+ *       (DRC_REACH_*); waypoints_reached [B]: the w at the stop, 0 .. W;
+ *       steps_used [B]: the total k; these five are required;
+ *   status_last [B]: the status of the last QP that ran in the whole call, 0 if
+ *       none ran; iters_total [B]: the sum of the ADMM iterations over the call;
+ *   err_final [2][B]: the error against waypoint min(w, W - 1) at q_final;
+ *   dist_final [1+dof][B]: d, grad d at q_final;
+ *   dist_min [B]: the least d over every state at which the stage ran;
+ *   steps_at [W][B]: the k at which waypoint w was found reached, -1 for those
+ *       never reached; these six may be NULL.
+ * A call takes at most W max_steps QP solves and W max_steps + W task stages
+ * per instance; max_steps = 0 only walks through the waypoints that are
+ * already satisfied.
+ * The dispatch is drc_qpik_reach_batch's (compiled QP shape, no collision
+ * meshes, drc_set_fusion, up to DRC_REACH_MAX instances: one persistent
+ * kernel), except that a model with obstacle slots qualifies too, through
+ * drc_qpik_reach_path_obstacles_batch.  Everything else runs in W (max_steps
+ * + 1) rounds of the stage launch, drc_qpik_batch's launches and an update
+ * kernel, every instance's current target held in stream scratch.  Results are
+ * bit-identical either way.
+ * DRC_ERR_INVALID_ARGUMENT: as drc_qpik_reach_batch, waypoints < 1, a model
+ * with obstacle slots (drc_qpik_reach_path_obstacles_batch takes their poses).
+ * B = 0 returns DRC_OK.  Asynchronous on `stream`, no host synchronisation.
+ * (Reference: no counterpart.) */
+int drc_qpik_reach_path_batch(const drc_model* model, const drc_qpik_params* params,
+                              int64_t B, int waypoints, int max_steps, double dt,
+                              double pos_tol, double rot_tol,
+                              const double* q0, const double* qdot0,
+                              const double* x_path, const double* xdot_path,
+                              double* q_final, double* qdot_final,
+                              int32_t* result, int32_t* waypoints_reached, int32_t* steps_used,
+                              int32_t* status_last, int32_t* iters_total,
+                              double* err_final, double* dist_final,
+                              double* dist_min, int32_t* steps_at, void* stream);
+
+/* drc_qpik_reach_path_batch on a model with obstacle slots: obstacle_pose and
+ * obstacle_ld as for drc_qpik_reach_obstacles_batch, one pose set for the
+ * call.  The persistent kernel where the dispatch above allows it.
+ * DRC_ERR_INVALID_ARGUMENT on a model without slots (drc_qpik_reach_path_batch
+ * runs it). */
+int drc_qpik_reach_path_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                        int64_t B, int waypoints, int max_steps, double dt,
+                                        double pos_tol, double rot_tol,
+                                        const double* q0, const double* qdot0,
+                                        const double* x_path, const double* xdot_path,
+                                        const double* obstacle_pose, int64_t obstacle_ld,
+                                        double* q_final, double* qdot_final,
+                                        int32_t* result, int32_t* waypoints_reached,
+                                        int32_t* steps_used,
+                                        int32_t* status_last, int32_t* iters_total,
+                                        double* err_final, double* dist_final,
+                                        double* dist_min, int32_t* steps_at, void* stream);
 
 /* The thresholds of drc_qpik_reach_batch (host only, no device is touched):
  * out[0] = tau_p, out[1] = tau_R.  DRC_ERR_INVALID_ARGUMENT: a tolerance that
