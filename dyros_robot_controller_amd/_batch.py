@@ -289,6 +289,82 @@ def qpik_reach_path_batch(model, params, q, qdot, x_path, xdot_path, max_steps, 
     return res
 
 
+REACH_SEEDS_FIELDS = REACH_FIELDS + ("inst_result", "inst_steps")
+SEEDS_RULES = {"first": _capi.SEEDS_FIRST, "fewest_steps": _capi.SEEDS_FEWEST_STEPS}
+
+
+class ReachSeedsResult:
+    """Device tensors of one ``drc_qpik_reach_seeds_batch`` call, one entry per
+    target: ``seed`` [T] (the winner's index), ``result`` [T], ``steps_used``
+    [T], ``q_sol``, ``qdot_sol`` [dof][T], and those of ``status_last`` [T],
+    ``iters_total`` [T], ``err_final`` [2][T], ``dist_final`` [1+dof][T] and the
+    per-instance diagnostics ``inst_result``, ``inst_steps`` [S][T] that were
+    asked for (None otherwise); ``thresholds``: (tau_p, tau_R) on the host."""
+    REACHED, BUDGET, QP_FAILED, CANCELLED = (_capi.REACH_REACHED, _capi.REACH_BUDGET, _capi.REACH_QP_FAILED,
+                                             _capi.REACH_CANCELLED)
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def qpik_reach_seeds_batch(model, params, q, qdot, x_target, xdot_target, max_steps, dt, pos_tol=1e-4, rot_tol=1e-3,
+                           seeds=None, rule="first", cancel=True, want=REACH_FIELDS, stream=None, obstacle_pose=None):
+    """Launch ``drc_qpik_reach_seeds_batch`` on device tensors: ``q`` / ``qdot``
+    [dof][S][T], or [dof][S*T] with ``seeds`` = S (seed s of target t at column
+    s*T + t); ``x_target`` [12][T], ``xdot_target`` [6][T]
+    (``drc_qpik_reach_seeds_obstacles_batch`` with ``obstacle_pose`` [n][12]
+    for one scene or [n][12][T] for one per target).  ``rule``: "first" or
+    "fewest_steps" (or the DRC_SEEDS_* value); ``cancel``: losers stop once
+    their group has its answer, which never changes an output.  ``want``: the
+    optional outputs to allocate and fill (REACH_SEEDS_FIELDS)."""
+    torch = _torch()
+    dev = q.device
+    nv = model.dof
+    T = x_target.shape[1] if x_target.dim() == 2 else -1
+    if q.dim() == 3:
+        S = q.shape[1]
+        if seeds is not None and int(seeds) != S:
+            raise ValueError("q is [dof][S=%d][T] but seeds = %s" % (S, seeds))
+    else:
+        if seeds is None:
+            raise ValueError("q laid out [dof][S*T] needs seeds = S")
+        S = int(seeds)
+    for name, t in (("q", q), ("qdot", qdot)):
+        if tuple(t.shape) not in ((nv, S, T), (nv, S * T)) or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 [%d][S=%d][T=%d] or [%d][S*T] tensor, got %s"
+                             % (name, nv, S, T, nv, tuple(t.shape)))
+    check_shapes(nv, T, x_target=x_target, xdot_target=xdot_target)
+    unknown = set(want) - set(REACH_SEEDS_FIELDS)
+    if unknown:
+        raise ValueError("unknown reach seeds outputs %s (know %s)" % (sorted(unknown), REACH_SEEDS_FIELDS))
+    f = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    i = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    res = ReachSeedsResult(
+        seed=i(T), result=i(T), steps_used=i(T), q_sol=f(nv, T), qdot_sol=f(nv, T),
+        status_last=i(T) if "status_last" in want else None,
+        iters_total=i(T) if "iters_total" in want else None,
+        err_final=f(2, T) if "err_final" in want else None,
+        dist_final=f(1 + nv, T) if "dist_final" in want else None,
+        inst_result=i(S, T) if "inst_result" in want else None,
+        inst_steps=i(S, T) if "inst_steps" in want else None,
+        thresholds=None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    head = (model.handle, C.byref(params), C.c_int64(T), C.c_int(S), C.c_int(SEEDS_RULES.get(rule, rule)),
+            C.c_int(1 if cancel else 0), C.c_int(int(max_steps)), C.c_double(dt), C.c_double(pos_tol),
+            C.c_double(rot_tol), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target))
+    tail = (_ptr(res.seed), _ptr(res.result), _ptr(res.steps_used), _ptr(res.q_sol), _ptr(res.qdot_sol),
+            _ptr(res.status_last), _ptr(res.iters_total), _ptr(res.err_final), _ptr(res.dist_final),
+            _ptr(res.inst_result), _ptr(res.inst_steps), C.c_void_p(stream))
+    if obstacle_pose is not None:
+        op, ld, _ = obstacle_poses(model, obstacle_pose, T, dev)
+        _capi.check(_capi.lib().drc_qpik_reach_seeds_obstacles_batch(*head, _ptr(op), C.c_int64(ld), *tail))
+    else:
+        _capi.check(_capi.lib().drc_qpik_reach_seeds_batch(*head, *tail))
+    res.thresholds = reach_thresholds(pos_tol, rot_tol)
+    return res
+
+
 def qpid_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
                qddot=None, tau=None, status=None, iters=None, stream=None):
     """Launch ``drc_qpid_batch``: returns (qddot [na][B],

@@ -49,13 +49,19 @@ EXPORTED_SYMBOLS = (
     "drc_qpik_rollout_obstacles_batch",
     "drc_qpik_reach_batch", "drc_qpik_reach_obstacles_batch", "drc_reach_thresholds",
     "drc_qpik_reach_path_batch", "drc_qpik_reach_path_obstacles_batch",
+    "drc_qpik_reach_seeds_batch", "drc_qpik_reach_seeds_obstacles_batch",
 )
 # the goal-reaching rollouts (absent from older A/B builds)
 REACH_SYMBOLS = ("drc_qpik_reach_batch", "drc_qpik_reach_obstacles_batch", "drc_reach_thresholds")
 # the reach paths (absent from older A/B builds)
 REACH_PATH_SYMBOLS = ("drc_qpik_reach_path_batch", "drc_qpik_reach_path_obstacles_batch")
+# reach from several seeds per target (absent from older A/B builds)
+REACH_SEEDS_SYMBOLS = ("drc_qpik_reach_seeds_batch", "drc_qpik_reach_seeds_obstacles_batch")
 # drc_qpik_reach_batch's result codes
 REACH_REACHED, REACH_BUDGET, REACH_QP_FAILED = 0, 1, 2
+# drc_qpik_reach_seeds_batch: inst_result of an instance stopped by its group's winner, and the rules
+REACH_CANCELLED = 3
+SEEDS_FIRST, SEEDS_FEWEST_STEPS = 0, 1
 # the obstacle-slot entries (absent from older A/B builds)
 OBSTACLE_SYMBOLS = ("drc_model_set_obstacles", "drc_qpik_obstacles_batch", "drc_qpik_stages_obstacles_batch",
                     "drc_qpik_rollout_obstacles_batch")
@@ -183,6 +189,14 @@ def _load():
                                                             C.c_double, C.c_double, C.c_double, vp, vp, vp, vp,
                                                             vp, C.c_int64,
                                                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "drc_qpik_reach_seeds_batch"):  # reach seeds: absent from older A/B builds
+        lib.drc_qpik_reach_seeds_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp,
+                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.drc_qpik_reach_seeds_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int, C.c_int,
+                                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                             vp, vp, vp, vp, vp, C.c_int64,
+                                                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.drc_debug_kernel_timing.argtypes = [vp, C.c_int]
     # diagnostics added in r05: bound only when present, so A/B runs can load
     # an older build (tests/test_capi_symbols.py checks the product exports them)
@@ -227,6 +241,7 @@ def _load():
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
                     "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info",
                     "drc_mesh_convex_hull", "drc_qpik_rollout_batch") + OBSTACLE_SYMBOLS + REACH_SYMBOLS + REACH_PATH_SYMBOLS \
+                + REACH_SEEDS_SYMBOLS \
                 and not hasattr(lib, name):
             continue  # diagnostics an older A/B build may lack
         if name not in ("drc_model_destroy", "drc_error_string", "drc_last_error", "drc_build_id"):

@@ -25,6 +25,7 @@
 #include "mesh.hpp"
 #include "reach.hpp"
 #include "reach_path.hpp"
+#include "reach_seeds.hpp"
 
 // ==========================================================================
 // host side: the C-ABI (include/drc_amd.h)
@@ -55,6 +56,8 @@ struct StreamCtx {
   int64_t dyn_list_cap = 0;
   void* roll = nullptr;  // rollouts without qdot_traj: one step's eta [na][B]
   int64_t roll_bytes = 0;
+  void* seeds = nullptr;  // drc_qpik_reach_seeds_batch: per-instance results, expanded targets, group words
+  int64_t seeds_bytes = 0;
 };
 constexpr size_t kMaxStreamCtx = 8;
 
@@ -153,6 +156,9 @@ static void free_ctx(StreamCtx* c) {
   if (c->roll) (void)hipFree(c->roll);
   c->roll = nullptr;
   c->roll_bytes = 0;
+  if (c->seeds) (void)hipFree(c->seeds);
+  c->seeds = nullptr;
+  c->seeds_bytes = 0;
   c->d_queue = nullptr;
   c->pool = nullptr;
   c->dyn_list = nullptr;
@@ -1126,14 +1132,13 @@ static bool finite_positive(double x) { return std::isfinite(x) && x > 0; }
 // is still active: it enqueues max_steps steps, then one more stage launch
 // and update that settle the instances still active.  Same device functions
 // either way: identical bits (tests/test_gpu_reach.py).
-static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int max_steps, double dt,
-                 double pos_tol, double rot_tol, const double* q0, const double* qdot0, const double* xt,
-                 const double* xdt, double* qf, double* vf, int32_t* result, int32_t* steps_used,
-                 int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final, void* stream,
-                 const Obst* ob = nullptr) {
-  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
-  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
-  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+// (reach_locked: the caller holds m->launch_mu -- reach() for one call,
+// reach_seeds() for its stepwise path)
+static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_t B, int max_steps, double dt,
+                        double pos_tol, double rot_tol, const double* q0, const double* qdot0, const double* xt,
+                        const double* xdt, double* qf, double* vf, int32_t* result, int32_t* steps_used,
+                        int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final,
+                        void* stream, const Obst* ob) {
   const bool slots = m->hm.dev.nobst > 0;
   if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsReachMsg);
   if (!slots && ob)
@@ -1230,6 +1235,18 @@ static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_
   }
   done_guard.ok = true;
   return DRC_OK;
+}
+
+static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int max_steps, double dt,
+                 double pos_tol, double rot_tol, const double* q0, const double* qdot0, const double* xt,
+                 const double* xdt, double* qf, double* vf, int32_t* result, int32_t* steps_used,
+                 int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final, void* stream,
+                 const Obst* ob = nullptr) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  return reach_locked(m, params, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt, qf, vf, result, steps_used,
+                      status_last, iters_total, err_final, dist_final, stream, ob);
 }
 
 static const char kSlotsReachPathMsg[] =
@@ -1369,6 +1386,149 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
     HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, s_pose, s_dist,
                                                                     eta, s_status, s_iters)));
   }
+  done_guard.ok = true;
+  return DRC_OK;
+}
+
+static const char kSlotsReachSeedsMsg[] =
+    "the model has obstacle slots: pass their poses through drc_qpik_reach_seeds_obstacles_batch";
+
+static_assert(kSeedsFirst == DRC_SEEDS_FIRST && kSeedsFewestSteps == DRC_SEEDS_FEWEST_STEPS &&
+                  kSeedsReached == DRC_REACH_REACHED && kSeedsCancelled == DRC_REACH_CANCELLED,
+              "reach_seeds.hpp restates include/drc_amd.h");
+
+// drc_qpik_reach_seeds_batch: S seeds for each of T targets, the S T instances
+// of reach() with instance (s, t) at column s T + t, and one answer per target
+// by the rule of reach_seeds.hpp (include/drc_amd.h), enqueued on the caller's
+// stream.  Per-instance finals and outcomes go to stream scratch, from which
+// the select kernel gathers the winners.  task_instance indexes targets and
+// poses with the state's stride, so the targets (and per-target poses) are
+// expanded to [..][S T] in scratch first.  reach_path()'s dispatch rule applied
+// to S T: the persistent kernel (reach_seeds_kernel.hip, with its ObstIn builds
+// for models with slots), where seeds of a group tell each other through the
+// group's word that the answer is there; everything else runs reach()'s
+// stepwise path on the expanded arrays, without cancellation.  Same device
+// functions either way: identical bits (tests/test_gpu_reach_seeds.py).
+static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, int64_t T, int S, int rule, int cancel,
+                       int max_steps, double dt, double pos_tol, double rot_tol, const double* q0,
+                       const double* qdot0, const double* xt, const double* xdt, int32_t* seed, int32_t* result,
+                       int32_t* steps_used, double* q_sol, double* qdot_sol, int32_t* status_last,
+                       int32_t* iters_total, double* err_final, double* dist_final, int32_t* inst_result,
+                       int32_t* inst_steps, void* stream, const Obst* ob = nullptr) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  const bool slots = m->hm.dev.nobst > 0;
+  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsReachSeedsMsg);
+  if (!slots && ob)
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   "the model has no obstacle slots (drc_model_set_obstacles declares them): "
+                   "drc_qpik_reach_seeds_batch runs it");
+  if (S < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "seeds must be at least 1");
+  if (T < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative number of targets");
+  if (rule != DRC_SEEDS_FIRST && rule != DRC_SEEDS_FEWEST_STEPS)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "rule is DRC_SEEDS_FIRST or DRC_SEEDS_FEWEST_STEPS");
+  if (ob && T > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < T)))
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the number of targets");
+  if (params->mode != DRC_MODE_QPIK_STEP)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_seeds_batch runs DRC_MODE_QPIK_STEP only");
+  if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
+  if ((int64_t(max_steps) + 1) * S >= (int64_t(1) << 31))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "(max_steps + 1) * seeds must be below 2^31");  // the 32-bit keys
+  if (T > 0x7ffffff0 / S)  // 32-bit work-queue counters
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "seeds * targets too large");
+  if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
+  if (!finite_positive(pos_tol) || !finite_positive(rot_tol))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  if (!seed || !result || !steps_used || !q_sol || !qdot_sol)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "seed, result, steps_used, q_sol and qdot_sol are required");
+  if (T > 0 && (!q0 || !qdot0 || !xt || !xdt))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_target and xdot_target are required");
+  KParams kt, kq;
+  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
+  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (T == 0) return DRC_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DevModel& dm = m->hm.dev;
+  const int nv = dm.nv, na = kq.na;
+  const int64_t B = T * S;
+  double tau[2];
+  reach_thresholds(pos_tol, rot_tol, tau);
+  const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
+  const bool persistent = m->fused && m->lane_stage == 0 && B <= reach_max && kQpGroup == 64 &&
+                          qp_compiled(kq.nx, kq.ng, kq.np) && !dm.has_mesh;
+  const bool ob_expand = ob && ob->ld != 0;
+  StreamCtx* cx = nullptr;
+  DoneGuard done_guard{cx, st};
+  // scratch: the expanded targets [12][B], [6][B], the instances' finals
+  // [nv][B] twice, err [2][B], dist [1+nv][B], the per-target poses expanded
+  // [nobst][12][B], (persistent) one step's eta [na][B]; then result, steps,
+  // status_last, iters_total [B], (persistent) one step's status and iters [B]
+  // and the groups' words [T]
+  const int64_t n_dbl = int64_t(12 + 6 + 2 * nv + 2 + 1 + nv + (ob_expand ? dm.nobst * 12 : 0) + (persistent ? na : 0)) * B;
+  {
+    std::lock_guard<std::mutex> g(m->mu);
+    if (int r = stream_ctx(m, st, &cx)) return r;
+    const int64_t bytes = n_dbl * 8 + 6 * B * 4 + T * 4;
+    if (cx->seeds_bytes < bytes) {
+      if (cx->seeds) HIP_TRY(hipFree(cx->seeds));  // synchronises: no launch still uses it
+      cx->seeds = nullptr;
+      cx->seeds_bytes = 0;
+      HIP_TRY(hipMalloc(&cx->seeds, bytes));
+      cx->seeds_bytes = bytes;
+    }
+  }
+  double* s_xt = static_cast<double*>(cx->seeds);
+  double* s_xdt = s_xt + 12 * B;
+  double* s_qf = s_xdt + 6 * B;
+  double* s_vf = s_qf + int64_t(nv) * B;
+  double* s_err = s_vf + int64_t(nv) * B;
+  double* s_dist = s_err + 2 * B;
+  double* s_pose = s_dist + int64_t(1 + nv) * B;
+  double* s_eta = s_pose + (ob_expand ? int64_t(dm.nobst) * 12 * B : 0);
+  int32_t* s_res = reinterpret_cast<int32_t*>(s_xt + n_dbl);
+  int32_t* s_steps = s_res + B;
+  int32_t* s_stl = s_steps + B;
+  int32_t* s_its = s_stl + B;
+  int32_t* s_status = s_its + B;
+  int32_t* s_iters = s_status + B;
+  uint32_t* s_word = reinterpret_cast<uint32_t*>(s_iters + B);
+  HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 12, T, S, xt, T, s_xt)));
+  HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 6, T, S, xdt, T, s_xdt)));
+  Obst obe{nullptr, 0};
+  if (ob) obe = *ob;
+  if (ob_expand) {
+    HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, dm.nobst * 12, T, S, ob->pose, ob->ld, s_pose)));
+    obe = Obst{s_pose, B};
+  }
+  // the diagnostics are the instances' own result / steps_used
+  const ReachSeedsArgs rs{{max_steps, dt, tau[0], tau[1], s_qf, s_vf, inst_result ? inst_result : s_res,
+                           inst_steps ? inst_steps : s_steps, status_last ? s_stl : nullptr,
+                           iters_total ? s_its : nullptr, s_err, dist_final ? s_dist : nullptr},
+                          T, S, rule, persistent && cancel ? 1 : 0, s_word};
+  const ReachArgs& re = rs.re;
+  if (persistent) {
+    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
+    const int64_t grid = B < cap ? B : cap;
+    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
+    IO io{B, 0, B, q0, qdot0, s_xt, s_xdt, nullptr, nullptr, s_eta, s_status, s_iters, nullptr, nullptr, nullptr,
+          nullptr, nullptr, nullptr, nullptr, 0};
+    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
+    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(s_word, 0xff, size_t(T) * 4, st));  // kSeedsNoKey
+    HIP_TRY(static_cast<hipError_t>(
+        slots ? launch_reach_seeds_obstacle_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rs, obe)
+              : launch_reach_seeds_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rs)));
+  } else {
+    if (int rc = reach_locked(m, params, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, s_xt, s_xdt, re.qf, re.vf,
+                              re.result, re.steps_used, re.status_last, re.iters_total, re.err_final, re.dist_final,
+                              stream, ob ? &obe : nullptr))
+      return rc;
+  }
+  const ReachSeedsOut out{seed, result, steps_used, q_sol, qdot_sol, status_last, iters_total, err_final, dist_final};
+  HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_select_kernel(st, nv, rs, out)));
   done_guard.ok = true;
   return DRC_OK;
 }
@@ -2144,6 +2304,31 @@ int drc_qpik_reach_path_obstacles_batch(const drc_model* m, const drc_qpik_param
   return drc_amd::reach_path(m, p, B, waypoints, max_steps, dt, pos_tol, rot_tol, q0, qdot0, x_path, xdot_path,
                              q_final, qdot_final, result, waypoints_reached, steps_used, status_last, iters_total,
                              err_final, dist_final, dist_min, steps_at, stream, &ob);
+}
+
+int drc_qpik_reach_seeds_batch(const drc_model* m, const drc_qpik_params* p, int64_t targets, int seeds, int rule,
+                               int cancel, int max_steps, double dt, double pos_tol, double rot_tol, const double* q0,
+                               const double* qdot0, const double* xt, const double* xdt, int32_t* seed,
+                               int32_t* result, int32_t* steps_used, double* q_sol, double* qdot_sol,
+                               int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final,
+                               int32_t* inst_result, int32_t* inst_steps, void* stream) {
+  return drc_amd::reach_seeds(m, p, targets, seeds, rule, cancel, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt,
+                              seed, result, steps_used, q_sol, qdot_sol, status_last, iters_total, err_final,
+                              dist_final, inst_result, inst_steps, stream);
+}
+
+int drc_qpik_reach_seeds_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t targets, int seeds,
+                                         int rule, int cancel, int max_steps, double dt, double pos_tol,
+                                         double rot_tol, const double* q0, const double* qdot0, const double* xt,
+                                         const double* xdt, const double* obstacle_pose, int64_t obstacle_ld,
+                                         int32_t* seed, int32_t* result, int32_t* steps_used, double* q_sol,
+                                         double* qdot_sol, int32_t* status_last, int32_t* iters_total,
+                                         double* err_final, double* dist_final, int32_t* inst_result,
+                                         int32_t* inst_steps, void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  return drc_amd::reach_seeds(m, p, targets, seeds, rule, cancel, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt,
+                              seed, result, steps_used, q_sol, qdot_sol, status_last, iters_total, err_final,
+                              dist_final, inst_result, inst_steps, stream, &ob);
 }
 
 int drc_reach_thresholds(double pos_tol, double rot_tol, double out[2]) {

@@ -1,0 +1,253 @@
+// Reach from several seeds per target (drc_qpik_reach_seeds_batch): S T
+// instances of drc_qpik_reach_batch's loop (reach_kernel.hip), instance (s, t)
+// at column s T + t, of which the select kernel returns one per target by the
+// rule of reach_seeds.hpp.  Reference: no counterpart.
+//
+// reach_seeds_kernel: the persistent form for the compiled QP shapes, shaped
+// like reach_kernel: one instance per wave from the work queue, the task record
+// in LDS, the state in the (scratch) q_final / qdot_final arrays, the update
+// scratch at the start of the plan.  New is one 32-bit word per group.  A wave
+// whose instance is REACHED publishes its key with an atomic min (lane 0); a
+// wave whose verdict failed loads the word (relaxed, agent scope, made uniform)
+// and leaves the instance on a uniform branch if seeds_cancelled says so.  No
+// spin, no fence and no payload behind the flag: the word is the whole message,
+// a stale value only delays a stop, and no output depends on it (reach_seeds.hpp
+// has the argument).  The per-XCD L2s are not coherent for plain accesses, so
+// the word is touched by these two atomics alone.  OB: empty, or one ObstIn --
+// the build for models with obstacle slots (reach_seeds_obstacle_kernel.hip).
+//
+// reach_seeds_expand_kernel: targets (and per-target poses) [..][T] to
+// [..][S T], since task_instance indexes them with the state's stride.
+// reach_seeds_select_kernel: one thread per group, the winner and the gather.
+// Both serve the stepwise path too (api.cpp), which runs the existing stepwise
+// reach on the expanded arrays: the same bits as the persistent kernel
+// (tests/test_gpu_reach_seeds.py).
+#include "task_stage.hpp"
+#include "qp_solver.hpp"
+#include "reach.hpp"
+#include "reach_seeds.hpp"
+#include "rollout_update.hpp"
+
+namespace drc_amd {
+
+#ifndef DRC_FUSED_WAVES
+#define DRC_FUSED_WAVES 2
+#endif
+template <class QD, class... OB>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
+reach_seeds_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io,
+                   const ReachSeedsArgs rs, const OB... ob) {
+  extern __shared__ __attribute__((aligned(16))) double S[];
+  PH_KSCOPE();
+  __shared__ KParams kpl;  // LDS copy of the QP parameters for the out-of-line ADMM blocks
+  {
+    static_assert(sizeof(KParams) % 8 == 0, "KParams copied as 8-byte words");
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(&kq);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&kpl);
+    for (int e = lane_id(); e < static_cast<int>(sizeof(KParams) / 8); e += 64) dst[e] = src[e];
+    wsync();
+  }
+  static_assert(QD::gs == 64, "the reach seeds kernel runs one instance per wave");
+  static_assert(sizeof...(OB) <= 1, "at most one set of obstacle poses");
+  const ReachArgs& re = rs.re;
+  const int l = lane_id();
+  const int64_t B = io.B, LD = io.ld;
+  const int nv = kt.nv, na = kq.na;
+  IO iol = io;  // the record lives in LDS, as in fused_kernel
+  iol.rec = S + fused_rec_offset(kt, kq);
+  iol.rec_stride = 0;
+  double* qs = S;  // (rollout_state_doubles: dead plan space)
+  double* es = qs + ((nv + 1) & ~1);
+  double(*Jm)[kMaxWheels] = reinterpret_cast<double(*)[kMaxWheels]>(es + ((na + 1) & ~1));
+  const InstSeq seq(B, kq.xcd_map, io.queue);
+  for (int64_t j = seq.first(); j < seq.n; j = seq.next(j)) {
+    const int64_t b = seq.at(j);
+    if (b >= B) continue;
+    const int64_t gb = io.b0 + b;
+    const int sd = static_cast<int>(gb / rs.T);  // the seed and its group
+    uint32_t* word = rs.word + (gb - sd * rs.T);
+    int k = 0, res = DRC_REACH_BUDGET, st_last = 0, it_total = 0;
+    for (;;) {
+      IO is = iol;
+      if (k > 0) {
+        is.q = re.qf;
+        is.qdot = re.vf;
+      }
+      task_instance<0, false, sizeof...(OB) != 0>(M0, kt, is, S, b, ob...);
+      wsync();
+      // the pose at q_k from the task plan against the target (reach_kernel)
+      double err[2];
+      {
+        const double* Te = S + kt.kTe;
+        double ps[12], tg[12];
+        for (int i = 0; i < 12; ++i) {
+          ps[i] = i < 9 ? Te[(i % 3) * 3 + i / 3] : Te[i];
+          tg[i] = io.xt[i * LD + gb];
+        }
+        reach_error(ps, tg, err);
+      }
+      if (l < 2) re.err_final[l * LD + gb] = l ? err[1] : err[0];  // (the select kernel needs it)
+      if (re.dist_final && l <= nv) re.dist_final[l * LD + gb] = iol.rec[kt.rDist + l];
+      const int within = __builtin_amdgcn_readfirstlane(reach_within(err, re.tau_p, re.tau_r) ? 1 : 0);
+      if (within) {
+        if (rs.cancel && l == 0)
+          __hip_atomic_fetch_min(word, seeds_key(rs.rule, rs.S, k, sd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        res = DRC_REACH_REACHED;
+        break;
+      }
+      if (k == re.max_steps) {
+        res = DRC_REACH_BUDGET;
+        break;
+      }
+      if (rs.cancel) {  // has a seed of this group made this one a loser?
+        const uint32_t w = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(
+            static_cast<int>(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))));
+        if (seeds_cancelled(rs.rule, rs.S, w, k, sd)) {
+          res = DRC_REACH_CANCELLED;
+          break;
+        }
+      }
+      wsync();
+      qp_instance<QD>(M0, kq, kpl, is, S, b);
+      // ---------------- this step's status, wave-uniform ----------------------
+      state_visible();
+      st_last = __builtin_amdgcn_readfirstlane(
+          __hip_atomic_load(is.status + gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      it_total += __builtin_amdgcn_readfirstlane(
+          __hip_atomic_load(is.iters + gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      if (st_last != DRC_STATUS_SOLVED) {
+        res = DRC_REACH_QP_FAILED;
+        break;
+      }
+      // ---------------- state update (as rollout_kernel) ----------------------
+      const double qk = l < nv ? is.q[l * LD + gb] : 0.0;
+      if (l < nv) qs[l] = qk;
+      if (l < na) es[l] = is.out[l * LD + gb];
+      wsync();
+      const DevModel* M = opaque_model(M0);
+      double cy = 1, sy = 0;
+      if (M->kind == 1) {
+        if (l == 0) mobile_fk(M, qs + M->mobi_start, Jm);
+        const double yaw = qs[M->virtual_start + 2];
+        cy = cos(yaw);
+        sy = sin(yaw);
+        wsync();
+      }
+      if (l < nv) {
+        const double v = rollout_velocity(M, l, cy, sy, Jm, [&](int a) { return es[a]; });
+        const double qn = rollout_advance(qk, re.dt, v);
+        re.vf[l * LD + gb] = v;
+        re.qf[l * LD + gb] = qn;
+      }
+      state_visible();
+      wsync();
+      ++k;
+    }
+    // stopped at (q_k, v_k): from step 1 on the finals hold it
+    if (k == 0 && l < nv) {
+      const double q0 = io.q[l * LD + gb], v0 = io.qdot[l * LD + gb];
+      re.qf[l * LD + gb] = q0;
+      re.vf[l * LD + gb] = v0;
+    }
+    if (l == 0) {
+      re.result[gb] = res;
+      re.steps_used[gb] = k;
+      if (re.status_last) re.status_last[gb] = st_last;
+      if (re.iters_total) re.iters_total[gb] = it_total;
+    }
+    wsync();
+  }
+}
+
+template <class... OB>
+static int launch_shapes(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
+                         const IO& io, const ReachSeedsArgs& rs, const OB&... ob) {
+  // the update scratch lies in the plan: fused_lds_doubles for every compiled shape
+  const int plan = fused_lds_doubles(kt, kq), state = rollout_state_doubles(kt, kq);
+  const size_t lds = static_cast<size_t>(plan > state ? plan : state) * sizeof(double);
+  const dim3 g(grid), blk(64);
+  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
+    hipLaunchKernelGGL((reach_seeds_kernel<Dims<23, 16, 7, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io,
+                       rs, ob...);
+  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
+    hipLaunchKernelGGL((reach_seeds_kernel<Dims<20, 14, 6, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io,
+                       rs, ob...);
+  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
+    hipLaunchKernelGGL((reach_seeds_kernel<Dims<9, 16, 9, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io, rs,
+                       ob...);
+  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
+    hipLaunchKernelGGL((reach_seeds_kernel<Dims<11, 16, 11, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io,
+                       rs, ob...);
+  else
+    return hipErrorInvalidValue;  // not a compiled shape: the stepwise path runs it
+  return hipGetLastError();
+}
+
+// The builds for models with obstacle slots are a translation unit of their
+// own (reach_seeds_obstacle_kernel.hip includes this file with
+// DRC_REACH_SEEDS_OBST defined), as reach_path_obstacle_kernel.hip's.
+#if defined(DRC_REACH_SEEDS_OBST)
+int launch_reach_seeds_obstacle_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt,
+                                       const KParams& kq, const IO& io, const ReachSeedsArgs& rs, const ObstIn& ob) {
+  return launch_shapes(grid, st, m, kt, kq, io, rs, ob);
+}
+#else
+int launch_reach_seeds_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
+                              const IO& io, const ReachSeedsArgs& rs) {
+  return launch_shapes(grid, st, m, kt, kq, io, rs);
+}
+
+// dst [rows][S T] from src [rows][ld]: one thread per element of dst
+__global__ void __launch_bounds__(256)
+reach_seeds_expand_kernel(int64_t n, int64_t T, int64_t B, const double* __restrict__ src, int64_t ld,
+                          double* __restrict__ dst) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = i / B, c = i - r * B;
+  dst[i] = src[r * ld + c % T];
+}
+
+int launch_reach_seeds_expand_kernel(hipStream_t st, int rows, int64_t T, int S, const double* src, int64_t ld,
+                                     double* dst) {
+  const int64_t B = T * S, n = B * rows;
+  hipLaunchKernelGGL(reach_seeds_expand_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, n, T, B,
+                     src, ld, dst);
+  return hipGetLastError();
+}
+
+// One thread per group.  The instances' outcomes are those of this call -- with
+// cancellation the losers' may be cut short, which leaves the winner what it is
+// (reach_seeds.hpp)
+__global__ void __launch_bounds__(256)
+reach_seeds_select_kernel(int nv, const ReachSeedsArgs rs, const ReachSeedsOut out) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t T = rs.T, B = T * rs.S;
+  if (t >= T) return;
+  const ReachArgs& re = rs.re;
+  const int s = seeds_winner(rs.rule, rs.S, re.result + t, re.steps_used + t, re.err_final + t, re.err_final + B + t, T);
+  const int64_t b = s * T + t;
+  out.seed[t] = s;
+  out.result[t] = re.result[b];
+  out.steps_used[t] = re.steps_used[b];
+  for (int r = 0; r < nv; ++r) {
+    out.q_sol[r * T + t] = re.qf[r * B + b];
+    out.qdot_sol[r * T + t] = re.vf[r * B + b];
+  }
+  if (out.status_last) out.status_last[t] = re.status_last[b];
+  if (out.iters_total) out.iters_total[t] = re.iters_total[b];
+  if (out.err_final) {
+    out.err_final[t] = re.err_final[b];
+    out.err_final[T + t] = re.err_final[B + b];
+  }
+  if (out.dist_final)
+    for (int r = 0; r <= nv; ++r) out.dist_final[r * T + t] = re.dist_final[r * B + b];
+}
+
+int launch_reach_seeds_select_kernel(hipStream_t st, int nv, const ReachSeedsArgs& rs, const ReachSeedsOut& out) {
+  hipLaunchKernelGGL(reach_seeds_select_kernel, dim3(static_cast<unsigned>((rs.T + 255) / 256)), dim3(256), 0, st, nv,
+                     rs, out);
+  return hipGetLastError();
+}
+#endif
+
+}  // namespace drc_amd

@@ -378,6 +378,22 @@ def _reach_path(ctrl, kv, q, qdot, x_path, link_name, max_steps, dt, pos_tol, ro
                                         obstacle_pose=obstacle_pose)
 
 
+def _reach_seeds(ctrl, kv, q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol, xdot_target, w_reg,
+                 obstacle_pose, want, seeds, rule, cancel):
+    """QPIK_reach_seeds_batch of both controllers (``kv``: the task Kv of its QPIKStep)."""
+    p = ctrl._pb.params(link_name, _capi.MODE_QPIK_STEP, ctrl.Kp_task_, kv)
+    if w_reg is not None:
+        p.w_reg = float(w_reg)
+    dev = ctrl.robot_data_.device
+    x_target = _batch.as_device(x_target, dev)
+    if xdot_target is None:
+        xdot_target = np.zeros((6, x_target.shape[1]))
+    return _batch.qpik_reach_seeds_batch(ctrl.robot_data_.model, p, _batch.as_device(q, dev),
+                                         _batch.as_device(qdot, dev), x_target, _batch.as_device(xdot_target, dev),
+                                         max_steps, ctrl.dt_ if dt is None else dt, pos_tol, rot_tol, seeds=seeds,
+                                         rule=rule, cancel=cancel, want=want, obstacle_pose=obstacle_pose)
+
+
 class RobotController:
     """Manipulator::RobotController QPIK entries
     (src/manipulator/robot_controller.cpp:7-19,277-317).
@@ -527,6 +543,19 @@ class RobotController:
         ``xdot_path`` None: zeros (DESIGN.md "Reach paths")."""
         return _reach_path(self, self.Kv_task_, q, qdot, x_path, link_name, max_steps, dt, pos_tol, rot_tol,
                            xdot_path, w_reg, obstacle_pose, want)
+
+    def QPIK_reach_seeds_batch(self, q, qdot, x_target, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
+                               xdot_target=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_FIELDS,
+                               seeds=None, rule="first", cancel=True):
+        """QPIK_reach_batch from S start states ``q`` [dof][S][T] (or [dof][S*T]
+        with ``seeds`` = S) for each of the T poses ``x_target`` [12][T], in one
+        device call, and one answer per pose: the first seed that reaches
+        (``rule`` "first": order them by preference) or the one that needs the
+        fewest steps ("fewest_steps"); if none reaches, the closest.  With
+        ``cancel`` the losers stop early, which never changes a result: a
+        _batch.ReachSeedsResult (DESIGN.md "Reach seeds")."""
+        return _reach_seeds(self, self.Kv_task_, q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol,
+                            xdot_target, w_reg, obstacle_pose, want, seeds, rule, cancel)
 
     # -- single-instance entries (reference signatures; B = 1 launches) -------
     def _one(self, out_status):

@@ -33,7 +33,8 @@ import numpy as np
 
 from . import _batch, _capi
 from ._capi import C
-from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, _reach, _reach_path, _rollout, pose_to12
+from .manipulator import QPIKParamsBuilder, _ModelHandle, _default_device, _reach, _reach_path, _reach_seeds, _rollout, \
+    pose_to12
 
 
 class DriveType(IntEnum):
@@ -516,6 +517,19 @@ class RobotController:
         ``xdot_path`` None: zeros (DESIGN.md "Reach paths")."""
         return _reach_path(self, np.zeros(6), q, qdot, x_path, link_name, max_steps, dt, pos_tol, rot_tol, xdot_path,
                            w_reg, obstacle_pose, want)
+
+    def QPIK_reach_seeds_batch(self, q, qdot, x_target, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
+                               xdot_target=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_FIELDS,
+                               seeds=None, rule="first", cancel=True):
+        """QPIK_reach_batch from S start states ``q`` [dof][S][T] (or [dof][S*T]
+        with ``seeds`` = S) for each of the T poses ``x_target`` [12][T], in one
+        device call, and one answer per pose: the first seed that reaches
+        (``rule`` "first") or the one that needs the fewest steps
+        ("fewest_steps"); if none reaches, the closest.  With ``cancel`` the
+        losers stop early, which never changes a result: a
+        _batch.ReachSeedsResult (DESIGN.md "Reach seeds")."""
+        return _reach_seeds(self, np.zeros(6), q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol,
+                            xdot_target, w_reg, obstacle_pose, want, seeds, rule, cancel)
 
     def split_actuated(self, eta):
         """eta [A] -> (qdot_mobile [W], qdot_mani [n]) by ActuatorIndex."""

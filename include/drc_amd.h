@@ -513,6 +513,94 @@ int drc_qpik_reach_path_obstacles_batch(const drc_model* model, const drc_qpik_p
                                         double* err_final, double* dist_final,
                                         double* dist_min, int32_t* steps_at, void* stream);
 
+/* ---- reach from several seeds per target -------------------------------------- */
+enum {
+    DRC_REACH_CANCELLED = 3      /* drc_qpik_reach_seeds_batch, inst_result only: stopped
+                                    because another seed of its group had won          */
+};
+enum {
+    DRC_SEEDS_FIRST = 0,         /* the lowest seed index that reached                 */
+    DRC_SEEDS_FEWEST_STEPS = 1   /* the least steps_used, ties to the lowest index     */
+};
+
+/* Reach from several seeds per target: for each of T = `targets` poses, S =
+ * `seeds` start states are tried and one answer is returned.
+ * There are T groups, S seeds per group and S T instances; instance (s, t) is
+ * column s T + t of q0, qdot0 [dof][S T].  Targets are per group: x_target
+ * [12][T], xdot_target [6][T].  Mode DRC_MODE_QPIK_STEP only.
+ * Every instance runs the loop of drc_qpik_reach_batch unchanged.  Its
+ * uncancelled outcome is what that entry returns for it: result, steps_used,
+ * the finals, status_last, iters_total, err_final, dist_final.
+ * The group's winner is defined on uncancelled outcomes alone.
+ * If some seed is DRC_REACH_REACHED:
+ *   rule = DRC_SEEDS_FIRST: the lowest seed index that reached (order the seeds
+ *       by preference: warm start first, then perturbations, then random);
+ *   rule = DRC_SEEDS_FEWEST_STEPS: the seed with the least steps_used, ties to
+ *       the lowest seed index.
+ * If no seed is DRC_REACH_REACHED: the seed with the least e_p at its final
+ * state, ties to the least e_R, then to the lowest seed index; a NaN counts as
+ * +inf.
+ * Outputs per group, [..][T] field-major, each the winner's uncancelled value:
+ *   seed [T], result [T], steps_used [T], q_sol, qdot_sol [dof][T]: required;
+ *   status_last [T], iters_total [T], err_final [2][T], dist_final [1+dof][T]:
+ *       may be NULL.
+ * Together they are, bit for bit, what drc_qpik_reach_batch on the S T
+ * instances with the targets replicated gives, gathered by the rule above.
+ * Cancellation (cancel = 1): an instance that is REACHED at step k publishes a
+ * key to its group's word with an atomic min: s under FIRST, k S + s under
+ * FEWEST_STEPS.  An instance whose verdict at step k is "not within" (and that
+ * has steps left) reads the word and stops as DRC_REACH_CANCELLED if word < s
+ * (FIRST) or floor(word / S) <= k (FEWEST_STEPS).  The true winner can never
+ * satisfy its own stop condition, so every per-group output is independent of
+ * timing; a stale read only delays a stop, and nothing depends on when, or
+ * whether, a published key becomes visible.  cancel = 0 runs every instance to
+ * its own stop.  Cancellation only changes how much work the losers do.
+ * Diagnostics inst_result, inst_steps [S T] (may be NULL): what each instance
+ * did in this call.  cancel = 0: exactly drc_qpik_reach_batch's result /
+ * steps_used.  cancel = 1: the winners' entries are their uncancelled ones, the
+ * others' depend on timing (inst_steps never exceeds the uncancelled count).
+ * The dispatch is drc_qpik_reach_path_batch's, applied to S T: compiled QP
+ * shape, no collision meshes, drc_set_fusion, up to DRC_REACH_MAX instances run
+ * one persistent kernel, models with obstacle slots too
+ * (drc_qpik_reach_seeds_obstacles_batch).  Everything else runs the stepwise
+ * path of drc_qpik_reach_batch on the S T instances; there is no cancellation
+ * there (a lockstep path saves nothing by it).  The per-group outputs are
+ * bit-identical either way.  Per-instance results, the replicated targets and
+ * the groups' words live in stream scratch.
+ * DRC_ERR_INVALID_ARGUMENT: seeds < 1, targets < 0, (max_steps + 1) seeds not
+ * below 2^31, seeds targets above the work-queue limit (0x7ffffff0), an unknown
+ * rule, any of drc_qpik_reach_batch's own conditions, a model with obstacle
+ * slots (drc_qpik_reach_seeds_obstacles_batch takes their poses).  targets = 0
+ * returns DRC_OK.  Asynchronous on `stream`, no host synchronisation.
+ * (Reference: no counterpart.) */
+int drc_qpik_reach_seeds_batch(const drc_model* model, const drc_qpik_params* params,
+                               int64_t targets, int seeds, int rule, int cancel,
+                               int max_steps, double dt, double pos_tol, double rot_tol,
+                               const double* q0, const double* qdot0,
+                               const double* x_target, const double* xdot_target,
+                               int32_t* seed, int32_t* result, int32_t* steps_used,
+                               double* q_sol, double* qdot_sol,
+                               int32_t* status_last, int32_t* iters_total,
+                               double* err_final, double* dist_final,
+                               int32_t* inst_result, int32_t* inst_steps, void* stream);
+
+/* drc_qpik_reach_seeds_batch on a model with obstacle slots: obstacle_pose
+ * [n][12][obstacle_ld]; obstacle_ld = 0 is one scene for the whole call,
+ * obstacle_ld >= targets one scene per target (column t; every seed of the
+ * group meets it).  DRC_ERR_INVALID_ARGUMENT on a model without slots
+ * (drc_qpik_reach_seeds_batch runs it). */
+int drc_qpik_reach_seeds_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                         int64_t targets, int seeds, int rule, int cancel,
+                                         int max_steps, double dt, double pos_tol, double rot_tol,
+                                         const double* q0, const double* qdot0,
+                                         const double* x_target, const double* xdot_target,
+                                         const double* obstacle_pose, int64_t obstacle_ld,
+                                         int32_t* seed, int32_t* result, int32_t* steps_used,
+                                         double* q_sol, double* qdot_sol,
+                                         int32_t* status_last, int32_t* iters_total,
+                                         double* err_final, double* dist_final,
+                                         int32_t* inst_result, int32_t* inst_steps, void* stream);
+
 /* The thresholds of drc_qpik_reach_batch (host only, no device is touched):
  * out[0] = tau_p, out[1] = tau_R.  DRC_ERR_INVALID_ARGUMENT: a tolerance that
  * is not finite and positive, out NULL. */
