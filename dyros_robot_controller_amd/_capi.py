@@ -39,7 +39,8 @@ EXPORTED_SYMBOLS = (
     "drc_mobile_fk_jacobian", "drc_mobile_ik_jacobian",
     "drc_default_qpik_params", "drc_qpik_batch", "drc_qpik_stages_batch", "drc_debug_kernel_timing", "drc_debug_lds_plan",
     "drc_debug_host_timeline", "drc_debug_waves", "drc_debug_qpik_stamps",
-    "drc_debug_kernel_times", "drc_debug_instance_order", "drc_set_concurrency", "drc_set_fusion", "drc_model_release_stream", "drc_debug_lane_stage", "drc_debug_eqp_small_cap", "drc_qpik_host", "drc_qpik_stages_host",
+    "drc_debug_kernel_times", "drc_debug_instance_order", "drc_set_concurrency", "drc_set_fusion", "drc_model_release_stream", "drc_debug_lane_stage", "drc_debug_eqp_small_cap",
+    "drc_debug_qp_dense", "drc_debug_qp_dense_launches", "drc_qpik_host", "drc_qpik_stages_host",
     "drc_dynamics_batch", "drc_dynamics_host", "drc_joint_torque_step_batch", "drc_joint_torque_step_host",
     "drc_default_qpid_params", "drc_qpid_batch", "drc_qpid_stages_batch", "drc_qpid_host",
     "drc_qpid_stages_host", "drc_clik_batch", "drc_osf_batch", "drc_closed_form_host",
@@ -57,6 +58,8 @@ REACH_SYMBOLS = ("drc_qpik_reach_batch", "drc_qpik_reach_obstacles_batch", "drc_
 REACH_PATH_SYMBOLS = ("drc_qpik_reach_path_batch", "drc_qpik_reach_path_obstacles_batch")
 # reach from several seeds per target (absent from older A/B builds)
 REACH_SEEDS_SYMBOLS = ("drc_qpik_reach_seeds_batch", "drc_qpik_reach_seeds_obstacles_batch")
+# the dense reference build of the manipulator QP kernels (absent from older A/B builds)
+QP_DENSE_SYMBOLS = ("drc_debug_qp_dense", "drc_debug_qp_dense_launches")
 # drc_qpik_reach_batch's result codes
 REACH_REACHED, REACH_BUDGET, REACH_QP_FAILED = 0, 1, 2
 # drc_qpik_reach_seeds_batch: inst_result of an instance stopped by its group's winner, and the rules
@@ -213,6 +216,9 @@ def _load():
     lib.drc_debug_lane_stage.argtypes = [vp, C.c_int]
     if hasattr(lib, "drc_debug_eqp_small_cap"):  # absent from older A/B builds
         lib.drc_debug_eqp_small_cap.argtypes = [vp, C.c_int]
+    if hasattr(lib, "drc_debug_qp_dense"):  # absent from older A/B builds
+        lib.drc_debug_qp_dense.argtypes = [vp, C.c_int]
+        lib.drc_debug_qp_dense_launches.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.drc_set_concurrency.argtypes = [vp, C.c_int]
     lib.drc_model_release_stream.argtypes = [vp, vp]
     lib.drc_set_fusion.argtypes = [vp, C.c_int]
@@ -241,7 +247,7 @@ def _load():
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
                     "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info",
                     "drc_mesh_convex_hull", "drc_qpik_rollout_batch") + OBSTACLE_SYMBOLS + REACH_SYMBOLS + REACH_PATH_SYMBOLS \
-                + REACH_SEEDS_SYMBOLS \
+                + REACH_SEEDS_SYMBOLS + QP_DENSE_SYMBOLS \
                 and not hasattr(lib, name):
             continue  # diagnostics an older A/B build may lack
         if name not in ("drc_model_destroy", "drc_error_string", "drc_last_error", "drc_build_id"):

@@ -92,6 +92,8 @@ struct drc_model_impl {
   int timing = 0;  // drc_debug_kernel_timing: HIP events around each launch
   int lane_stage = 0;  // drc_debug_lane_stage: 0 off, 1 lane stage + side-stream hard path, 2 + serial hard path, 3 auto
   int eqp_small_cap = -1;  // drc_debug_eqp_small_cap: -1 the compiled tiers, 0 general EQP only, k small EQP for N <= k
+  bool qp_dense = false;   // drc_debug_qp_dense: the manipulator shapes' QP kernel with dense G loops
+  int64_t qp_dense_launches = 0;
   // timed calls: {caller-stream start, caller-stream end, per chunk: task start, task end, qp end}
   // timed calls: {call start, call end, task start, task end, QP end of the
   // sub-batch on the caller's stream} and the call's sub-batch count
@@ -905,6 +907,12 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
       io.queue = qc + 8;
       // compile-time QP shapes of the bundled robots; anything else runs the
       // runtime-sized instantiation (one LDS plan per lane group)
+      if (m->qp_dense && dm.kind == 0 && qp_compiled(kq_c.nx, kq_c.ng, kq_c.np)) {  // the dense reference build
+        HIP_TRY(static_cast<hipError_t>(
+            launch_qp_dense_kernel(static_cast<unsigned>(gq), lds_q, cs, m->d_model, kq_c, io)));
+        ++m->qp_dense_launches;
+        return DRC_OK;
+      }
       HIP_TRY(static_cast<hipError_t>(launch_qp_kernel(static_cast<unsigned>(gq), lds_q, cs, m->d_model, kq_c, io)));
       return DRC_OK;
     };
@@ -1860,18 +1868,37 @@ int drc_debug_instance_order(drc_model* m, const int32_t* order, int64_t n) {
 }
 
 #ifdef DRC_PHASE_TIMING
-// diagnostic build only: accumulated per-phase s_memtime cycles (32 slots)
-int drc_debug_phase_cycles(unsigned long long* out, int reset) {
-  for (int i = 0; i < 64; ++i) out[i] = 0;
-  if (drc_amd::phase_cycles_task(out, reset) || drc_amd::phase_cycles_qp(out, reset) ||
-      drc_amd::phase_cycles_qpid(out, reset) || drc_amd::phase_cycles_fused(out, reset))
+// diagnostic build only: accumulated per-phase s_memtime cycles, slots 0 .. 63
+static int phase_cycles_all(unsigned long long* all, int reset) {
+  for (int i = 0; i < 96; ++i) all[i] = 0;
+  if (drc_amd::phase_cycles_task(all, reset) || drc_amd::phase_cycles_qp(all, reset) ||
+      drc_amd::phase_cycles_qp_dense(all, reset) ||
+      drc_amd::phase_cycles_qpid(all, reset) || drc_amd::phase_cycles_fused(all, reset))
     return DRC_ERR_HIP;
+  return DRC_OK;
+}
+int drc_debug_phase_cycles(unsigned long long* out, int reset) {
+  unsigned long long all[96];
+  if (int rc = phase_cycles_all(all, reset)) return rc;
+  for (int i = 0; i < 64; ++i) out[i] = all[i];
+  return DRC_OK;
+}
+// ... and slots 64 .. 95 into out[32]: the QP kernel's front end split finer
+// (Ruiz scaling: checks, V load, passes, write-back; schur_setup: weights, S
+// entries, Gauss-Jordan, G_c S^-1; qp_assemble after the record load: J~ and
+// P, G / q / bounds).  Never resets: drc_debug_phase_cycles does.
+int drc_debug_phase_cycles_fine(unsigned long long* out) {
+  unsigned long long all[96];
+  if (int rc = phase_cycles_all(all, 0)) return rc;
+  for (int i = 0; i < 32; ++i) out[i] = all[64 + i];
   return DRC_OK;
 }
 // diagnostic build only: polish EQPs by reduced-KKT size N (bins 0 .. 14, then N >= 15)
 int drc_debug_eqp_hist(unsigned long long* out, int reset) {
   for (int i = 0; i < 16; ++i) out[i] = 0;
-  if (drc_amd::phase_cycles_qp_hist(out, reset) || drc_amd::phase_cycles_fused_hist(out, reset)) return DRC_ERR_HIP;
+  if (drc_amd::phase_cycles_qp_hist(out, reset) || drc_amd::phase_cycles_qp_dense_hist(out, reset) ||
+      drc_amd::phase_cycles_fused_hist(out, reset))
+    return DRC_ERR_HIP;
   return DRC_OK;
 }
 #endif
@@ -1880,6 +1907,20 @@ int drc_debug_eqp_small_cap(drc_model* m, int cap) {
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
   std::lock_guard<std::mutex> g(m->launch_mu);
   m->eqp_small_cap = cap < 0 ? -1 : cap;
+  return DRC_OK;
+}
+
+int drc_debug_qp_dense(drc_model* m, int on) {
+  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  std::lock_guard<std::mutex> g(m->launch_mu);
+  m->qp_dense = on != 0;
+  return DRC_OK;
+}
+
+int drc_debug_qp_dense_launches(drc_model* m, int64_t* count) {
+  if (!m || !count) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null argument");
+  std::lock_guard<std::mutex> g(m->launch_mu);
+  *count = m->qp_dense_launches;
   return DRC_OK;
 }
 

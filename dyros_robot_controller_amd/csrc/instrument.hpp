@@ -1,18 +1,19 @@
 // Diagnostic phase instrumentation (tools/phase_timing.py, the
 // libdrc_amd_timing.so build of tools/build_variants.sh).  With
 // -DDRC_PHASE_TIMING the kernels accumulate s_memtime cycle stamps per phase
-// into a 64-slot device array of their translation unit (drc_debug_phase_cycles
-// sums the units); without it every macro below expands to nothing, so the
+// into a 96-slot device array of their translation unit (drc_debug_phase_cycles
+// sums the units' slots 0 .. 63, drc_debug_phase_cycles_fine their slots 64 .. 95:
+// the finer split of the QP kernel's front end); without it every macro below expands to nothing, so the
 // product kernels carry no instrumentation.
 #pragma once
 
 #ifdef DRC_PHASE_TIMING
 namespace drc_amd {
-static __device__ unsigned long long g_phase_cycles[64];
+static __device__ unsigned long long g_phase_cycles[96];
 // per-wave accumulators in LDS (lane 0 adds; the kernel adds them to the
 // device array once, at its end): a global atomic per phase and call from
 // every wave queued at the L2 and inflated the very cycles being measured
-static __shared__ unsigned long long g_ph_lds[64];
+static __shared__ unsigned long long g_ph_lds[96];
 // histogram of the polish's reduced-KKT sizes (PH_HIST: bins 0 .. 15, the last
 // one open-ended), kept the same way; drc_debug_eqp_hist sums the units
 static __device__ unsigned long long g_phase_hist[16];
@@ -21,6 +22,7 @@ static __shared__ unsigned long long g_ph_hist_lds[16];
 #define PH_KINIT()                         \
   do {                                     \
     g_ph_lds[__lane_id()] = 0ull;          \
+    if (__lane_id() < 32) g_ph_lds[64 + __lane_id()] = 0ull; \
     if (__lane_id() < 16) g_ph_hist_lds[__lane_id()] = 0ull; \
     __builtin_amdgcn_wave_barrier();       \
   } while (0)
@@ -29,6 +31,8 @@ static __shared__ unsigned long long g_ph_hist_lds[16];
     __builtin_amdgcn_wave_barrier();                                  \
     const unsigned long long v_ = g_ph_lds[__lane_id()];              \
     if (v_) atomicAdd(&g_phase_cycles[__lane_id()], v_);              \
+    const unsigned long long w_ = g_ph_lds[64 + (__lane_id() & 31)];  \
+    if (w_ && __lane_id() < 32) atomicAdd(&g_phase_cycles[64 + __lane_id()], w_); \
     const unsigned long long h_ = g_ph_hist_lds[__lane_id() & 15];    \
     if (h_ && __lane_id() < 16) atomicAdd(&g_phase_hist[__lane_id()], h_); \
   } while (0)
@@ -92,14 +96,14 @@ struct PhKernelScope {
     ck_t = t_;                                                          \
   } while (0)
 #define CK_N(slot) PH_ADD(slot, 1)
-// host: add this unit's slots to out[64] (and zero them when reset)
+// host: add this unit's slots to out[96] (and zero them when reset)
 #define DRC_PHASE_EXPORT(fn)                                                                       \
   int fn(unsigned long long* out, int reset) {                                                     \
-    unsigned long long v[64];                                                                      \
+    unsigned long long v[96];                                                                      \
     if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_phase_cycles), sizeof(v)) != hipSuccess) return 1;     \
-    for (int i = 0; i < 64; ++i) out[i] += v[i];                                                   \
+    for (int i = 0; i < 96; ++i) out[i] += v[i];                                                   \
     if (reset) {                                                                                   \
-      for (int i = 0; i < 64; ++i) v[i] = 0;                                                       \
+      for (int i = 0; i < 96; ++i) v[i] = 0;                                                       \
       if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase_cycles), v, sizeof(v)) != hipSuccess) return 1;     \
     }                                                                                              \
     return 0;                                                                                      \

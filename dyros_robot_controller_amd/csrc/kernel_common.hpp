@@ -255,12 +255,15 @@ __device__ void so3_exp(V3 w, double* R) {
 // row, so that block is diagonal): S = K_cc - K_ca D^-1 K_ac is np x np.
 // gs: lanes per instance (64, or 32 = two instances per wave; the QPIK
 // shapes whose n + NG Schur lanes and polish rows fit in 32).
-template <int NX, int NG, int NP, bool REG = (NX > 0), bool SCHUR = false, int GS = 64>
+// dense: the manipulator shapes' reference build, every G loop over the whole
+// matrix (qp_dense_kernel.hip; kQpikSparse in qp_solver.hpp).
+template <int NX, int NG, int NP, bool REG = (NX > 0), bool SCHUR = false, int GS = 64, bool DENSE = false>
 struct Dims {
   static constexpr int nx = NX, ng = NG, np = NP;
   static constexpr bool reg = REG;
   static constexpr bool schur = SCHUR;
   static constexpr int gs = GS;
+  static constexpr bool dense = DENSE;
 };
 #define DNX (QD::nx ? QD::nx : kp.nx)
 #define DNG (QD::ng ? QD::ng : kp.ng)

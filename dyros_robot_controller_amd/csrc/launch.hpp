@@ -25,6 +25,10 @@ int launch_lane_task_kernel(int nv, unsigned grid, hipStream_t st, const DevMode
 bool qp_compiled(int nx, int ng, int np);
 // qp_kernel for kp's shape; lds = one lane group's plan
 int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io);
+// the two manipulator shapes' dense reference build (qp_dense_kernel.hip;
+// hipErrorInvalidValue for any other shape)
+int launch_qp_dense_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                           const IO& io);
 int launch_qpid_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io);
 // fused task + QP kernel (compiled QPIK shapes; hipErrorInvalidValue otherwise);
 // lds = both plans' maximum plus the record slot
@@ -88,13 +92,15 @@ int launch_order_kernel(int64_t B, hipStream_t st, const DevModel* m, const IO& 
                         uint8_t* hot_flag, int32_t* order);
 
 #ifdef DRC_PHASE_TIMING
-// diagnostic build: add each unit's phase slots to out[64]
+// diagnostic build: add each unit's phase slots to out[96]
 int phase_cycles_task(unsigned long long* out, int reset);
 int phase_cycles_qp(unsigned long long* out, int reset);
+int phase_cycles_qp_dense(unsigned long long* out, int reset);
 int phase_cycles_qpid(unsigned long long* out, int reset);
 int phase_cycles_fused(unsigned long long* out, int reset);
 // ... and the QP kernels' histogram of polish reduced-KKT sizes to out[16]
 int phase_cycles_qp_hist(unsigned long long* out, int reset);
+int phase_cycles_qp_dense_hist(unsigned long long* out, int reset);
 int phase_cycles_fused_hist(unsigned long long* out, int reset);
 #endif
 

@@ -55,6 +55,7 @@ qp_kernel(const DevModel* __restrict__ M0, const KParams kp, const IO io) {
 }
 
 
+#ifndef DRC_QP_DENSE_UNIT
 bool qp_compiled(int nx, int ng, int np) {
   return (nx == 23 && ng == 16 && np == 7) || (nx == 20 && ng == 14 && np == 6) || (nx == 9 && ng == 16 && np == 9) ||
          (nx == 11 && ng == 16 && np == 11);
@@ -65,6 +66,9 @@ int qp_waves_per_simd() { return DRC_QP_WAVES; }
 int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io) {
   const dim3 g(grid), blk(64);
   const size_t lg = lds * (64 / kQpGroup);  // one LDS plan per lane group
+  // QPIK only: the manipulator shapes' G pattern (kQpikSparse) is qp_assemble's.  The fused, rollout and reach
+  // launchers take the same shapes and are QPIK entry points by construction (QPID has qpid_kernel.hip)
+  if (kp.problem != 0) return hipErrorInvalidValue;
   if (kp.nx == 23 && kp.ng == 16 && kp.np == 7)  // FR3
     hipLaunchKernelGGL((qp_kernel<Dims<23, 16, 7, true, true, kQpGroup>>), g, blk, lg, st, m, kp, io);
   else if (kp.nx == 20 && kp.ng == 14 && kp.np == 6)  // UR5e
@@ -78,8 +82,31 @@ int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* 
   return hipGetLastError();
 }
 
+#else
+// The manipulator shapes with every G loop dense (Dims<..., dense = true>): the
+// reference the shipped instantiations are compared with bit for bit
+// (drc_debug_qp_dense), in a unit of its own (qp_dense_kernel.hip).
+int launch_qp_dense_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                           const IO& io) {
+  const dim3 g(grid), blk(64);
+  const size_t lg = lds * (64 / kQpGroup);
+  if (kp.problem != 0) return hipErrorInvalidValue;  // QPIK only, as launch_qp_kernel
+  if (kp.nx == 23 && kp.ng == 16 && kp.np == 7)  // FR3
+    hipLaunchKernelGGL((qp_kernel<Dims<23, 16, 7, true, true, kQpGroup, true>>), g, blk, lg, st, m, kp, io);
+  else if (kp.nx == 20 && kp.ng == 14 && kp.np == 6)  // UR5e
+    hipLaunchKernelGGL((qp_kernel<Dims<20, 14, 6, true, true, kQpGroup, true>>), g, blk, lg, st, m, kp, io);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+#endif
+
 #ifdef DRC_PHASE_TIMING
+#ifndef DRC_QP_DENSE_UNIT
 DRC_PHASE_EXPORT(phase_cycles_qp)
+#else
+DRC_PHASE_EXPORT(phase_cycles_qp_dense)
+#endif
 #endif
 
 }  // namespace drc_amd

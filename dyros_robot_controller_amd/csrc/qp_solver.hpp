@@ -7,8 +7,69 @@
 
 #include "kernel_common.hpp"
 #include "eqp_small.hpp"
+#include "qpik_pattern.hpp"
 
 namespace drc_amd {
+
+// The manipulator QP-IK shapes (Dims<23,16,7>, <20,14,6>): G has the fixed
+// pattern of qpik_pattern.hpp, and schur_setup, the Schur ADMM's G-column
+// pass, qp_scale_roles and the polish's Jacobi guess visit its nonzero entries
+// only.  These shapes reach the QP code only as QPIK on a fixed-base model
+// (make_kparams: kind 0 <=> np < nx, nx = np + ng, ng = 2 np + 2; QPID has its
+// own kernel and shapes).  Dims<..., dense = true> keeps the dense loops: the
+// reference build the sparse one is compared with bit for bit
+// (drc_debug_qp_dense, tests/test_gpu_qp_sparse.py).
+// Why the bits stay: a dropped term is fma(+-0, v, acc) with finite v, which
+// returns acc unless acc is -0 (then +0 or -0 by the product's sign).  The
+// accumulators of schur_setup, the ADMM pass and the row sums start at +0 or at
+// a P entry and a sum of such terms is never -0.  Three start from a value
+// that can be -0 -- the Jacobi guess's c0 (q_l) and aty / s in residuals /
+// primal_infeasible (ab y) -- and there the zero's sign cannot reach a result:
+// c = c0 + c1 with c1 never -0, and aty and s are read through fabs or added
+// to a sum that fabs closes.
+#ifndef DRC_ADMM_READLANE_BCAST
+template <class QD>
+constexpr bool kQpikSparse = QD::schur && QD::gs == 64 && QD::np > 0 && QD::np < QD::nx && QD::ng == 2 * QD::np + 2 &&
+                             QD::nx == QD::np + QD::ng && !QD::dense;
+#else
+template <class QD>
+constexpr bool kQpikSparse = false;
+#endif
+
+// sum_i G[i][c] v[i] added to acc in ascending row order over column c's rows
+// that can be nonzero (kQpikSparse; a q-dot column's four, a slack column's one)
+template <class QD>
+__device__ __forceinline__ double qpik_col_dot(const double* G, const double* v, int c, double acc) {
+  using Pat = QpikPattern<QD::np>;
+  const int cnt = Pat::col_count(c);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k < cnt) {
+      const int i = Pat::col_row(c, k);
+      acc += G[i * QD::nx + c] * v[i];
+    }
+  }
+  return acc;
+}
+// sum_j G[r][j] x[j] from zero in ascending column order over row r's columns
+// that can be nonzero (a row r < 2 n: its q-dot column; a gradient row: all
+// of them; then the slack column)
+template <class QD>
+__device__ __forceinline__ double qpik_row_dot(const double* G, const double* x, int r) {
+  using Pat = QpikPattern<QD::np>;
+  constexpr int NX = QD::nx, NP = QD::np;
+  double ax = 0;
+  if (r < 2 * NP) {
+    const int c = Pat::row_col(r, 0);
+    ax += G[r * NX + c] * x[c];
+  } else {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) ax += G[r * NX + j] * x[j];
+  }
+  const int a = Pat::slack_col(r);
+  ax += G[r * NX + a] * x[a];
+  return ax;
+}
 
 // ------------------------------------------------------------------------
 // OSQP residuals (lane-parallel): fills SC_* slots.  x, z, y in LDS (scaled)
@@ -42,8 +103,12 @@ __device__ __forceinline__ void residuals(const KParams& kp, double* S, const do
       for (int c = 0; c < np; ++c) px += P[lp * np + c] * x[c];
     }
     double aty = ab[lx] * y[lx];
+    if constexpr (kQpikSparse<QD>) {
+      aty = qpik_col_dot<QD>(G, y + nx, lx, aty);
+    } else {
 #pragma unroll
-    for (int i = 0; i < ng; ++i) aty += G[i * nx + lx] * y[nx + i];
+      for (int i = 0; i < ng; ++i) aty += G[i * nx + lx] * y[nx + i];
+    }
     double rr = px + q[lx] + aty;
     drs = fabs(rr);
     dr = fabs(rr * Di[lx]);
@@ -59,6 +124,8 @@ __device__ __forceinline__ void residuals(const KParams& kp, double* S, const do
     double ax = 0;
     if constexpr (PRE) {
       ax = axg_pre;
+    } else if constexpr (kQpikSparse<QD>) {
+      ax = qpik_row_dot<QD>(G, x, lg);
     } else {
 #pragma unroll
       for (int j = 0; j < nx; ++j) ax += G[lg * nx + j] * x[j];
@@ -226,10 +293,17 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
   double* wt = cf + NG;                // NG (row weights w_r)
   int* aux = reinterpret_cast<int*>(wt + NG);  // NG
   const double sig = kp.s.sigma;
+  constexpr bool kSparse = kQpikSparse<QD>;
+  using Pat = QpikPattern<NP>;
+  PH_STAMP(ss_t0);
   if (l < NG) {
     int a = -1;
-    for (int j = NP; j < NX; ++j)
-      if (G[l * NX + j] != 0.0) a = j;
+    if constexpr (kSparse) {
+      a = Pat::slack_col(l);  // (its entry is 1 times Ruiz factors in [1e-4, 1e4]: never zero)
+    } else {
+      for (int j = NP; j < NX; ++j)
+        if (G[l * NX + j] != 0.0) a = j;
+    }
     const double rr = rho[NX + l];
     double d = 1.0, w = rr, c = 0.0;
     if (a >= 0) {
@@ -244,15 +318,30 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
     wt[l] = w;
   }
   wsync();
+  PH_SINCE(68, ss_t0);  // row weights
+  PH_STAMP(ss_t1);
   for (int e = l; e < NP * NP; e += GL::size) {  // entry (i, c) of S, one per lane
     const int i = e / NP, c = e % NP;
     double sv = P[i * NP + c];
     if (c == i) sv += sig + rho[i] * ab[i] * ab[i];
+    if constexpr (kSparse) {
+      // rows i and n + i hold column i alone: they add on the diagonal; the
+      // two gradient rows add everywhere (ascending r, as the dense loop)
+      if (c == i) {
+        sv += wt[i] * G[i * NX + i] * G[i * NX + c];
+        sv += wt[NP + i] * G[(NP + i) * NX + i] * G[(NP + i) * NX + c];
+      }
+      sv += wt[Pat::kMan] * G[Pat::kMan * NX + i] * G[Pat::kMan * NX + c];
+      sv += wt[Pat::kDist] * G[Pat::kDist * NX + i] * G[Pat::kDist * NX + c];
+    } else {
 #pragma unroll
-    for (int r = 0; r < NG; ++r) sv += wt[r] * G[r * NX + i] * G[r * NX + c];
+      for (int r = 0; r < NG; ++r) sv += wt[r] * G[r * NX + i] * G[r * NX + c];
+    }
     Si[e] = sv;
   }
   wsync();
+  PH_SINCE(69, ss_t1);  // S entries
+  PH_STAMP(ss_t2);
   // Gauss-Jordan in registers, lane l holding row l (S is SPD)
   const int lr = l < NP ? l : 0;
   double Sr[NP];
@@ -291,14 +380,20 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
     for (int c = 0; c < NP; ++c) Si[l * NP + c] = Sr[c];
   }
   wsync();
+  PH_SINCE(70, ss_t2);  // Gauss-Jordan
+  PH_STAMP(ss_t3);
   for (int e = l; e < NG * NP; e += GL::size) {  // G_c S^-1
     const int r = e / NP, c = e % NP;
     double sv = 0;
+    // (dense for every shape: a row r < 2 n has one nonzero term, but the lanes
+    // of the two gradient rows keep the wave on all NP terms, so a split by row
+    // kind runs both forms; DESIGN.md "qp_kernel" has the measurement)
 #pragma unroll
     for (int k = 0; k < NP; ++k) sv += G[r * NX + k] * Si[k * NP + c];
     GS[e] = sv;
   }
   wsync();
+  PH_SINCE(71, ss_t3);  // G_c S^-1
 }
 
 template <class QD>
@@ -350,7 +445,11 @@ __device__ __forceinline__ bool primal_infeasible(const KParams& kp, double* S, 
   double viol = 0;
   if (l < nx) {
     double s = ab[l] * dy[l];
-    for (int i = 0; i < ng; ++i) s += G[i * nx + l] * dy[nx + i];
+    if constexpr (kQpikSparse<QD>) {
+      s = qpik_col_dot<QD>(G, dy + nx, l, s);
+    } else {
+      for (int i = 0; i < ng; ++i) s += G[i * nx + l] * dy[nx + i];
+    }
     viol = fabs(s * S[kp.oDi + l]);
   }
   viol = GL::max(viol);
@@ -1269,15 +1368,28 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
     // row (gv, yr, cnt; used below)
     double c0 = qv[lx], c1 = 0.0, gv = 0.0, yr = 0.0;
     int cnt = 0;
+    if constexpr (kQpikSparse<QD>) {
+      // a q-dot lane's four rows in the dense pass's parity split; a slack
+      // lane's own row (c0 / c1 are read on the q-dot lanes only)
+      using Pat = QpikPattern<QD::np>;
+      const int ra = Pat::pair_a(lp), rb = Pat::pair_b(lp);
+      Pat::parity_sums(lp, G[ra * nx + lp], y[nx + ra], G[rb * nx + lp], y[nx + rb], G[Pat::kMan * nx + lp],
+                       y[nx + Pat::kMan], G[Pat::kDist * nx + lp], y[nx + Pat::kDist], c0, c1);
+      const int rs = l >= np && l < nx ? l - np : 0;
+      gv = G[rs * nx + Pat::slack_col(rs)];
+      yr = y[nx + rs];
+      cnt = gv != 0.0 ? 1 : 0;
+    } else {
 #pragma unroll
-    for (int i = 0; i < ng; ++i) {
-      const double g = G[i * nx + lx], yi = y[nx + i];
-      if (i & 1) c1 += g * yi;
-      else c0 += g * yi;
-      if (g != 0.0) {
-        gv = g;
-        yr = yi;
-        ++cnt;
+      for (int i = 0; i < ng; ++i) {
+        const double g = G[i * nx + lx], yi = y[nx + i];
+        if (i & 1) c1 += g * yi;
+        else c0 += g * yi;
+        if (g != 0.0) {
+          gv = g;
+          yr = yi;
+          ++cnt;
+        }
       }
     }
     const double c = c0 + c1;
@@ -1609,6 +1721,7 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
   }
   wsync();
   PH_SINCE(44, as_t0);
+  PH_STAMP(as_t1);
   const double bestd = S[kp.oSc + SC_DIST];
   // ---------------- QP assembly (QP_IK.cpp:69-131 / MoMa :59-128) --------
   const int nx = DNX, ng = DNG, np = DNP, m = DM;
@@ -1645,6 +1758,8 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
     for (int r = 0; r < 6; ++r) s += Jt[r * np + i] * Jt[r * np + j];
     P[e] = 2.0 * s + (i == j ? kp.w_reg : 0.0);
   }
+  PH_SINCE(72, as_t1);  // J~ and P
+  PH_STAMP(as_t2);
   for (int e = l; e < ng * nx; e += GL::size) G[e] = 0.0;
   if (l < nx) {
     double qi;
@@ -1693,6 +1808,7 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
     up[row] = kInf;
   }
   wsync();
+  PH_SINCE(73, as_t2);  // G zero fill, q, bounds (the model's vel / lower / upper), G rows
 }
 
 // Whole-body QP infeasibility certificate (exact mode, D15).  The MoMa QP has
@@ -1971,7 +2087,11 @@ __device__ __forceinline__ int qp_scale_regs(const KParams& kp, double* S) {
 // operands, same products in the same order as qp_scale_regs (bit-identical);
 // the column copy of G is dropped at the end, as there.
 template <class QD>
+__device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* S);
+
+template <class QD>
 __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
+  if constexpr (kQpikSparse<QD>) return qp_scale_roles_sparse<QD>(kp, S);
   using GL = Grp<64>;
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np, M = NX + NG;
   constexpr int KV = NP + NG > NX ? NP + NG : NX;
@@ -1979,6 +2099,7 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
   const int l = GL::lane();
   double *P = S + kp.oP, *G = S + kp.oG, *qq = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU;
   double *D = S + kp.oD, *E = S + kp.oE, *sc = S + kp.oSc;
+  PH_STAMP(sr_t0);
   {
     bool finite = true;
     for (int e = l; e < NP * NP; e += GL::size) finite &= isfinite(P[e]);
@@ -1987,6 +2108,8 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
     for (int row = l; row < M; row += GL::size) finite &= !isnan(lo[row]) && !isnan(up[row]);
     if (!GL::all(finite)) return DRC_STATUS_NONFINITE;
   }
+  PH_SINCE(64, sr_t0);  // finiteness sweep
+  PH_STAMP(sr_t1);
   const bool col = l < NX, row = l >= NX && l < M, hp = l < NP;
   const int lc = col ? l : 0, lp = hp ? l : 0, r = row ? l - NX : 0;
   double V[KV];
@@ -1999,6 +2122,8 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
     V[k] = col ? vc : (row ? vr : 0.0);
   }
   double abl = ab[lc], ql = qq[lc], Dl = 1.0, El = 1.0, EGl = 1.0, cs = 1.0;
+  PH_SINCE(65, sr_t1);  // V load
+  PH_STAMP(sr_t2);
   auto clampf = [](double v) { return v < kMinScaling ? 1.0 : (v > kMaxScaling ? kMaxScaling : v); };
   lds_double* wb = (lds_double*)(S + kp.oBc);  // NX + NG doubles (plan_layout)
   for (int it = 0; it < kp.s.scaling; ++it) {
@@ -2054,6 +2179,8 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
     cs *= ct;
     if (ct == 1.0 && unit) break;
   }
+  PH_SINCE(66, sr_t2);  // the passes
+  PH_STAMP(sr_t3);
   if (hp)
 #pragma unroll
     for (int c = 0; c < NP; ++c) P[l * NP + c] = V[c];
@@ -2074,6 +2201,150 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
     up[rw] = fmin(up[rw], kInf) * E[rw];
   }
   wsync();
+  PH_SINCE(67, sr_t3);  // write-back
+  return DRC_STATUS_MAX_ITER;
+}
+
+// qp_scale_roles on the manipulator QP's pattern (kQpikSparse): a lane holds
+// only the entries of its column / row that can be nonzero.
+//   V[0 .. NP)   q-dot column lanes: row l of P; the two gradient row lanes:
+//                G[r][0 .. NP); every other lane: zeros
+//   V[NP + j]    j < 4, entry eo[j] of G with the other side's factor at
+//                wb[wi[j]]: a q-dot column's four rows; a slack column's one
+//                row; row r < 2 n: its q-dot and slack entries; a gradient
+//                row: its slack entry.  Unused slots hold zeros.
+// The row lanes between them hold every entry of G that can be nonzero and
+// the q-dot column lanes all of P, so the finiteness check reads V.  The
+// same factors, and per entry the same two products, as the dense passes (a
+// maximum does not depend on its order; zeros scale to zeros): bit-identical
+// P, G, q, D, E, c.  G's other entries keep qp_assemble's zero fill.
+template <class QD>
+__device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* S) {
+  using GL = Grp<64>;
+  using Pat = QpikPattern<QD::np>;
+  constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np, M = NX + NG;
+  constexpr int KV = NP + 4;
+  static_assert(M <= 64, "one lane per column and per G row");
+  const int l = GL::lane();
+  double *P = S + kp.oP, *G = S + kp.oG, *qq = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU;
+  double *D = S + kp.oD, *E = S + kp.oE, *sc = S + kp.oSc;
+  PH_STAMP(sr_t1);
+  const bool col = l < NX, row = l >= NX && l < M, hp = l < NP;
+  const int lc = col ? l : 0, r = row ? l - NX : 0;
+  const bool grow = row && r >= 2 * NP;  // the two gradient rows
+  const bool hv = hp || grow;            // V[0 .. NP) live
+  double* const Vb = hp ? P + l * NP : G + r * NX;
+  // the lane's short list: element offsets into G, and where the other side's factor sits in wb
+  const int nl = hp ? 4 : (row && !grow ? 2 : (col || grow ? 1 : 0));
+  int eo[4], wi[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int e = 0, w = 0;
+    if (hp) {
+      const int rj = Pat::col_row(l, j);
+      e = rj * NX + l;
+      w = NX + rj;
+    } else if (col) {  // slack column: row l - NP
+      e = (l - NP) * NX + l;
+      w = NX + l - NP;
+    } else if (row && !grow) {  // row r < 2 n: the q-dot entry, the slack entry
+      const int cj = Pat::row_col(r, j < 2 ? j : 0);
+      e = r * NX + cj;
+      w = cj;
+    } else if (grow) {  // gradient row: the slack entry
+      e = r * NX + Pat::slack_col(r);
+      w = Pat::slack_col(r);
+    }
+    eo[j] = j < nl ? e : 0;
+    wi[j] = j < nl ? w : 0;
+  }
+  double V[KV];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) V[k] = hv ? Vb[k] : 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) V[NP + j] = j < nl ? G[eo[j]] : 0.0;
+  PH_SINCE(65, sr_t1);  // lane roles + V load
+  PH_STAMP(sr_t0);
+  {
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) finite &= isfinite(V[k]);
+    if (l < NX) finite &= isfinite(qq[l]);
+    for (int rw = l; rw < M; rw += GL::size) finite &= !isnan(lo[rw]) && !isnan(up[rw]);
+    if (!GL::all(finite)) return DRC_STATUS_NONFINITE;
+  }
+  PH_SINCE(64, sr_t0);  // finiteness check (on V)
+  PH_STAMP(sr_t2);
+  double abl = ab[lc], ql = qq[lc], Dl = 1.0, El = 1.0, EGl = 1.0, cs = 1.0;
+  auto clampf = [](double v) { return v < kMinScaling ? 1.0 : (v > kMaxScaling ? kMaxScaling : v); };
+  lds_double* wb = (lds_double*)(S + kp.oBc);  // NX + NG doubles (plan_layout)
+  for (int it = 0; it < kp.s.scaling; ++it) {
+    PH_ADD(49, 1);  // Ruiz passes
+    const double mx = absmax_tree(V);
+    const double F = 1.0 / sqrt(clampf(col ? fmax(fabs(abl), mx) : mx));  // D~ (column) / E~ (row)
+    const double Et = 1.0 / sqrt(clampf(fabs(abl)));                       // bound-row E~ (column lanes)
+    const bool unit = GL::all((!col || (F == 1.0 && Et == 1.0)) && (!row || F == 1.0));
+    if (!unit) {
+      if (l < M) wb[l] = F;  // wb[c] = D~_c, wb[NX + r] = E~_r
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int k = 0; k < NP; ++k) V[k] *= F * wb[k];  // P entry (D~_l D~_k) / gradient row entry (E~_r D~_k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) V[NP + j] *= F * wb[wi[j]];  // G entry (E~_i D~_c)
+      asm volatile("" ::: "memory");
+      if (col) {
+        abl *= Et * F;
+        ql *= F;
+        Dl *= F;
+        El *= Et;
+      }
+      if (row) EGl *= F;
+    }
+    // cost scaling: mean column norm of P vs |q|_inf
+    double cn = 0, qn = 0;
+    if (hp) {
+      double t[NP];
+#pragma unroll
+      for (int c = 0; c < NP; ++c) t[c] = V[c];
+      cn = absmax_tree(t);
+    }
+    if (col) qn = fabs(ql);
+    cn = GL::sum(cn) / NX;
+    qn = GL::max(qn);
+    qn = clampf(qn);
+    double ct = clampf(fmax(cn, qn));
+    ct = 1.0 / ct;
+    if (hp)
+#pragma unroll
+      for (int c = 0; c < NP; ++c) V[c] *= ct;
+    if (col) ql *= ct;
+    cs *= ct;
+    if (ct == 1.0 && unit) break;
+  }
+  PH_SINCE(66, sr_t2);  // the passes
+  PH_STAMP(sr_t3);
+  if (hv)
+#pragma unroll
+    for (int c = 0; c < NP; ++c) Vb[c] = V[c];
+  if (row)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < nl) G[eo[j]] = V[NP + j];
+  if (col) {
+    ab[l] = abl;
+    qq[l] = ql;
+    D[l] = Dl;
+    E[l] = El;
+  }
+  if (row) E[NX + r] = EGl;
+  if (l == 0) sc[SC_C] = cs;
+  wsync();
+  for (int rw = l; rw < M; rw += GL::size) {
+    lo[rw] = fmax(lo[rw], -kInf) * E[rw];
+    up[rw] = fmin(up[rw], kInf) * E[rw];
+  }
+  wsync();
+  PH_SINCE(67, sr_t3);  // write-back
   return DRC_STATUS_MAX_ITER;
 }
 
@@ -2118,17 +2389,28 @@ struct SchurLanes {
     iv = hc ? lc : ia;
   }
   // lane l: row l of S^-1 then column l of G_c (core lanes); row r of G_c S^-1 (row lanes)
-  __device__ __forceinline__ void load(double (&R)[NP + NG]) const {
+  // (kQpikSparse: of column l's entries the four that can be nonzero, rows
+  // pair_a, pair_b, 2 n, 2 n + 1 of qpik_pattern.hpp)
+  static constexpr int kCol = kQpikSparse<QD> ? 4 : NG;
+  __device__ __forceinline__ void load(double (&R)[NP + kCol]) const {
     if (hc) {
 #pragma unroll
       for (int c = 0; c < NP; ++c) R[c] = Si[lc * NP + c];
+      if constexpr (kQpikSparse<QD>) {
+        using Pat = QpikPattern<NP>;
+        R[NP] = G[Pat::pair_a(lc) * NX + lc];
+        R[NP + 1] = G[Pat::pair_b(lc) * NX + lc];
+        R[NP + 2] = G[Pat::kMan * NX + lc];
+        R[NP + 3] = G[Pat::kDist * NX + lc];
+      } else {
 #pragma unroll
-      for (int i = 0; i < NG; ++i) R[NP + i] = G[i * NX + lc];
+        for (int i = 0; i < NG; ++i) R[NP + i] = G[i * NX + lc];
+      }
     } else {
 #pragma unroll
       for (int c = 0; c < NP; ++c) R[c] = GS[rr * NP + c];
 #pragma unroll
-      for (int i = 0; i < NG; ++i) R[NP + i] = 0.0;
+      for (int i = 0; i < kCol; ++i) R[NP + i] = 0.0;
     }
   }
 };
@@ -2159,7 +2441,9 @@ __device__ __forceinline__ void admm_iters_schur(const KParams& kpl, double* S, 
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
   (void)NX;
   static_assert(NP + NG <= QD::gs, "one lane per core variable and per G row");
-  double R[NP + NG];
+  constexpr bool kSparse = kQpikSparse<QD>;
+  using Pat = QpikPattern<NP>;
+  double R[NP + SchurLanes<QD>::kCol];
   // The lane's variable v (with its bound row): the core variable on a core
   // lane, the auxiliary variable on a row lane that has one.  A lane is never
   // both, so the two share one register set (same update formulas; fewer
@@ -2212,12 +2496,17 @@ __device__ __forceinline__ void admm_iters_schur(const KParams& kpl, double* S, 
 #ifndef DRC_ADMM_READLANE_BCAST  // the two passes' vectors broadcast through LDS (r04: +1-3 %)
       if (hr) wb[rr_l] = u;
       asm volatile("" ::: "memory");
-      static_for<NG>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        const double ui = wb[i];
-        if constexpr (i & 1) r1 += R[NP + i] * ui;
-        else r0 += R[NP + i] * ui;
-      });
+      if constexpr (kSparse) {  // column lc's four rows, in the dense pass's parity split
+        const double ua = wb[Pat::pair_a(lc_l)], ub = wb[Pat::pair_b(lc_l)], um = wb[Pat::kMan], ud = wb[Pat::kDist];
+        Pat::parity_sums(lc_l, R[NP], ua, R[NP + 1], ub, R[NP + 2], um, R[NP + 3], ud, r0, r1);
+      } else {
+        static_for<NG>([&](auto I) {
+          constexpr int i = decltype(I)::value;
+          const double ui = wb[i];
+          if constexpr (i & 1) r1 += R[NP + i] * ui;
+          else r0 += R[NP + i] * ui;
+        });
+      }
       const double rp = loc + (r0 + r1);
       if (hc) wb[NG + lc_l] = rp;
       asm volatile("" ::: "memory");

@@ -82,6 +82,17 @@ int drc_debug_instance_order(drc_model* model, const int32_t* order, int64_t n);
  * identical inputs and exercise each size boundary. */
 int drc_debug_eqp_small_cap(drc_model* model, int cap);
 
+/* The dense reference build of the manipulator QP kernels.  The shipped QP
+ * code of the fixed-base shapes (FR3, UR5e) visits only the entries of G that
+ * qp_assemble can make nonzero; with `on` != 0 a QPIK call of the two-kernel
+ * pipeline (drc_set_fusion(model, 0)) launches the same kernel built with every
+ * G loop dense instead.  Both return the same bits (only exact zeros leave the
+ * sums); the switch lets tests compare them on identical inputs.  Other shapes
+ * ignore it.  drc_debug_qp_dense_launches reports how many dense QP kernels
+ * the model has launched so far. */
+int drc_debug_qp_dense(drc_model* model, int on);
+int drc_debug_qp_dense_launches(drc_model* model, int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,9 @@ mod = manipulator if spec["kind"] == "manipulator" else mobile_manipulator
 ctrl = mod.RobotController(0.001, rd, solver_mode=SOLVER)
 _, args, _ = bench.make_inputs(rd, robot, B, 12345, 0, dev)   # bench.py's workload (stress tiers)
 _capi.lib().drc_set_concurrency(rd.model.handle, 1)  # one sub-batch: per-instance cycles without overlap
+if os.environ.get("DRC_QP_DENSE") == "1":  # the manipulator shapes' dense reference QP kernel (= the loops before the G pattern)
+    _capi.check(_capi.lib().drc_debug_qp_dense(rd.model.handle, 1))
+    print("QP kernel: dense reference build (drc_debug_qp_dense)")
 link = spec["link"]
 ctrl.QPIK_step_batch(*args, link); torch.cuda.synchronize()
 buf = (C.c_ulonglong * 64)()
@@ -61,3 +64,11 @@ if has_hist:
     n = max(h.sum(), 1)
     print("reduced-KKT size N of the %d EQPs: " % h.sum() + ", ".join("%s %.2f%%" % (("N=%d" % k) if k < 9 else "N>=9", 100 * x / n)
           for k, x in enumerate(list(h[:9]) + [h[9:].sum()])))
+if hasattr(_capi.lib(), "drc_debug_phase_cycles_fine"):  # (absent from older timing builds)
+    fine = (C.c_ulonglong * 32)()
+    _capi.lib().drc_debug_phase_cycles_fine(fine)
+    f = np.array(fine[:], dtype=np.float64) / B
+    print("QP front end, finer (cycles/instance): assemble after the record load: J~ and P %.0f, G fill + q + bounds + G rows %.0f"
+          % (f[8], f[9]))
+    print("  scaling: finiteness %.0f, lane roles + V load %.0f, passes %.0f, write-back %.0f" % tuple(f[0:4]))
+    print("  schur_setup (every factorisation): row weights %.0f, S entries %.0f, Gauss-Jordan %.0f, G_c S^-1 %.0f" % tuple(f[4:8]))
