@@ -26,6 +26,7 @@
 #include "reach.hpp"
 #include "reach_path.hpp"
 #include "reach_seeds.hpp"
+#include "rollout_update.hpp"
 
 // ==========================================================================
 // host side: the C-ABI (include/drc_amd.h)
@@ -54,7 +55,7 @@ struct StreamCtx {
   int* d_queue = nullptr;
   int* dyn_list = nullptr;  // instances whose M_inv needs the serial COD
   int64_t dyn_list_cap = 0;
-  void* roll = nullptr;  // rollouts without qdot_traj: one step's eta [na][B]
+  void* roll = nullptr;  // rollout / reach / reach path scratch: one step's eta, stage outputs, status, counters
   int64_t roll_bytes = 0;
   void* seeds = nullptr;  // drc_qpik_reach_seeds_batch: per-instance results, expanded targets, group words
   int64_t seeds_bytes = 0;
@@ -996,11 +997,110 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
                        pair, xdd, stream, stamps, ob);
 }
 
-// t_k = t + k dt as a rounded product and a rounded sum (the persistent
-// kernel's rollout_time, rollout_update.hpp)
-static double rollout_time(double t, int k, double dt) {
-  volatile double d = static_cast<double>(k) * dt;
-  return t + d;
+// --------------------------------------------------------------------------
+// The closed-loop entries (rollout, reach, reach_path, reach_seeds): what their
+// host sides have in common
+// --------------------------------------------------------------------------
+static bool finite_positive(double x) { return std::isfinite(x) && x > 0; }
+
+// The obstacle arguments against the model: slots need poses (slots_msg: the
+// entry's own "pass their poses through ..."), poses need slots (plain_entry:
+// the entry that runs a model without them, where the text names one)
+static int check_slots(const drc_model_impl* m, const Obst* ob, const char* slots_msg,
+                       const char* plain_entry = nullptr) {
+  const bool slots = m->hm.dev.nobst > 0;
+  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, slots_msg);
+  if (!slots && ob)
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   std::string("the model has no obstacle slots (drc_model_set_obstacles declares them)") +
+                       (plain_entry ? std::string(": ") + plain_entry + " runs it" : std::string()));
+  return DRC_OK;
+}
+// ... and the poses themselves: [nobst][12][ld] with ld = 0 or at least `cols` columns
+static int check_obstacle_pose(const Obst* ob, int64_t cols, const char* cols_name) {
+  if (ob && cols > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < cols)))
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   std::string("obstacle_pose is required, obstacle_ld is 0 (shared) or at least ") + cols_name);
+  return DRC_OK;
+}
+static int check_dt(double dt) {
+  if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
+  return DRC_OK;
+}
+static int check_dt_tolerances(double dt, double pos_tol, double rot_tol) {
+  if (int rc = check_dt(dt)) return rc;
+  if (!finite_positive(pos_tol) || !finite_positive(rot_tol))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  return DRC_OK;
+}
+static int check_batch(int64_t B) {
+  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
+  return DRC_OK;
+}
+// the task stage's and the QP's parameters of a QPIK call
+static int make_kparams_pair(const drc_model_impl* m, const drc_qpik_params* params, KParams* kt, KParams* kq) {
+  if (int rc = make_kparams(m, params, 1, kt)) return rc;
+  return make_kparams(m, params, 0, kq);
+}
+
+// The fusion rule (launch_locked) selects an entry's persistent kernel: the
+// compiled QP shapes up to max_b instances, where the entry has a build that
+// serves the model's hulls / obstacle slots
+static bool persistent_path(const drc_model_impl* m, const KParams& kq, int64_t B, int64_t max_b, bool serves_hulls,
+                            bool serves_slots) {
+  const DevModel& dm = m->hm.dev;
+  return m->fused && m->lane_stage == 0 && B <= max_b && kQpGroup == 64 && qp_compiled(kq.nx, kq.ng, kq.np) &&
+         (serves_slots || dm.nobst == 0) && (serves_hulls || !dm.has_mesh);
+}
+
+// Grows a stream context's scratch block (cx->roll, cx->seeds) to `bytes`; the
+// caller holds m->mu
+static int grow_scratch(void** p, int64_t* have, int64_t bytes) {
+  if (*have >= bytes) return DRC_OK;
+  if (*p) HIP_TRY(hipFree(*p));  // synchronises: no launch still uses it
+  *p = nullptr;
+  *have = 0;
+  HIP_TRY(hipMalloc(p, bytes));
+  *have = bytes;
+  return DRC_OK;
+}
+// Carves arrays off a scratch block one after the other: the doubles first,
+// then the int32 arrays, so every array is aligned to its element
+struct Carver {
+  char* p;
+  template <class T>
+  T* take(int64_t n) {
+    T* r = reinterpret_cast<T*>(p);
+    p += n * int64_t(sizeof(T));
+    return r;
+  }
+};
+
+// What a persistent closed-loop launch needs first: the grid, the placement
+// and the zeroed work queue of io, the caller's IO of the whole batch (q, qdot,
+// the targets, eta / status / iters -- one step's scratch or the trajectories;
+// every other member null)
+static int persistent_setup(StreamCtx* cx, hipStream_t st, KParams* kt, KParams* kq, IO* io, unsigned* grid) {
+  static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
+  *grid = static_cast<unsigned>(io->B < cap ? io->B : cap);
+  kt->xcd_map = kq->xcd_map = io->B >= 16384 ? 1 : 0;
+  io->queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
+  HIP_TRY(hipMemsetAsync(io->queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+  return DRC_OK;
+}
+
+// Start of a stepwise reach: the finals carry the state from the start, every
+// instance active, the counters zero
+static int stepwise_reach_init(hipStream_t st, int64_t B, int nv, const double* q0, const double* qdot0,
+                               const ReachArgs& re) {
+  const size_t state_bytes = size_t(nv) * B * 8;
+  if (re.qf != q0) HIP_TRY(hipMemcpyAsync(re.qf, q0, state_bytes, hipMemcpyDeviceToDevice, st));
+  if (re.vf != qdot0) HIP_TRY(hipMemcpyAsync(re.vf, qdot0, state_bytes, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetAsync(re.result, 0xff, size_t(B) * 4, st));  // kReachActive
+  if (re.status_last) HIP_TRY(hipMemsetAsync(re.status_last, 0, size_t(B) * 4, st));
+  if (re.iters_total) HIP_TRY(hipMemsetAsync(re.iters_total, 0, size_t(B) * 4, st));
+  return DRC_OK;
 }
 
 // drc_qpik_rollout_batch: `steps` control cycles (QPIK*, then the state
@@ -1019,23 +1119,18 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  const bool slots = m->hm.dev.nobst > 0;
-  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsPlainMsg);
-  if (!slots && ob)
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "the model has no obstacle slots (drc_model_set_obstacles declares them)");
+  if (int rc = check_slots(m, ob, kSlotsPlainMsg)) return rc;
   if (ob_per_step != 0 && ob_per_step != 1)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacles_per_step must be 0 or 1");
-  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
+  if (int rc = check_obstacle_pose(ob, B, "the batch")) return rc;
   if (steps < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "steps must be at least 1");
-  if (!std::isfinite(dt) || !(dt > 0)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
+  if (int rc = check_dt(dt)) return rc;
   if (per_step != 0 && per_step != 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "targets_per_step must be 0 or 1");
   if (per_step && params->mode == DRC_MODE_QPIK_CUBIC)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "per-step targets with QPIKCubic: the time already moves the target");
   if (!qf || !vf || !status_traj)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q_final, qdot_final and status_traj are required");
-  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
+  if (int rc = check_batch(B)) return rc;
   if (B > 0) {
     if (!q0 || !qdot0 || !xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0 and xdot_target are required");
     if (params->mode != DRC_MODE_QPIK && !xt)
@@ -1044,25 +1139,22 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
       return set_err(DRC_ERR_INVALID_ARGUMENT, "x_init/xdot_init required for QPIKCubic");
   }
   KParams kt, kq;
-  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
-  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (B == 0) return DRC_OK;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
-  // The fusion rule (launch_locked) selects the persistent kernel, up to the
-  // batch size where it was measured to beat the stepwise path at 32 steps
-  // (profiles/rollout_bench.json, DESIGN.md "Rollouts"): manipulators (FR3)
-  // through 4 096 instances -- from 8 192 on the stepwise path's fused calls
-  // with their EPA-first order win, 10.8 against 12.4 ms -- and whole-body
-  // robots (Husky-FR3) at every size measured, through 65 536 (92.8 against
-  // 133.2 ms).  DRC_ROLLOUT_MAX overrides (read per call, so that one process
-  // can measure both paths)
+  // The persistent kernel up to the batch size where it was measured to beat
+  // the stepwise path at 32 steps (profiles/rollout_bench.json, DESIGN.md
+  // "Rollouts"): manipulators (FR3) through 4 096 instances -- from 8 192 on
+  // the stepwise path's fused calls with their EPA-first order win, 10.8
+  // against 12.4 ms -- and whole-body robots (Husky-FR3) at every size
+  // measured, through 65 536 (92.8 against 133.2 ms).  DRC_ROLLOUT_MAX
+  // overrides (read per call, so that one process can measure both paths)
   const int64_t rollout_max = env_int("DRC_ROLLOUT_MAX", dm.kind == 0 ? 4096 : 65536, 0);
   // (models with obstacle slots: the stepwise path; no persistent build takes poses)
-  const bool persistent = m->fused && m->lane_stage == 0 && B <= rollout_max && kQpGroup == 64 &&
-                          qp_compiled(kq.nx, kq.ng, kq.np) && !slots;
+  const bool persistent = persistent_path(m, kq, B, rollout_max, true, false);
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
   double* eta = qdot_traj;  // without qdot_traj: one step's eta in stream scratch
@@ -1070,29 +1162,17 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     std::lock_guard<std::mutex> g(m->mu);
     if (int r = stream_ctx(m, st, &cx)) return r;
     if (!qdot_traj) {
-      const int64_t bytes = int64_t(na) * B * 8;
-      if (cx->roll_bytes < bytes) {
-        if (cx->roll) HIP_TRY(hipFree(cx->roll));  // synchronises: no launch still uses it
-        cx->roll = nullptr;
-        cx->roll_bytes = 0;
-        HIP_TRY(hipMalloc(&cx->roll, bytes));
-        cx->roll_bytes = bytes;
-      }
+      if (int r = grow_scratch(&cx->roll, &cx->roll_bytes, int64_t(na) * B * 8)) return r;
       eta = static_cast<double*>(cx->roll);
     }
   }
   const int64_t out_step = qdot_traj ? int64_t(na) * B : 0;
   if (persistent) {
-    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
-    const int64_t grid = B < cap ? B : cap;
-    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
-    IO io{B, 0, B, q0, qdot0, xt, xdt, xi, xdi, eta, status_traj, iters_traj, nullptr, nullptr, nullptr, nullptr,
-          nullptr, nullptr, nullptr, 0};
-    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
-    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
-    HIP_TRY(static_cast<hipError_t>(launch_rollout_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io,
-                                                          steps, per_step, dt, qf, vf, q_traj, pose_traj, dist_traj,
-                                                          out_step, dm.has_mesh != 0)));
+    IO io{B, 0, B, q0, qdot0, xt, xdt, xi, xdi, eta, status_traj, iters_traj};
+    unsigned grid;
+    if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
+    HIP_TRY(static_cast<hipError_t>(launch_rollout_kernel(grid, st, m->d_model, kt, kq, io, steps, per_step, dt, qf, vf,
+                                                          q_traj, pose_traj, dist_traj, out_step, dm.has_mesh != 0)));
     done_guard.ok = true;
     return DRC_OK;
   }
@@ -1127,8 +1207,6 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
 static const char kSlotsReachMsg[] =
     "the model has obstacle slots: pass their poses through drc_qpik_reach_obstacles_batch";
 
-static bool finite_positive(double x) { return std::isfinite(x) && x > 0; }
-
 // drc_qpik_reach_batch: the QPIKStep loop towards x_target with per-instance
 // stopping (include/drc_amd.h), enqueued on the caller's stream.  The compiled
 // QP shapes without hulls or slots, up to reach_max instances, run the
@@ -1147,27 +1225,19 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
                         const double* xdt, double* qf, double* vf, int32_t* result, int32_t* steps_used,
                         int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final,
                         void* stream, const Obst* ob) {
-  const bool slots = m->hm.dev.nobst > 0;
-  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsReachMsg);
-  if (!slots && ob)
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "the model has no obstacle slots (drc_model_set_obstacles declares them)");
-  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
+  if (int rc = check_slots(m, ob, kSlotsReachMsg)) return rc;
+  if (int rc = check_obstacle_pose(ob, B, "the batch")) return rc;
   if (params->mode != DRC_MODE_QPIK_STEP)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_batch runs DRC_MODE_QPIK_STEP only");
   if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
-  if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
-  if (!finite_positive(pos_tol) || !finite_positive(rot_tol))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  if (int rc = check_dt_tolerances(dt, pos_tol, rot_tol)) return rc;
   if (!qf || !vf || !result || !steps_used)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q_final, qdot_final, result and steps_used are required");
-  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
+  if (int rc = check_batch(B)) return rc;
   if (B > 0 && (!q0 || !qdot0 || !xt || !xdt))
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_target and xdot_target are required");
   KParams kt, kq;
-  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
-  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (B == 0) return DRC_OK;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1184,8 +1254,7 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   // measure both paths).  No persistent build has the hull narrow phase or
   // takes obstacle poses
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = m->fused && m->lane_stage == 0 && B <= reach_max && kQpGroup == 64 &&
-                          qp_compiled(kq.nx, kq.ng, kq.np) && !slots && !dm.has_mesh;
+  const bool persistent = persistent_path(m, kq, B, reach_max, false, false);
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
   // one step's scratch: eta [na][B], then (stepwise) pose [12][B] and dist
@@ -1194,41 +1263,25 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   {
     std::lock_guard<std::mutex> g(m->mu);
     if (int r = stream_ctx(m, st, &cx)) return r;
-    const int64_t bytes = n_dbl * 8 + 2 * B * 4;
-    if (cx->roll_bytes < bytes) {
-      if (cx->roll) HIP_TRY(hipFree(cx->roll));  // synchronises: no launch still uses it
-      cx->roll = nullptr;
-      cx->roll_bytes = 0;
-      HIP_TRY(hipMalloc(&cx->roll, bytes));
-      cx->roll_bytes = bytes;
-    }
+    if (int r = grow_scratch(&cx->roll, &cx->roll_bytes, n_dbl * 8 + 2 * B * 4)) return r;
   }
-  double* eta = static_cast<double*>(cx->roll);
-  double* s_pose = eta + int64_t(na) * B;
-  double* s_dist = s_pose + 12 * B;
-  int32_t* s_status = reinterpret_cast<int32_t*>(eta + n_dbl);
-  int32_t* s_iters = s_status + B;
+  Carver sc{static_cast<char*>(cx->roll)};
+  double* eta = sc.take<double>(int64_t(na) * B);
+  double* s_pose = sc.take<double>(persistent ? 0 : 12 * B);
+  double* s_dist = sc.take<double>(persistent ? 0 : int64_t(1 + nv) * B);
+  int32_t* s_status = sc.take<int32_t>(B);
+  int32_t* s_iters = sc.take<int32_t>(B);
   const ReachArgs re{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
                      err_final, dist_final};
   if (persistent) {
-    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
-    const int64_t grid = B < cap ? B : cap;
-    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
-    IO io{B, 0, B, q0, qdot0, xt, xdt, nullptr, nullptr, eta, s_status, s_iters, nullptr, nullptr, nullptr, nullptr,
-          nullptr, nullptr, nullptr, 0};
-    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
-    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
-    HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, re)));
+    IO io{B, 0, B, q0, qdot0, xt, xdt, nullptr, nullptr, eta, s_status, s_iters};
+    unsigned grid;
+    if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
+    HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(grid, st, m->d_model, kt, kq, io, re)));
     done_guard.ok = true;
     return DRC_OK;
   }
-  // the finals carry the state from the start; every instance active
-  const size_t state_bytes = size_t(nv) * B * 8;
-  if (qf != q0) HIP_TRY(hipMemcpyAsync(qf, q0, state_bytes, hipMemcpyDeviceToDevice, st));
-  if (vf != qdot0) HIP_TRY(hipMemcpyAsync(vf, qdot0, state_bytes, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemsetAsync(result, 0xff, size_t(B) * 4, st));  // kReachActive
-  if (status_last) HIP_TRY(hipMemsetAsync(status_last, 0, size_t(B) * 4, st));
-  if (iters_total) HIP_TRY(hipMemsetAsync(iters_total, 0, size_t(B) * 4, st));
+  if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, re)) return r;
   for (int k = 0; k <= max_steps; ++k) {
     const int last = k == max_steps;
     if (int rc = launch_locked(m, params, 1, B, qf, vf, xt, xdt, nullptr, nullptr, nullptr, nullptr, nullptr, s_pose,
@@ -1281,38 +1334,29 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  const bool slots = m->hm.dev.nobst > 0;
-  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsReachPathMsg);
-  if (!slots && ob)
-    return set_err(DRC_ERR_INVALID_ARGUMENT,
-                   "the model has no obstacle slots (drc_model_set_obstacles declares them): "
-                   "drc_qpik_reach_path_batch runs it");
-  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
+  if (int rc = check_slots(m, ob, kSlotsReachPathMsg, "drc_qpik_reach_path_batch")) return rc;
+  if (int rc = check_obstacle_pose(ob, B, "the batch")) return rc;
   if (params->mode != DRC_MODE_QPIK_STEP)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_path_batch runs DRC_MODE_QPIK_STEP only");
   if (W < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints must be at least 1");
   if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
   if (int64_t(W) * (int64_t(max_steps) + 1) > 0x7ffffff0)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints * (max_steps + 1) too large");  // 32-bit step counters
-  if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
-  if (!finite_positive(pos_tol) || !finite_positive(rot_tol))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  if (int rc = check_dt_tolerances(dt, pos_tol, rot_tol)) return rc;
   if (!qf || !vf || !result || !waypoints_reached || !steps_used)
     return set_err(DRC_ERR_INVALID_ARGUMENT,
                    "q_final, qdot_final, result, waypoints_reached and steps_used are required");
-  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
+  if (int rc = check_batch(B)) return rc;
   if (B > 0 && (!q0 || !qdot0 || !x_path || !xdot_path))
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_path and xdot_path are required");
   KParams kt, kq;
-  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
-  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (B == 0) return DRC_OK;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
+  const bool slots = dm.nobst > 0;
   double tau[2];
   reach_thresholds(pos_tol, rot_tol, tau);
   // reach()'s rule and its DRC_REACH_MAX (read per call), with the slots let in:
@@ -1322,8 +1366,7 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   // Husky-FR3 129 against 570 ms) and with four slots and one waypoint (FR3 565
   // against 1 786 ms; profiles/reach_path_bench.json, DESIGN.md "Reach paths")
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = m->fused && m->lane_stage == 0 && B <= reach_max && kQpGroup == 64 &&
-                          qp_compiled(kq.nx, kq.ng, kq.np) && !dm.has_mesh;
+  const bool persistent = persistent_path(m, kq, B, reach_max, false, true);
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
   // scratch: one step's eta [na][B], then (stepwise) pose [12][B], dist
@@ -1333,53 +1376,36 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   {
     std::lock_guard<std::mutex> g(m->mu);
     if (int r = stream_ctx(m, st, &cx)) return r;
-    const int64_t bytes = n_dbl * 8 + 3 * B * 4;
-    if (cx->roll_bytes < bytes) {
-      if (cx->roll) HIP_TRY(hipFree(cx->roll));  // synchronises: no launch still uses it
-      cx->roll = nullptr;
-      cx->roll_bytes = 0;
-      HIP_TRY(hipMalloc(&cx->roll, bytes));
-      cx->roll_bytes = bytes;
-    }
+    if (int r = grow_scratch(&cx->roll, &cx->roll_bytes, n_dbl * 8 + 3 * B * 4)) return r;
   }
-  double* eta = static_cast<double*>(cx->roll);
-  double* s_pose = eta + int64_t(na) * B;
-  double* s_dist = s_pose + 12 * B;
-  double* s_xt = s_dist + int64_t(1 + nv) * B;
-  double* s_xdt = s_xt + 12 * B;
-  int32_t* s_status = reinterpret_cast<int32_t*>(eta + n_dbl);
-  int32_t* s_iters = s_status + B;
-  int32_t* s_seg = s_iters + B;
+  Carver sc{static_cast<char*>(cx->roll)};
+  double* eta = sc.take<double>(int64_t(na) * B);
+  double* s_pose = sc.take<double>(persistent ? 0 : 12 * B);
+  double* s_dist = sc.take<double>(persistent ? 0 : int64_t(1 + nv) * B);
+  double* s_xt = sc.take<double>(persistent ? 0 : 12 * B);
+  double* s_xdt = sc.take<double>(persistent ? 0 : 6 * B);
+  int32_t* s_status = sc.take<int32_t>(B);
+  int32_t* s_iters = sc.take<int32_t>(B);
+  int32_t* s_seg = sc.take<int32_t>(B);
   const ReachPathArgs rp{{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
                           err_final, dist_final},
                          W, x_path, xdot_path, waypoints_reached, dist_min, steps_at, s_xt, s_xdt, s_seg};
   if (persistent) {
-    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
-    const int64_t grid = B < cap ? B : cap;
-    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
-    IO io{B, 0, B, q0, qdot0, x_path, xdot_path, nullptr, nullptr, eta, s_status, s_iters, nullptr, nullptr, nullptr,
-          nullptr, nullptr, nullptr, nullptr, 0};
-    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
-    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
-    HIP_TRY(static_cast<hipError_t>(
-        slots ? launch_reach_path_obstacle_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rp, *ob)
-              : launch_reach_path_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rp)));
+    IO io{B, 0, B, q0, qdot0, x_path, xdot_path, nullptr, nullptr, eta, s_status, s_iters};
+    unsigned grid;
+    if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
+    HIP_TRY(static_cast<hipError_t>(slots ? launch_reach_path_obstacle_kernel(grid, st, m->d_model, kt, kq, io, rp, *ob)
+                                          : launch_reach_path_kernel(grid, st, m->d_model, kt, kq, io, rp)));
     done_guard.ok = true;
     return DRC_OK;
   }
-  // the finals carry the state from the start; every instance active, at
-  // waypoint 0 with no step taken
-  const size_t state_bytes = size_t(nv) * B * 8;
-  if (qf != q0) HIP_TRY(hipMemcpyAsync(qf, q0, state_bytes, hipMemcpyDeviceToDevice, st));
-  if (vf != qdot0) HIP_TRY(hipMemcpyAsync(vf, qdot0, state_bytes, hipMemcpyDeviceToDevice, st));
+  // reach()'s start, at waypoint 0 with no step taken
+  if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, rp.re)) return r;
   HIP_TRY(hipMemcpyAsync(s_xt, x_path, size_t(12) * B * 8, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(s_xdt, xdot_path, size_t(6) * B * 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemsetAsync(result, 0xff, size_t(B) * 4, st));  // kReachActive
   HIP_TRY(hipMemsetAsync(waypoints_reached, 0, size_t(B) * 4, st));
   HIP_TRY(hipMemsetAsync(steps_used, 0, size_t(B) * 4, st));
   HIP_TRY(hipMemsetAsync(s_seg, 0, size_t(B) * 4, st));
-  if (status_last) HIP_TRY(hipMemsetAsync(status_last, 0, size_t(B) * 4, st));
-  if (iters_total) HIP_TRY(hipMemsetAsync(iters_total, 0, size_t(B) * 4, st));
   if (steps_at) HIP_TRY(hipMemsetAsync(steps_at, 0xff, size_t(W) * B * 4, st));  // -1: never reached
   const int64_t rounds = int64_t(W) * (int64_t(max_steps) + 1);
   for (int64_t r = 0; r <= rounds; ++r) {
@@ -1426,19 +1452,12 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  const bool slots = m->hm.dev.nobst > 0;
-  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsReachSeedsMsg);
-  if (!slots && ob)
-    return set_err(DRC_ERR_INVALID_ARGUMENT,
-                   "the model has no obstacle slots (drc_model_set_obstacles declares them): "
-                   "drc_qpik_reach_seeds_batch runs it");
+  if (int rc = check_slots(m, ob, kSlotsReachSeedsMsg, "drc_qpik_reach_seeds_batch")) return rc;
   if (S < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "seeds must be at least 1");
   if (T < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative number of targets");
   if (rule != DRC_SEEDS_FIRST && rule != DRC_SEEDS_FEWEST_STEPS)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "rule is DRC_SEEDS_FIRST or DRC_SEEDS_FEWEST_STEPS");
-  if (ob && T > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < T)))
-    return set_err(DRC_ERR_INVALID_ARGUMENT,
-                   "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the number of targets");
+  if (int rc = check_obstacle_pose(ob, T, "the number of targets")) return rc;
   if (params->mode != DRC_MODE_QPIK_STEP)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_seeds_batch runs DRC_MODE_QPIK_STEP only");
   if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
@@ -1446,27 +1465,24 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
     return set_err(DRC_ERR_INVALID_ARGUMENT, "(max_steps + 1) * seeds must be below 2^31");  // the 32-bit keys
   if (T > 0x7ffffff0 / S)  // 32-bit work-queue counters
     return set_err(DRC_ERR_INVALID_ARGUMENT, "seeds * targets too large");
-  if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
-  if (!finite_positive(pos_tol) || !finite_positive(rot_tol))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "pos_tol and rot_tol must be finite and positive");
+  if (int rc = check_dt_tolerances(dt, pos_tol, rot_tol)) return rc;
   if (!seed || !result || !steps_used || !q_sol || !qdot_sol)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "seed, result, steps_used, q_sol and qdot_sol are required");
   if (T > 0 && (!q0 || !qdot0 || !xt || !xdt))
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_target and xdot_target are required");
   KParams kt, kq;
-  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
-  if (int rc = make_kparams(m, params, 0, &kq)) return rc;
+  if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (T == 0) return DRC_OK;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
+  const bool slots = dm.nobst > 0;
   const int64_t B = T * S;
   double tau[2];
   reach_thresholds(pos_tol, rot_tol, tau);
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = m->fused && m->lane_stage == 0 && B <= reach_max && kQpGroup == 64 &&
-                          qp_compiled(kq.nx, kq.ng, kq.np) && !dm.has_mesh;
+  const bool persistent = persistent_path(m, kq, B, reach_max, false, true);
   const bool ob_expand = ob && ob->ld != 0;
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
@@ -1475,34 +1491,29 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   // [nobst][12][B], (persistent) one step's eta [na][B]; then result, steps,
   // status_last, iters_total [B], (persistent) one step's status and iters [B]
   // and the groups' words [T]
-  const int64_t n_dbl = int64_t(12 + 6 + 2 * nv + 2 + 1 + nv + (ob_expand ? dm.nobst * 12 : 0) + (persistent ? na : 0)) * B;
+  const int64_t n_pose = ob_expand ? int64_t(dm.nobst) * 12 * B : 0;
+  const int64_t n_dbl = int64_t(12 + 6 + 2 * nv + 2 + 1 + nv + (persistent ? na : 0)) * B + n_pose;
   {
     std::lock_guard<std::mutex> g(m->mu);
     if (int r = stream_ctx(m, st, &cx)) return r;
-    const int64_t bytes = n_dbl * 8 + 6 * B * 4 + T * 4;
-    if (cx->seeds_bytes < bytes) {
-      if (cx->seeds) HIP_TRY(hipFree(cx->seeds));  // synchronises: no launch still uses it
-      cx->seeds = nullptr;
-      cx->seeds_bytes = 0;
-      HIP_TRY(hipMalloc(&cx->seeds, bytes));
-      cx->seeds_bytes = bytes;
-    }
+    if (int r = grow_scratch(&cx->seeds, &cx->seeds_bytes, n_dbl * 8 + 6 * B * 4 + T * 4)) return r;
   }
-  double* s_xt = static_cast<double*>(cx->seeds);
-  double* s_xdt = s_xt + 12 * B;
-  double* s_qf = s_xdt + 6 * B;
-  double* s_vf = s_qf + int64_t(nv) * B;
-  double* s_err = s_vf + int64_t(nv) * B;
-  double* s_dist = s_err + 2 * B;
-  double* s_pose = s_dist + int64_t(1 + nv) * B;
-  double* s_eta = s_pose + (ob_expand ? int64_t(dm.nobst) * 12 * B : 0);
-  int32_t* s_res = reinterpret_cast<int32_t*>(s_xt + n_dbl);
-  int32_t* s_steps = s_res + B;
-  int32_t* s_stl = s_steps + B;
-  int32_t* s_its = s_stl + B;
-  int32_t* s_status = s_its + B;
-  int32_t* s_iters = s_status + B;
-  uint32_t* s_word = reinterpret_cast<uint32_t*>(s_iters + B);
+  Carver sc{static_cast<char*>(cx->seeds)};
+  double* s_xt = sc.take<double>(12 * B);
+  double* s_xdt = sc.take<double>(6 * B);
+  double* s_qf = sc.take<double>(int64_t(nv) * B);
+  double* s_vf = sc.take<double>(int64_t(nv) * B);
+  double* s_err = sc.take<double>(2 * B);
+  double* s_dist = sc.take<double>(int64_t(1 + nv) * B);
+  double* s_pose = sc.take<double>(n_pose);
+  double* s_eta = sc.take<double>(persistent ? int64_t(na) * B : 0);
+  int32_t* s_res = sc.take<int32_t>(B);
+  int32_t* s_steps = sc.take<int32_t>(B);
+  int32_t* s_stl = sc.take<int32_t>(B);
+  int32_t* s_its = sc.take<int32_t>(B);
+  int32_t* s_status = sc.take<int32_t>(B);
+  int32_t* s_iters = sc.take<int32_t>(B);
+  uint32_t* s_word = sc.take<uint32_t>(T);
   HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 12, T, S, xt, T, s_xt)));
   HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 6, T, S, xdt, T, s_xdt)));
   Obst obe{nullptr, 0};
@@ -1518,17 +1529,12 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
                           T, S, rule, persistent && cancel ? 1 : 0, s_word};
   const ReachArgs& re = rs.re;
   if (persistent) {
-    static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
-    const int64_t grid = B < cap ? B : cap;
-    kt.xcd_map = kq.xcd_map = B >= 16384 ? 1 : 0;
-    IO io{B, 0, B, q0, qdot0, s_xt, s_xdt, nullptr, nullptr, s_eta, s_status, s_iters, nullptr, nullptr, nullptr,
-          nullptr, nullptr, nullptr, nullptr, 0};
-    io.queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
-    HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+    IO io{B, 0, B, q0, qdot0, s_xt, s_xdt, nullptr, nullptr, s_eta, s_status, s_iters};
+    unsigned grid;
+    if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(hipMemsetAsync(s_word, 0xff, size_t(T) * 4, st));  // kSeedsNoKey
-    HIP_TRY(static_cast<hipError_t>(
-        slots ? launch_reach_seeds_obstacle_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rs, obe)
-              : launch_reach_seeds_kernel(static_cast<unsigned>(grid), st, m->d_model, kt, kq, io, rs)));
+    HIP_TRY(static_cast<hipError_t>(slots ? launch_reach_seeds_obstacle_kernel(grid, st, m->d_model, kt, kq, io, rs, obe)
+                                          : launch_reach_seeds_kernel(grid, st, m->d_model, kt, kq, io, rs)));
   } else {
     if (int rc = reach_locked(m, params, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, s_xt, s_xdt, re.qf, re.vf,
                               re.result, re.steps_used, re.status_last, re.iters_total, re.err_final, re.dist_final,

@@ -58,20 +58,14 @@ fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
   }
 }
 
-template <bool MESH>
+template <bool MESH, class... OB>
 static int launch_fused(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
-                        const KParams& kq, const IO& io) {
+                        const KParams& kq, const IO& io, const OB&... ob) {
   const dim3 g(grid), blk(64);
-  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
-    hipLaunchKernelGGL((fused_kernel<Dims<23, 16, 7, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
-  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
-    hipLaunchKernelGGL((fused_kernel<Dims<20, 14, 6, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
-  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
-    hipLaunchKernelGGL((fused_kernel<Dims<9, 16, 9, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
-  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
-    hipLaunchKernelGGL((fused_kernel<Dims<11, 16, 11, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io);
-  else
-    return hipErrorInvalidValue;  // not a compiled shape: the two-kernel pipeline runs it
+  if (int r = with_compiled_shape(kq.nx, kq.ng, kq.np, [&](auto qd) {
+        hipLaunchKernelGGL((fused_kernel<decltype(qd), MESH, OB...>), g, blk, lds, st, m, kt, kq, io, ob...);
+      }))
+    return r;  // not a compiled shape: the two-kernel pipeline runs it
   return hipGetLastError();
 }
 
@@ -82,18 +76,7 @@ static int launch_fused(unsigned grid, size_t lds, hipStream_t st, const DevMode
 #if defined(DRC_FUSED_OBST)
 int launch_fused_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                                  const KParams& kq, const IO& io, const ObstIn& ob) {
-  const dim3 g(grid), blk(64);
-  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // the compiled shapes of launch_fused
-    hipLaunchKernelGGL((fused_kernel<Dims<23, 16, 7, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
-  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)
-    hipLaunchKernelGGL((fused_kernel<Dims<20, 14, 6, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
-  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)
-    hipLaunchKernelGGL((fused_kernel<Dims<9, 16, 9, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
-  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)
-    hipLaunchKernelGGL((fused_kernel<Dims<11, 16, 11, true, true, 64>, false, ObstIn>), g, blk, lds, st, m, kt, kq, io, ob);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return launch_fused<false>(grid, lds, st, m, kt, kq, io, ob);
 }
 #elif defined(DRC_FUSED_MESH)
 int launch_fused_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,

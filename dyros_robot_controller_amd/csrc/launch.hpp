@@ -21,7 +21,24 @@ int qp_waves_per_simd();
 // lane-per-instance task stage (nv = 6 or 7)
 int launch_lane_task_kernel(int nv, unsigned grid, hipStream_t st, const DevModel* m, const KParams& kp,
                             const IO& io);
-// QPIK shapes with a compile-time qp_kernel instantiation (register Schur ADMM)
+// The QPIK shapes with compile-time instantiations (register Schur ADMM), once:
+// calls f with the shape's Dims<..., gs = GS> tag, or returns
+// hipErrorInvalidValue for any other shape without calling it.  Every launcher
+// of a compiled kernel dispatches through it, and qp_compiled() asks it
+template <int GS = 64, class F>
+int with_compiled_shape(int nx, int ng, int np, F&& f) {
+  if (nx == 23 && ng == 16 && np == 7)  // FR3
+    f(Dims<23, 16, 7, true, true, GS>{});
+  else if (nx == 20 && ng == 14 && np == 6)  // UR5e
+    f(Dims<20, 14, 6, true, true, GS>{});
+  else if (nx == 9 && ng == 16 && np == 9)  // Husky-FR3
+    f(Dims<9, 16, 9, true, true, GS>{});
+  else if (nx == 11 && ng == 16 && np == 11)  // XLS-FR3
+    f(Dims<11, 16, 11, true, true, GS>{});
+  else
+    return hipErrorInvalidValue;
+  return hipSuccess;
+}
 bool qp_compiled(int nx, int ng, int np);
 // qp_kernel for kp's shape; lds = one lane group's plan
 int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io);

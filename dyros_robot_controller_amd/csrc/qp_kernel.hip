@@ -57,8 +57,7 @@ qp_kernel(const DevModel* __restrict__ M0, const KParams kp, const IO io) {
 
 #ifndef DRC_QP_DENSE_UNIT
 bool qp_compiled(int nx, int ng, int np) {
-  return (nx == 23 && ng == 16 && np == 7) || (nx == 20 && ng == 14 && np == 6) || (nx == 9 && ng == 16 && np == 9) ||
-         (nx == 11 && ng == 16 && np == 11);
+  return with_compiled_shape(nx, ng, np, [](auto) {}) == hipSuccess;
 }
 
 int qp_waves_per_simd() { return DRC_QP_WAVES; }
@@ -69,15 +68,9 @@ int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* 
   // QPIK only: the manipulator shapes' G pattern (kQpikSparse) is qp_assemble's.  The fused, rollout and reach
   // launchers take the same shapes and are QPIK entry points by construction (QPID has qpid_kernel.hip)
   if (kp.problem != 0) return hipErrorInvalidValue;
-  if (kp.nx == 23 && kp.ng == 16 && kp.np == 7)  // FR3
-    hipLaunchKernelGGL((qp_kernel<Dims<23, 16, 7, true, true, kQpGroup>>), g, blk, lg, st, m, kp, io);
-  else if (kp.nx == 20 && kp.ng == 14 && kp.np == 6)  // UR5e
-    hipLaunchKernelGGL((qp_kernel<Dims<20, 14, 6, true, true, kQpGroup>>), g, blk, lg, st, m, kp, io);
-  else if (kp.nx == 9 && kp.ng == 16 && kp.np == 9)  // Husky-FR3
-    hipLaunchKernelGGL((qp_kernel<Dims<9, 16, 9, true, true, kQpGroup>>), g, blk, lg, st, m, kp, io);
-  else if (kp.nx == 11 && kp.ng == 16 && kp.np == 11)  // XLS-FR3
-    hipLaunchKernelGGL((qp_kernel<Dims<11, 16, 11, true, true, kQpGroup>>), g, blk, lg, st, m, kp, io);
-  else  // any other model: runtime-sized shapes
+  if (with_compiled_shape<kQpGroup>(kp.nx, kp.ng, kp.np, [&](auto qd) {
+        hipLaunchKernelGGL((qp_kernel<decltype(qd)>), g, blk, lg, st, m, kp, io);
+      }))  // any other model: runtime-sized shapes
     hipLaunchKernelGGL((qp_kernel<Dims<0, 0, 0>>), g, blk, lds, st, m, kp, io);
   return hipGetLastError();
 }

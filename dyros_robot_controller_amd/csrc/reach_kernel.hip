@@ -5,25 +5,26 @@
 // would stay where it is for the rest of a fixed horizon).  Reference: no
 // counterpart.
 //
-// reach_kernel: the persistent form for the compiled QP shapes, shaped like
-// rollout_kernel (rollout_kernel.hip): one instance per wave from the work
-// queue, the task record in LDS, the state in the caller's q_final /
-// qdot_final arrays.  The verdict is wave-uniform, so the three stops are
-// uniform branches that leave the step loop, and the wave takes the next
-// instance from the queue: an instance costs the steps it needs, not the
-// horizon.
+// reach_kernel: the persistent form for the compiled QP shapes: one instance
+// per wave from the work queue, the task record in LDS, the state in the
+// caller's q_final / qdot_final arrays.  The verdict is wave-uniform, so the
+// three stops are uniform branches that leave the step loop, and the wave takes
+// the next instance from the queue: an instance costs the steps it needs, not
+// the horizon.  Its own here: the step loop with the three stops; the blocks
+// between them -- LDS views, the stores at the state, status read-back, state
+// update, epilogue -- are closed_loop.hpp's, which reach_seeds_kernel calls too
+// (rollout_kernel and reach_path_kernel keep the same blocks as their own text;
+// only their update kernels and launchers use the header).
 //
 // reach_update_kernel: verdict and state update alone, one thread per
 // instance, for the stepwise path (api.cpp: the stage launch and
 // drc_qpik_batch's launch sequence per step, then this kernel).  Both forms
-// call reach_error / reach_within (reach.hpp) and rollout_velocity /
-// rollout_advance (rollout_update.hpp) on the same values, so the two paths
-// return identical bits (tests/test_gpu_reach.py).
+// go through the same functions of closed_loop.hpp (reach.hpp's and
+// rollout_update.hpp's arithmetic) on the same values, so the two paths return
+// identical bits (tests/test_gpu_reach.py).
 #include "task_stage.hpp"
 #include "qp_solver.hpp"
-#include "launch.hpp"
-#include "reach.hpp"
-#include "rollout_update.hpp"
+#include "closed_loop.hpp"
 
 namespace drc_amd {
 
@@ -34,8 +35,7 @@ namespace drc_amd {
 // skipped; an active one takes step k's verdict from the stage outputs at
 // (q_k, v_k) -- pose [12][B], dist [1+nv][B] -- and, unless it stops, the
 // update from that step's eta / status / iters.  last: k = max_steps, no QP ran.
-// The state is updated in place: the yaw and the wheel positions are read
-// before any row is written, and row r is read before it is written.
+// The state is updated in place (thread_state_update).
 __global__ void __launch_bounds__(256)
 reach_update_kernel(const DevModel* __restrict__ M, int64_t B, int k, int last, const ReachArgs re, const double* xt,
                     const double* pose, const double* dist, const double* eta, const int32_t* status,
@@ -54,46 +54,18 @@ reach_update_kernel(const DevModel* __restrict__ M, int64_t B, int k, int last, 
     res = DRC_REACH_REACHED;
   } else if (last) {
     res = DRC_REACH_BUDGET;
-  } else {
-    const int st = status[b];
-    if (re.status_last) re.status_last[b] = st;
-    if (re.iters_total) re.iters_total[b] += iters[b];
-    if (st != DRC_STATUS_SOLVED) res = DRC_REACH_QP_FAILED;
+  } else if (thread_step_status(re, b, status, iters) != DRC_STATUS_SOLVED) {
+    res = DRC_REACH_QP_FAILED;
   }
-  if (res != kReachActive) {  // stopped at (q_k, v_k): the finals hold it
+  if (res != kReachActive) {  // stopped at (q_k, v_k)
     re.result[b] = res;
     re.steps_used[b] = k;
-    if (re.err_final) {
-      re.err_final[b] = err[0];
-      re.err_final[B + b] = err[1];
-    }
-    if (re.dist_final)
-      for (int i = 0; i <= M->nv; ++i) re.dist_final[i * B + b] = dist[i * B + b];
+    thread_store_at_state(M, re, B, b, err, dist);
     return;
   }
-  double Jm[3][kMaxWheels];
-  double cy = 1, sy = 0;
-  if (M->kind == 1) {
-    double wp[kMaxWheels];
-    for (int w = 0; w < kMaxWheels; ++w) wp[w] = w < M->n_wheel ? re.qf[(M->mobi_start + w) * B + b] : 0.0;
-    mobile_fk(M, wp, Jm);
-    const double yaw = re.qf[(M->virtual_start + 2) * B + b];
-    cy = cos(yaw);
-    sy = sin(yaw);
-  }
-  const auto e = [&](int a) { return eta[a * B + b]; };
-  for (int r = 0; r < M->nv; ++r) {
-    const double q = re.qf[r * B + b];
-    const double v = rollout_velocity(M, r, cy, sy, Jm, e);
-    const double qn = rollout_advance(q, re.dt, v);
-    re.vf[r * B + b] = v;
-    re.qf[r * B + b] = qn;
-  }
+  thread_state_update(M, B, b, re.dt, re.qf, eta, re.qf, re.vf);
 }
 
-#ifndef DRC_FUSED_WAVES
-#define DRC_FUSED_WAVES 2
-#endif
 template <class QD>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
 reach_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io, const ReachArgs re) {
@@ -111,12 +83,7 @@ reach_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
   const int l = lane_id();
   const int64_t B = io.B, LD = io.ld;
   const int nv = kt.nv, na = kq.na;
-  IO iol = io;  // the record lives in LDS, as in fused_kernel
-  iol.rec = S + fused_rec_offset(kt, kq);
-  iol.rec_stride = 0;
-  double* qs = S;  // (rollout_state_doubles: dead plan space)
-  double* es = qs + ((nv + 1) & ~1);
-  double(*Jm)[kMaxWheels] = reinterpret_cast<double(*)[kMaxWheels]>(es + ((na + 1) & ~1));
+  const ClosedLoopLds cl(io, S, kt, kq);
   const InstSeq seq(B, kq.xcd_map, io.queue);
   for (int64_t j = seq.first(); j < seq.n; j = seq.next(j)) {
     const int64_t b = seq.at(j);
@@ -124,11 +91,7 @@ reach_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     const int64_t gb = io.b0 + b;
     int k = 0, res = DRC_REACH_BUDGET, st_last = 0, it_total = 0;
     for (;;) {
-      IO is = iol;
-      if (k > 0) {
-        is.q = re.qf;
-        is.qdot = re.vf;
-      }
+      IO is = step_io(cl.io, k, re.qf, re.vf);
       task_instance<0, false>(M0, kt, is, S, b);
       wsync();
       // the pose at q_k from the task plan (the pure copies of the stage entry's
@@ -138,15 +101,12 @@ reach_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
         const double* Te = S + kt.kTe;
         double ps[12], tg[12];
         for (int i = 0; i < 12; ++i) {
-          ps[i] = i < 9 ? Te[(i % 3) * 3 + i / 3] : Te[i];
+          ps[i] = plan_pose(Te, i);
           tg[i] = io.xt[i * LD + gb];
         }
         reach_error(ps, tg, err);
       }
-      // what stands there when the instance stops is the value at q_final (a
-      // QP that fails leaves the state where this stage ran)
-      if (re.err_final && l < 2) re.err_final[l * LD + gb] = l ? err[1] : err[0];
-      if (re.dist_final && l <= nv) re.dist_final[l * LD + gb] = iol.rec[kt.rDist + l];
+      store_at_state(re, cl.io.rec + kt.rDist, gb, LD, l, nv, err);
       const int within = __builtin_amdgcn_readfirstlane(reach_within(err, re.tau_p, re.tau_r) ? 1 : 0);
       if (within) {
         res = DRC_REACH_REACHED;
@@ -158,71 +118,28 @@ reach_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
       }
       wsync();
       qp_instance<QD>(M0, kq, kpl, is, S, b);
-      // ---------------- this step's status, wave-uniform ----------------------
-      state_visible();
-      st_last = __builtin_amdgcn_readfirstlane(
-          __hip_atomic_load(is.status + gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      it_total += __builtin_amdgcn_readfirstlane(
-          __hip_atomic_load(is.iters + gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      step_status(is, gb, st_last, it_total);
       if (st_last != DRC_STATUS_SOLVED) {
         res = DRC_REACH_QP_FAILED;
         break;
       }
-      // ---------------- state update (as rollout_kernel) ----------------------
-      const double qk = l < nv ? is.q[l * LD + gb] : 0.0;  // step 0: the caller's q0 (q_final may alias it)
-      if (l < nv) qs[l] = qk;
-      if (l < na) es[l] = is.out[l * LD + gb];
-      wsync();
-      const DevModel* M = opaque_model(M0);
-      double cy = 1, sy = 0;
-      if (M->kind == 1) {
-        if (l == 0) mobile_fk(M, qs + M->mobi_start, Jm);
-        const double yaw = qs[M->virtual_start + 2];
-        cy = cos(yaw);
-        sy = sin(yaw);
-        wsync();
-      }
-      if (l < nv) {
-        const double v = rollout_velocity(M, l, cy, sy, Jm, [&](int a) { return es[a]; });
-        const double qn = rollout_advance(qk, re.dt, v);
-        re.vf[l * LD + gb] = v;
-        re.qf[l * LD + gb] = qn;
-      }
-      state_visible();
-      wsync();
+      wave_state_update(M0, is, gb, LD, l, nv, na, re.dt, re.qf, re.vf, cl);
       ++k;
     }
-    // stopped at (q_k, v_k): from step 1 on the finals hold it
-    if (k == 0 && l < nv) {
-      const double q0 = io.q[l * LD + gb], v0 = io.qdot[l * LD + gb];
-      re.qf[l * LD + gb] = q0;
-      re.vf[l * LD + gb] = v0;
-    }
-    if (l == 0) {
-      re.result[gb] = res;
-      re.steps_used[gb] = k;
-      if (re.status_last) re.status_last[gb] = st_last;
-      if (re.iters_total) re.iters_total[gb] = it_total;
-    }
+    reach_finals(io, re, gb, LD, l, nv, k);
+    if (l == 0) reach_outcome(re, gb, k, res, st_last, it_total);
     wsync();
   }
 }
 
 int launch_reach_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
                         const IO& io, const ReachArgs& re) {
-  const int plan = fused_lds_doubles(kt, kq), state = rollout_state_doubles(kt, kq);
-  const size_t lds = static_cast<size_t>(plan > state ? plan : state) * sizeof(double);
+  const size_t lds = closed_loop_lds_bytes(kt, kq);
   const dim3 g(grid), blk(64);
-  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
-    hipLaunchKernelGGL((reach_kernel<Dims<23, 16, 7, true, true, 64>>), g, blk, lds, st, m, kt, kq, io, re);
-  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
-    hipLaunchKernelGGL((reach_kernel<Dims<20, 14, 6, true, true, 64>>), g, blk, lds, st, m, kt, kq, io, re);
-  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
-    hipLaunchKernelGGL((reach_kernel<Dims<9, 16, 9, true, true, 64>>), g, blk, lds, st, m, kt, kq, io, re);
-  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
-    hipLaunchKernelGGL((reach_kernel<Dims<11, 16, 11, true, true, 64>>), g, blk, lds, st, m, kt, kq, io, re);
-  else
-    return hipErrorInvalidValue;  // not a compiled shape: the stepwise path runs it
+  if (int r = with_compiled_shape(kq.nx, kq.ng, kq.np, [&](auto qd) {
+        hipLaunchKernelGGL((reach_kernel<decltype(qd)>), g, blk, lds, st, m, kt, kq, io, re);
+      }))
+    return r;  // not a compiled shape: the stepwise path runs it
   return hipGetLastError();
 }
 

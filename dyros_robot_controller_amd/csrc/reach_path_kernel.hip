@@ -6,30 +6,30 @@
 // drc_qpik_reach_batch calls, without the call boundaries: a wave leaves an
 // instance the moment it stops.  Reference: no counterpart.
 //
-// reach_path_kernel: the persistent form for the compiled QP shapes, shaped
-// like reach_kernel: one instance per wave from the work queue, the task record
-// in LDS, the state in the caller's q_final / qdot_final arrays, the update
-// scratch at the start of the plan.  The waypoint index, both step counters and
-// the verdict are wave-uniform, so the stops and the waypoint advance are
-// uniform branches.  OB: empty, or one ObstIn -- the build for models with
+// reach_path_kernel: the persistent form for the compiled QP shapes: one
+// instance per wave from the work queue, the task record in LDS, the state in
+// the caller's q_final / qdot_final arrays, the update scratch at the start of
+// the plan.  The waypoint index, both step counters and the verdict are
+// wave-uniform, so the stops and the waypoint advance are uniform branches.
+// The kernel body is written out in full, the blocks of closed_loop.hpp
+// included (the same text as there): through the header's functions, with
+// equal registers, scratch and spills, the FR3 build measured 1.3 to 1.8 %
+// slower than it was (profiles/closed_loop_refactor_ab.jsonl), so this kernel
+// keeps the text it had.  OB: empty, or one ObstIn -- the build for models with
 // obstacle slots (reach_path_obstacle_kernel.hip), as fused_kernel's.
 //
 // reach_path_update_kernel: verdict, advance and state update alone, one
-// thread per instance, for the stepwise path (api.cpp).  Both forms call
-// reach_error / reach_within (reach.hpp) and rollout_velocity /
-// rollout_advance (rollout_update.hpp) on the same values, so the two paths
-// return identical bits (tests/test_gpu_reach_path.py).
+// thread per instance, for the stepwise path (api.cpp).  Both forms go through
+// the same functions of closed_loop.hpp (reach.hpp's and rollout_update.hpp's
+// arithmetic) on the same values, so the two paths return identical bits
+// (tests/test_gpu_reach_path.py).
 #include "task_stage.hpp"
 #include "qp_solver.hpp"
-#include "reach.hpp"
 #include "reach_path.hpp"
-#include "rollout_update.hpp"
+#include "closed_loop.hpp"
 
 namespace drc_amd {
 
-#ifndef DRC_FUSED_WAVES
-#define DRC_FUSED_WAVES 2
-#endif
 template <class QD, class... OB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
 reach_path_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io,
@@ -175,24 +175,12 @@ reach_path_kernel(const DevModel* __restrict__ M0, const KParams kt, const KPara
 template <class... OB>
 static int launch_shapes(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
                          const IO& io, const ReachPathArgs& rp, const OB&... ob) {
-  // the update scratch lies in the plan: fused_lds_doubles for every compiled shape
-  const int plan = fused_lds_doubles(kt, kq), state = rollout_state_doubles(kt, kq);
-  const size_t lds = static_cast<size_t>(plan > state ? plan : state) * sizeof(double);
+  const size_t lds = closed_loop_lds_bytes(kt, kq);
   const dim3 g(grid), blk(64);
-  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
-    hipLaunchKernelGGL((reach_path_kernel<Dims<23, 16, 7, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io, rp,
-                       ob...);
-  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
-    hipLaunchKernelGGL((reach_path_kernel<Dims<20, 14, 6, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io, rp,
-                       ob...);
-  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
-    hipLaunchKernelGGL((reach_path_kernel<Dims<9, 16, 9, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io, rp,
-                       ob...);
-  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
-    hipLaunchKernelGGL((reach_path_kernel<Dims<11, 16, 11, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io, rp,
-                       ob...);
-  else
-    return hipErrorInvalidValue;  // not a compiled shape: the stepwise path runs it
+  if (int r = with_compiled_shape(kq.nx, kq.ng, kq.np, [&](auto qd) {
+        hipLaunchKernelGGL((reach_path_kernel<decltype(qd), OB...>), g, blk, lds, st, m, kt, kq, io, rp, ob...);
+      }))
+    return r;  // not a compiled shape: the stepwise path runs it
   return hipGetLastError();
 }
 
@@ -259,40 +247,15 @@ reach_path_update_kernel(const DevModel* __restrict__ M, int64_t B, int first, i
     return;
   } else if (rp.seg[b] == re.max_steps || last) {
     res = DRC_REACH_BUDGET;
-  } else {
-    const int st = status[b];
-    if (re.status_last) re.status_last[b] = st;
-    if (re.iters_total) re.iters_total[b] += iters[b];
-    if (st != DRC_STATUS_SOLVED) res = DRC_REACH_QP_FAILED;
+  } else if (thread_step_status(re, b, status, iters) != DRC_STATUS_SOLVED) {
+    res = DRC_REACH_QP_FAILED;
   }
-  if (res != kReachActive) {  // stopped at (q_k, v_k): the finals hold it
+  if (res != kReachActive) {  // stopped at (q_k, v_k); steps_used holds k
     re.result[b] = res;
-    if (re.err_final) {
-      re.err_final[b] = err[0];
-      re.err_final[B + b] = err[1];
-    }
-    if (re.dist_final)
-      for (int i = 0; i <= M->nv; ++i) re.dist_final[i * B + b] = dist[i * B + b];
+    thread_store_at_state(M, re, B, b, err, dist);
     return;
   }
-  double Jm[3][kMaxWheels];
-  double cy = 1, sy = 0;
-  if (M->kind == 1) {
-    double wp[kMaxWheels];
-    for (int c = 0; c < kMaxWheels; ++c) wp[c] = c < M->n_wheel ? re.qf[(M->mobi_start + c) * B + b] : 0.0;
-    mobile_fk(M, wp, Jm);
-    const double yaw = re.qf[(M->virtual_start + 2) * B + b];
-    cy = cos(yaw);
-    sy = sin(yaw);
-  }
-  const auto e = [&](int a) { return eta[a * B + b]; };
-  for (int r = 0; r < M->nv; ++r) {
-    const double q = re.qf[r * B + b];
-    const double v = rollout_velocity(M, r, cy, sy, Jm, e);
-    const double qn = rollout_advance(q, re.dt, v);
-    re.vf[r * B + b] = v;
-    re.qf[r * B + b] = qn;
-  }
+  thread_state_update(M, B, b, re.dt, re.qf, eta, re.qf, re.vf);
   re.steps_used[b] = k + 1;
   rp.seg[b] += 1;
 }

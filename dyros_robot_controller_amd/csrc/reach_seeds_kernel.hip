@@ -3,10 +3,11 @@
 // at column s T + t, of which the select kernel returns one per target by the
 // rule of reach_seeds.hpp.  Reference: no counterpart.
 //
-// reach_seeds_kernel: the persistent form for the compiled QP shapes, shaped
-// like reach_kernel: one instance per wave from the work queue, the task record
-// in LDS, the state in the (scratch) q_final / qdot_final arrays, the update
-// scratch at the start of the plan.  New is one 32-bit word per group.  A wave
+// reach_seeds_kernel: the persistent form for the compiled QP shapes: one
+// instance per wave from the work queue, the task record in LDS, the state in
+// the (scratch) q_final / qdot_final arrays, the update scratch at the start of
+// the plan; the blocks it has in common with reach_kernel are closed_loop.hpp's.
+// Its own here is the step loop with one 32-bit word per group.  A wave
 // whose instance is REACHED publishes its key with an atomic min (lane 0); a
 // wave whose verdict failed loads the word (relaxed, agent scope, made uniform)
 // and leaves the instance on a uniform branch if seeds_cancelled says so.  No
@@ -24,15 +25,11 @@
 // (tests/test_gpu_reach_seeds.py).
 #include "task_stage.hpp"
 #include "qp_solver.hpp"
-#include "reach.hpp"
 #include "reach_seeds.hpp"
-#include "rollout_update.hpp"
+#include "closed_loop.hpp"
 
 namespace drc_amd {
 
-#ifndef DRC_FUSED_WAVES
-#define DRC_FUSED_WAVES 2
-#endif
 template <class QD, class... OB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
 reach_seeds_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io,
@@ -53,12 +50,7 @@ reach_seeds_kernel(const DevModel* __restrict__ M0, const KParams kt, const KPar
   const int l = lane_id();
   const int64_t B = io.B, LD = io.ld;
   const int nv = kt.nv, na = kq.na;
-  IO iol = io;  // the record lives in LDS, as in fused_kernel
-  iol.rec = S + fused_rec_offset(kt, kq);
-  iol.rec_stride = 0;
-  double* qs = S;  // (rollout_state_doubles: dead plan space)
-  double* es = qs + ((nv + 1) & ~1);
-  double(*Jm)[kMaxWheels] = reinterpret_cast<double(*)[kMaxWheels]>(es + ((na + 1) & ~1));
+  const ClosedLoopLds cl(io, S, kt, kq);
   const InstSeq seq(B, kq.xcd_map, io.queue);
   for (int64_t j = seq.first(); j < seq.n; j = seq.next(j)) {
     const int64_t b = seq.at(j);
@@ -68,11 +60,7 @@ reach_seeds_kernel(const DevModel* __restrict__ M0, const KParams kt, const KPar
     uint32_t* word = rs.word + (gb - sd * rs.T);
     int k = 0, res = DRC_REACH_BUDGET, st_last = 0, it_total = 0;
     for (;;) {
-      IO is = iol;
-      if (k > 0) {
-        is.q = re.qf;
-        is.qdot = re.vf;
-      }
+      IO is = step_io(cl.io, k, re.qf, re.vf);
       task_instance<0, false, sizeof...(OB) != 0>(M0, kt, is, S, b, ob...);
       wsync();
       // the pose at q_k from the task plan against the target (reach_kernel)
@@ -81,13 +69,12 @@ reach_seeds_kernel(const DevModel* __restrict__ M0, const KParams kt, const KPar
         const double* Te = S + kt.kTe;
         double ps[12], tg[12];
         for (int i = 0; i < 12; ++i) {
-          ps[i] = i < 9 ? Te[(i % 3) * 3 + i / 3] : Te[i];
+          ps[i] = plan_pose(Te, i);
           tg[i] = io.xt[i * LD + gb];
         }
         reach_error(ps, tg, err);
       }
-      if (l < 2) re.err_final[l * LD + gb] = l ? err[1] : err[0];  // (the select kernel needs it)
-      if (re.dist_final && l <= nv) re.dist_final[l * LD + gb] = iol.rec[kt.rDist + l];
+      store_at_state(re, cl.io.rec + kt.rDist, gb, LD, l, nv, err);  // (err_final: scratch, the select kernel needs it)
       const int within = __builtin_amdgcn_readfirstlane(reach_within(err, re.tau_p, re.tau_r) ? 1 : 0);
       if (within) {
         if (rs.cancel && l == 0)
@@ -109,52 +96,16 @@ reach_seeds_kernel(const DevModel* __restrict__ M0, const KParams kt, const KPar
       }
       wsync();
       qp_instance<QD>(M0, kq, kpl, is, S, b);
-      // ---------------- this step's status, wave-uniform ----------------------
-      state_visible();
-      st_last = __builtin_amdgcn_readfirstlane(
-          __hip_atomic_load(is.status + gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      it_total += __builtin_amdgcn_readfirstlane(
-          __hip_atomic_load(is.iters + gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      step_status(is, gb, st_last, it_total);
       if (st_last != DRC_STATUS_SOLVED) {
         res = DRC_REACH_QP_FAILED;
         break;
       }
-      // ---------------- state update (as rollout_kernel) ----------------------
-      const double qk = l < nv ? is.q[l * LD + gb] : 0.0;
-      if (l < nv) qs[l] = qk;
-      if (l < na) es[l] = is.out[l * LD + gb];
-      wsync();
-      const DevModel* M = opaque_model(M0);
-      double cy = 1, sy = 0;
-      if (M->kind == 1) {
-        if (l == 0) mobile_fk(M, qs + M->mobi_start, Jm);
-        const double yaw = qs[M->virtual_start + 2];
-        cy = cos(yaw);
-        sy = sin(yaw);
-        wsync();
-      }
-      if (l < nv) {
-        const double v = rollout_velocity(M, l, cy, sy, Jm, [&](int a) { return es[a]; });
-        const double qn = rollout_advance(qk, re.dt, v);
-        re.vf[l * LD + gb] = v;
-        re.qf[l * LD + gb] = qn;
-      }
-      state_visible();
-      wsync();
+      wave_state_update(M0, is, gb, LD, l, nv, na, re.dt, re.qf, re.vf, cl);
       ++k;
     }
-    // stopped at (q_k, v_k): from step 1 on the finals hold it
-    if (k == 0 && l < nv) {
-      const double q0 = io.q[l * LD + gb], v0 = io.qdot[l * LD + gb];
-      re.qf[l * LD + gb] = q0;
-      re.vf[l * LD + gb] = v0;
-    }
-    if (l == 0) {
-      re.result[gb] = res;
-      re.steps_used[gb] = k;
-      if (re.status_last) re.status_last[gb] = st_last;
-      if (re.iters_total) re.iters_total[gb] = it_total;
-    }
+    reach_finals(io, re, gb, LD, l, nv, k);
+    if (l == 0) reach_outcome(re, gb, k, res, st_last, it_total);
     wsync();
   }
 }
@@ -163,23 +114,12 @@ template <class... OB>
 static int launch_shapes(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
                          const IO& io, const ReachSeedsArgs& rs, const OB&... ob) {
   // the update scratch lies in the plan: fused_lds_doubles for every compiled shape
-  const int plan = fused_lds_doubles(kt, kq), state = rollout_state_doubles(kt, kq);
-  const size_t lds = static_cast<size_t>(plan > state ? plan : state) * sizeof(double);
+  const size_t lds = closed_loop_lds_bytes(kt, kq);
   const dim3 g(grid), blk(64);
-  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
-    hipLaunchKernelGGL((reach_seeds_kernel<Dims<23, 16, 7, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io,
-                       rs, ob...);
-  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
-    hipLaunchKernelGGL((reach_seeds_kernel<Dims<20, 14, 6, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io,
-                       rs, ob...);
-  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
-    hipLaunchKernelGGL((reach_seeds_kernel<Dims<9, 16, 9, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io, rs,
-                       ob...);
-  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
-    hipLaunchKernelGGL((reach_seeds_kernel<Dims<11, 16, 11, true, true, 64>, OB...>), g, blk, lds, st, m, kt, kq, io,
-                       rs, ob...);
-  else
-    return hipErrorInvalidValue;  // not a compiled shape: the stepwise path runs it
+  if (int r = with_compiled_shape(kq.nx, kq.ng, kq.np, [&](auto qd) {
+        hipLaunchKernelGGL((reach_seeds_kernel<decltype(qd), OB...>), g, blk, lds, st, m, kt, kq, io, rs, ob...);
+      }))
+    return r;  // not a compiled shape: the stepwise path runs it
   return hipGetLastError();
 }
 

@@ -3,55 +3,41 @@
 // (examples/C++/src/fr3_controller.cpp:123-134) -- over a horizon of `steps`
 // cycles on the device.
 //
-// rollout_kernel: the persistent form for the compiled QP shapes, shaped like
-// fused_kernel.hip's kernel.  Each wave takes an instance from the work queue
-// and runs all its steps before the next: task stage (task_stage.hpp), QP
+// rollout_kernel: the persistent form for the compiled QP shapes.  Each wave
+// takes an instance from the work queue (as fused_kernel.hip's kernel) and runs
+// all its steps before the next: task stage (task_stage.hpp), QP
 // (qp_solver.hpp), state update.  The task record stays in LDS as in the fused
 // kernel; the state (q, v) lives in the caller's q_final / qdot_final arrays,
 // which task_instance reads through IO::q / IO::qdot from step 1 on: lane l
 // reads back the element lane l stored one step earlier (state_visible()).
 // Same device functions on the same values as drc_qpik_batch step by step, so
 // every step's result is bit-identical to it (tests/test_gpu_rollout.py).
+// The kernel body is written out in full, the blocks of closed_loop.hpp
+// included (LDS views, step IO, state update -- the same text as
+// wave_state_update): through the header's functions the hull build's FR3
+// instantiation came out with one more VGPR spill (56 to 57; UR5e's with one
+// fewer), in every form tried, so this kernel keeps the text it had
+// (profiles/closed_loop_refactor_resources.txt).
 //
 // rollout_integrate_kernel: the state update alone, one thread per instance,
 // for the stepwise path (api.cpp: drc_qpik_batch's launch sequence per step,
-// then this kernel).  Both forms call rollout_velocity / rollout_advance
-// (rollout_update.hpp), so the two paths return identical bits.
+// then this kernel): closed_loop.hpp's thread_state_update, on the arithmetic
+// of wave_state_update (rollout_update.hpp), so the two paths return identical
+// bits.
 #include "task_stage.hpp"
 #include "qp_solver.hpp"
-#include "launch.hpp"
-#include "rollout_update.hpp"
+#include "closed_loop.hpp"
 
 namespace drc_amd {
 
 #ifndef DRC_ROLLOUT_MESH
-// Stepwise path: one thread per instance.  q_in may be qf (in place): the yaw
-// and the wheel positions are read before any row is written, and row r is
-// read before it is written.
+// Stepwise path: one thread per instance.  q_in may be qf (in place)
 __global__ void __launch_bounds__(256)
 rollout_integrate_kernel(const DevModel* __restrict__ M, int64_t B, double dt, const double* q_in, const double* eta,
                          double* qf, double* vf, double* q_traj) {
   const int64_t b = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (b >= B) return;
-  double Jm[3][kMaxWheels];
-  double cy = 1, sy = 0;
-  if (M->kind == 1) {
-    double wp[kMaxWheels];
-    for (int w = 0; w < kMaxWheels; ++w) wp[w] = w < M->n_wheel ? q_in[(M->mobi_start + w) * B + b] : 0.0;
-    mobile_fk(M, wp, Jm);
-    const double yaw = q_in[(M->virtual_start + 2) * B + b];
-    cy = cos(yaw);
-    sy = sin(yaw);
-  }
-  const auto e = [&](int a) { return eta[a * B + b]; };
-  for (int r = 0; r < M->nv; ++r) {
-    const double q = q_in[r * B + b];
-    const double v = rollout_velocity(M, r, cy, sy, Jm, e);
-    const double qn = rollout_advance(q, dt, v);
-    vf[r * B + b] = v;
-    qf[r * B + b] = qn;
-    if (q_traj) q_traj[r * B + b] = qn;
-  }
+  thread_state_update(M, B, b, dt, q_in, eta, qf, vf, q_traj);
 }
 #endif
 
@@ -64,9 +50,6 @@ struct Rollout {
   int64_t out_step;  // doubles between two steps' eta in io.out (0: one scratch slot, no qdot_traj)
 };
 
-#ifndef DRC_FUSED_WAVES
-#define DRC_FUSED_WAVES 2
-#endif
 template <class QD, bool MESH = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
 rollout_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io, const Rollout ro) {
@@ -155,16 +138,10 @@ template <bool MESH>
 static int launch_rollout(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                           const KParams& kq, const IO& io, const Rollout& ro) {
   const dim3 g(grid), blk(64);
-  if (kq.nx == 23 && kq.ng == 16 && kq.np == 7)  // FR3
-    hipLaunchKernelGGL((rollout_kernel<Dims<23, 16, 7, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
-  else if (kq.nx == 20 && kq.ng == 14 && kq.np == 6)  // UR5e
-    hipLaunchKernelGGL((rollout_kernel<Dims<20, 14, 6, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
-  else if (kq.nx == 9 && kq.ng == 16 && kq.np == 9)  // Husky-FR3
-    hipLaunchKernelGGL((rollout_kernel<Dims<9, 16, 9, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
-  else if (kq.nx == 11 && kq.ng == 16 && kq.np == 11)  // XLS-FR3
-    hipLaunchKernelGGL((rollout_kernel<Dims<11, 16, 11, true, true, 64>, MESH>), g, blk, lds, st, m, kt, kq, io, ro);
-  else
-    return hipErrorInvalidValue;  // not a compiled shape: the stepwise path runs it
+  if (int r = with_compiled_shape(kq.nx, kq.ng, kq.np, [&](auto qd) {
+        hipLaunchKernelGGL((rollout_kernel<decltype(qd), MESH>), g, blk, lds, st, m, kt, kq, io, ro);
+      }))
+    return r;  // not a compiled shape: the stepwise path runs it
   return hipGetLastError();
 }
 
@@ -183,8 +160,7 @@ int launch_rollout_kernel(unsigned grid, hipStream_t st, const DevModel* m, cons
                           const IO& io, int steps, int per_step, double dt, double* qf, double* vf, double* q_traj,
                           double* pose_traj, double* dist_traj, int64_t out_step, bool mesh) {
   const Rollout ro{steps, per_step, dt, qf, vf, q_traj, pose_traj, dist_traj, out_step};
-  const int plan = fused_lds_doubles(kt, kq), state = rollout_state_doubles(kt, kq);
-  const size_t lds = static_cast<size_t>(plan > state ? plan : state) * sizeof(double);
+  const size_t lds = closed_loop_lds_bytes(kt, kq);
   return mesh ? launch_rollout_mesh_kernel(grid, lds, st, m, kt, kq, io, ro)
               : launch_rollout<false>(grid, lds, st, m, kt, kq, io, ro);
 }

@@ -1,6 +1,6 @@
-// The state update of a closed-loop step, shared by the rollout kernels
-// (rollout_kernel.hip) and the reach kernels (reach_kernel.hip): every path
-// calls rollout_velocity / rollout_advance, so they return identical bits.
+// The arithmetic of a closed-loop step's state update, shared by the rollout
+// and the reach kernels through closed_loop.hpp: every path calls
+// rollout_velocity / rollout_advance, so they return identical bits.
 #pragma once
 
 #include "kernel_common.hpp"
@@ -37,8 +37,9 @@ __device__ __forceinline__ double rollout_advance(double q, double dt, double v)
   const double d = dt * v;
   return q + d;
 }
-// t_k = t + k dt, rounded the same way (the host of the stepwise path: api.cpp)
-__device__ __forceinline__ double rollout_time(double t, int k, double dt) {
+// t_k = t + k dt, rounded the same way: the persistent kernel's step time and,
+// on the host, the stepwise path's (api.cpp) are this one function
+__host__ __device__ __forceinline__ double rollout_time(double t, int k, double dt) {
 #pragma clang fp contract(off)
   const double d = static_cast<double>(k) * dt;
   return t + d;
