@@ -58,10 +58,98 @@ def obstacle_poses(model, obstacle_pose, B, device, steps=None):
                      % (n, n, B, "" if steps is None else ", optionally with a leading [steps=%d]" % steps, shape))
 
 
+def obstacle_twists(model, obstacle_twist, B, device, steps=None):
+    """The obstacle-twist argument of the ``*_moving_obstacles_batch`` entries,
+    obstacle_poses' sibling: (device tensor, obstacle_ld, per_step) for [n][6]
+    or [n][6][B] (optionally with a leading [steps] axis), each twist the
+    world-frame velocity v of the slot pose's origin, then the angular velocity."""
+    n = model.n_obstacles
+    t = as_device(obstacle_twist, device)
+    shape = tuple(t.shape)
+    cores = ((n, 6), (n, 6, B))
+    per_step = shape not in cores and steps is not None and shape[:1] == (steps,) and shape[1:] in cores
+    core = shape[1:] if per_step else shape
+    if core in cores:
+        return t, (0 if len(core) == 2 else B), per_step
+    raise ValueError("obstacle_twist must be [n=%d][6] or [n=%d][6][B=%d]%s, got %s"
+                     % (n, n, B, "" if steps is None else ", optionally with a leading [steps=%d]" % steps, shape))
+
+
+def _pose_and_twist(model, obstacle_pose, obstacle_twist, B, device, steps=None):
+    """(pose, twist, obstacle_ld, per_step) of a call with twists: the C entries
+    take one obstacle_ld and one obstacles_per_step for both arrays, so a twist
+    laid out otherwise than the poses is brought to their layout."""
+    if obstacle_pose is None:
+        raise ValueError("obstacle_twist without obstacle_pose")
+    op, ld, per_step = obstacle_poses(model, obstacle_pose, B, device, steps=steps)
+    tw, tld, tps = obstacle_twists(model, obstacle_twist, B, device, steps=steps)
+    n = model.n_obstacles
+    if tps and not per_step:
+        raise ValueError("per-step obstacle_twist needs per-step obstacle_pose")
+    if tld and not ld:
+        raise ValueError("per-instance obstacle_twist needs per-instance obstacle_pose")
+    if ld and not tld:
+        tw = tw.unsqueeze(-1).expand(*tw.shape, B)
+    if per_step and not tps:
+        tw = tw.unsqueeze(0).expand(steps, *tw.shape)
+    return op, tw.contiguous(), ld, per_step
+
+
+def obstacle_trajectory(pose0, twist, dt, steps):
+    """Poses of obstacle slots that move with a constant twist: [steps][n][12]
+    (or [steps][n][12][B] when ``pose0`` or ``twist`` carries the [B] axis) with
+    R_k = exp(k dt omega^) R_0 and p_k = p_0 + k dt v, k = 0 .. steps - 1, from
+    ``pose0`` [n][12]([B]) (R column-major, then p) and ``twist`` [n][6]([B])
+    (v, then omega; world frame, v taken at the pose origin).  Rodrigues'
+    formula in float64 torch, on ``pose0``'s device.  The per-step
+    ``obstacle_pose`` that is consistent with an ``obstacle_twist``."""
+    torch = _torch()
+    p0 = pose0 if isinstance(pose0, torch.Tensor) else torch.as_tensor(np.asarray(pose0, dtype=np.float64))
+    p0 = p0.to(torch.float64)
+    tw = twist if isinstance(twist, torch.Tensor) else torch.as_tensor(np.asarray(twist, dtype=np.float64))
+    tw = tw.to(device=p0.device, dtype=torch.float64)
+    batched = p0.dim() == 3 or tw.dim() == 3
+    shapes = (tuple(p0.shape), tuple(tw.shape))
+    if p0.dim() == 2:
+        p0 = p0.unsqueeze(-1)
+    if tw.dim() == 2:
+        tw = tw.unsqueeze(-1)
+    n = p0.shape[0]
+    if p0.dim() != 3 or tw.dim() != 3 or p0.shape[1] != 12 or tuple(tw.shape[:2]) != (n, 6):
+        raise ValueError("pose0 must be [n][12]([B]) and twist [n][6]([B]), got %s and %s"
+                         % shapes)
+    nb = max(p0.shape[2], tw.shape[2])
+    p0 = p0.expand(n, 12, nb)
+    tw = tw.expand(n, 6, nb)
+    steps = int(steps)
+    k = torch.arange(steps, dtype=torch.float64, device=p0.device).view(steps, 1, 1, 1) * float(dt)
+    phi = k * tw[None, :, 3:6]                      # rotation vector k dt omega: [steps][n][3][nb]
+    th = torch.sqrt((phi * phi).sum(dim=2))         # [steps][n][nb]
+    u = phi / torch.where(th > 0, th, torch.ones_like(th)).unsqueeze(2)
+    s, c2 = torch.sin(th), 2.0 * torch.sin(0.5 * th) ** 2   # sin, 1 - cos
+    ux, uy, uz = u[:, :, 0], u[:, :, 1], u[:, :, 2]
+    zero = torch.zeros_like(ux)
+    K = torch.stack((torch.stack((zero, -uz, uy), 2), torch.stack((uz, zero, -ux), 2),
+                     torch.stack((-uy, ux, zero), 2)), 2)   # [steps][n][3][3][nb]
+    eye = torch.eye(3, dtype=torch.float64, device=p0.device).view(1, 1, 3, 3, 1)
+    uu = u.unsqueeze(3) * u.unsqueeze(2)
+    E = eye + s[:, :, None, None] * K + c2[:, :, None, None] * (uu - eye)   # unit u: K^2 = u u^T - I
+    C0 = p0[:, :9].reshape(n, 3, 3, nb)             # [n][column j][row i][nb]
+    Ck = torch.einsum("snimb,njmb->snjib", E, C0)
+    Ck = torch.where((th > 0)[:, :, None, None], Ck, C0.unsqueeze(0).expand(steps, n, 3, 3, nb))
+    kv = k * tw[None, :, 0:3]
+    P0 = p0[None, :, 9:12].expand(steps, n, 3, nb)
+    Pk = torch.where(kv != 0, P0 + kv, P0)
+    out = torch.cat((Ck.reshape(steps, n, 9, nb), Pk), dim=2).contiguous()
+    return out if batched else out[..., 0].contiguous()
+
+
 def qpik_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
-               out=None, status=None, iters=None, stream=None, obstacle_pose=None):
+               out=None, status=None, iters=None, stream=None, obstacle_pose=None, obstacle_twist=None):
     """Launch ``drc_qpik_batch`` on device tensors laid out [field][B]
-    (``drc_qpik_obstacles_batch`` with ``obstacle_pose``, see obstacle_poses)."""
+    (``drc_qpik_obstacles_batch`` with ``obstacle_pose``, see obstacle_poses;
+    ``drc_qpik_moving_obstacles_batch`` with ``obstacle_twist`` too, see
+    obstacle_twists)."""
     torch = _torch()
     dev = q.device
     B = q.shape[1]
@@ -73,6 +161,13 @@ def qpik_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=N
         status = torch.empty(B, dtype=torch.int32, device=dev)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
+    if obstacle_twist is not None:
+        op, tw, ld, _ = _pose_and_twist(model, obstacle_pose, obstacle_twist, B, dev)
+        _capi.check(_capi.lib().drc_qpik_moving_obstacles_batch(
+            model.handle, C.byref(params), C.c_int64(B), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target),
+            _ptr(x_init), _ptr(xdot_init), _ptr(op), _ptr(tw), C.c_int64(ld), _ptr(out), _ptr(status), _ptr(iters),
+            C.c_void_p(stream)))
+        return out, status
     if obstacle_pose is not None:
         op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
         _capi.check(_capi.lib().drc_qpik_obstacles_batch(
@@ -102,11 +197,13 @@ class RolloutResult:
 
 def qpik_rollout_batch(model, params, q, qdot, steps, dt, x_target=None, xdot_target=None, x_init=None,
                        xdot_init=None, targets_per_step=False, want=("qdot_traj", "q_traj"), q_final=None,
-                       qdot_final=None, stream=None, obstacle_pose=None):
+                       qdot_final=None, stream=None, obstacle_pose=None, obstacle_twist=None):
     """Launch ``drc_qpik_rollout_batch`` on device tensors laid out [field][B]
     (per-step targets: [steps][field][B]); with ``obstacle_pose`` (see
     obstacle_poses; a leading [steps] axis moves the obstacles)
-    ``drc_qpik_rollout_obstacles_batch``.  ``want``: the optional
+    ``drc_qpik_rollout_obstacles_batch``, with ``obstacle_twist`` too (see
+    obstacle_twists; obstacle_trajectory makes the poses that go with a
+    constant twist) ``drc_qpik_rollout_moving_obstacles_batch``.  ``want``: the optional
     trajectories to allocate and fill (ROLLOUT_FIELDS); ``q_final`` /
     ``qdot_final`` may be given (``q`` / ``qdot`` themselves: in place)."""
     torch = _torch()
@@ -141,6 +238,15 @@ def qpik_rollout_batch(model, params, q, qdot, steps, dt, x_target=None, xdot_ta
         dist_traj=f(n, 1 + nv, B) if "dist_traj" in want else None)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
+    if obstacle_twist is not None:
+        op, tw, ld, per_step = _pose_and_twist(model, obstacle_pose, obstacle_twist, B, dev, steps=steps)
+        _capi.check(_capi.lib().drc_qpik_rollout_moving_obstacles_batch(
+            model.handle, C.byref(params), C.c_int64(B), C.c_int(steps), C.c_double(dt), _ptr(q), _ptr(qdot),
+            _ptr(x_target), _ptr(xdot_target), _ptr(x_init), _ptr(xdot_init), C.c_int(1 if targets_per_step else 0),
+            _ptr(op), _ptr(tw), C.c_int64(ld), C.c_int(1 if per_step else 0),
+            _ptr(res.q_final), _ptr(res.qdot_final), _ptr(res.qdot_traj), _ptr(res.status_traj),
+            _ptr(res.iters_traj), _ptr(res.q_traj), _ptr(res.pose_traj), _ptr(res.dist_traj), C.c_void_p(stream)))
+        return res
     if obstacle_pose is not None:
         op, ld, per_step = obstacle_poses(model, obstacle_pose, B, dev, steps=steps)
         _capi.check(_capi.lib().drc_qpik_rollout_obstacles_batch(
@@ -410,9 +516,11 @@ def qpid_stages_batch(model, params, q, qdot, x_target=None, xdot_target=None, x
 
 
 def stages_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
-                 obstacle_pose=None):
+                 obstacle_pose=None, obstacle_twist=None):
     """Stage outputs (pose, J, manipulability, min distance, task velocity);
-    with ``obstacle_pose`` (see obstacle_poses) ``drc_qpik_stages_obstacles_batch``."""
+    with ``obstacle_pose`` (see obstacle_poses) ``drc_qpik_stages_obstacles_batch``;
+    with ``obstacle_twist`` too ``drc_qpik_stages_moving_obstacles_batch``, which
+    adds ``dist_rate`` [B], the closest pair's dd/dt from the slot's motion."""
     torch = _torch()
     dev = q.device
     B = q.shape[1]
@@ -422,6 +530,14 @@ def stages_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init
     pose, jac, man, dist, xdd = f(12), f(6 * nv), f(1 + mani), f(1 + nv), f(6)
     pair = torch.zeros(B, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if obstacle_twist is not None:
+        op, tw, ld, _ = _pose_and_twist(model, obstacle_pose, obstacle_twist, B, dev)
+        rate = torch.zeros(B, dtype=torch.float64, device=dev)
+        _capi.check(_capi.lib().drc_qpik_stages_moving_obstacles_batch(
+            model.handle, C.byref(params), C.c_int64(B), _ptr(q), _ptr(qdot), _ptr(x_target), _ptr(xdot_target),
+            _ptr(x_init), _ptr(xdot_init), _ptr(op), _ptr(tw), C.c_int64(ld), _ptr(pose), _ptr(jac), _ptr(man),
+            _ptr(dist), _ptr(pair), _ptr(xdd), _ptr(rate), C.c_void_p(stream)))
+        return dict(pose=pose, jac=jac, man=man, dist=dist, pair=pair, xdot_des=xdd, dist_rate=rate)
     if obstacle_pose is not None:
         op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
         _capi.check(_capi.lib().drc_qpik_stages_obstacles_batch(

@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = (
     "drc_state_host", "drc_model_geom_info", "drc_mesh_convex_hull", "drc_qpik_rollout_batch",
     "drc_model_set_obstacles", "drc_qpik_obstacles_batch", "drc_qpik_stages_obstacles_batch",
     "drc_qpik_rollout_obstacles_batch",
+    "drc_qpik_moving_obstacles_batch", "drc_qpik_stages_moving_obstacles_batch",
+    "drc_qpik_rollout_moving_obstacles_batch",
     "drc_qpik_reach_batch", "drc_qpik_reach_obstacles_batch", "drc_reach_thresholds",
     "drc_qpik_reach_path_batch", "drc_qpik_reach_path_obstacles_batch",
     "drc_qpik_reach_seeds_batch", "drc_qpik_reach_seeds_obstacles_batch",
@@ -68,6 +70,9 @@ SEEDS_FIRST, SEEDS_FEWEST_STEPS = 0, 1
 # the obstacle-slot entries (absent from older A/B builds)
 OBSTACLE_SYMBOLS = ("drc_model_set_obstacles", "drc_qpik_obstacles_batch", "drc_qpik_stages_obstacles_batch",
                     "drc_qpik_rollout_obstacles_batch")
+# the obstacle entries with a twist per slot (absent from older A/B builds)
+MOVING_OBSTACLE_SYMBOLS = ("drc_qpik_moving_obstacles_batch", "drc_qpik_stages_moving_obstacles_batch",
+                           "drc_qpik_rollout_moving_obstacles_batch")
 # drc_model_geom_info type codes
 GEOM_SPHERE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH, GEOM_HALFSPACE = 0, 1, 2, 3, 4
 
@@ -177,6 +182,15 @@ def _load():
         lib.drc_qpik_rollout_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int, C.c_double,
                                                          vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int,
                                                          vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "drc_qpik_moving_obstacles_batch"):  # obstacle twists: absent from older A/B builds
+        lib.drc_qpik_moving_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, vp, vp, vp, vp, vp, vp,
+                                                        vp, vp, C.c_int64, vp, vp, vp, vp]
+        lib.drc_qpik_stages_moving_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, vp, vp, vp, vp,
+                                                               vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp,
+                                                               vp]
+        lib.drc_qpik_rollout_moving_obstacles_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int,
+                                                                C.c_double, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp,
+                                                                C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "drc_qpik_reach_batch"):  # goal-reaching rollouts: absent from older A/B builds
         lib.drc_qpik_reach_batch.argtypes = [vp, C.POINTER(QPIKParams), C.c_int64, C.c_int, C.c_double, C.c_double,
                                              C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -246,7 +260,7 @@ def _load():
     for name in EXPORTED_SYMBOLS:
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
                     "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info",
-                    "drc_mesh_convex_hull", "drc_qpik_rollout_batch") + OBSTACLE_SYMBOLS + REACH_SYMBOLS + REACH_PATH_SYMBOLS \
+                    "drc_mesh_convex_hull", "drc_qpik_rollout_batch") + OBSTACLE_SYMBOLS + MOVING_OBSTACLE_SYMBOLS + REACH_SYMBOLS + REACH_PATH_SYMBOLS \
                 + REACH_SEEDS_SYMBOLS + QP_DENSE_SYMBOLS \
                 and not hasattr(lib, name):
             continue  # diagnostics an older A/B build may lack

@@ -405,6 +405,17 @@ static const char kMeshStageMsg[] =
 // Obstacle poses of a call (drc_qpik_*obstacles_batch): [n][12][ld] in
 // x_target's layout, ld = 0 one set shared by the batch (kernel_common.hpp)
 using Obst = ObstIn;
+// ... and their twists (drc_qpik_*moving_obstacles_batch): [n][6][ld] with the
+// poses' ld, and the stage output dist_rate.  A call without twists passes none
+using Rate = RateIn;
+// The twists against the call: the rate reaches the QP as d + (dd/dt) / alpha_cbf
+// (task_stage.hpp RATE), so a call with twists needs alpha_cbf > 0
+static int check_rate(const Rate* rt, const Obst* ob, const drc_qpik_params* params) {
+  if (rt && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_twist without obstacle_pose");
+  if (rt && !(params->alpha_cbf > 0))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_twist needs alpha_cbf > 0: the rate enters the QP as d + rate / alpha_cbf");
+  return DRC_OK;
+}
 static const char kSlotsPlainMsg[] =
     "the model has obstacle slots: pass their poses through drc_qpik_obstacles_batch, "
     "drc_qpik_stages_obstacles_batch or drc_qpik_rollout_obstacles_batch";
@@ -701,7 +712,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
                          const double* qdot, const double* xt, const double* xdt, const double* xi,
                          const double* xdi, double* out, int32_t* status, int32_t* iters, double* pose, double* jac,
                          double* man, double* dist, int32_t* pair, double* xdd, void* stream,
-                         uint64_t* stamps = nullptr, const Obst* ob = nullptr) {
+                         uint64_t* stamps = nullptr, const Obst* ob = nullptr, const Rate* rt = nullptr) {
   if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   const bool slots = m->hm.dev.nobst > 0;
   if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsPlainMsg);
@@ -709,6 +720,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     return set_err(DRC_ERR_INVALID_ARGUMENT, "the model has no obstacle slots (drc_model_set_obstacles declares them)");
   if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
     return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
+  if (int r = check_rate(rt, ob, params)) return r;
   if (B == 0) return DRC_OK;
   if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
   if (!q || !qdot || !xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, "q, qdot and xdot_target are required");
@@ -872,6 +884,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     io.stamps = stages ? nullptr : stamps;
     io.order = (!stages && !lane && dbg_order) ? m->d_order : nullptr;
     const ObstIn obin = ob ? *ob : ObstIn();
+    const RateIn rtin = rt ? *rt : RateIn();  // (twists: the rate builds; without, the obstacle builds as ever)
     int* qc = cx->d_queue + c * StreamCtx::kSlotInts;  // c < 16 (drc_set_concurrency)
     // the whole slot (128 B, one aligned fill; 17 ints took two fill kernels)
     HIP_TRY(hipMemsetAsync(qc, 0, StreamCtx::kSlotInts * sizeof(int), cs));
@@ -896,7 +909,10 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     const size_t lds_t = static_cast<size_t>(kt_c.lds_doubles) * sizeof(double);
     const size_t lds_q = stages ? 0 : static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
     auto launch_task = [&](hipStream_t sm) -> int {
-      if (slots)
+      if (slots && rt)
+        HIP_TRY(static_cast<hipError_t>(
+            launch_task_rate_kernel(static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io, obin, rtin)));
+      else if (slots)
         HIP_TRY(static_cast<hipError_t>(
             launch_task_obstacle_kernel(static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io, obin)));
       else
@@ -931,9 +947,11 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
           sizeof(double);
       io.queue = qc;
       HIP_TRY(static_cast<hipError_t>(
-          slots ? launch_fused_obstacle_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin)
-                : launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io,
-                                      dm.has_mesh != 0)));
+          slots && rt
+              ? launch_fused_rate_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin, rtin)
+          : slots ? launch_fused_obstacle_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin)
+                  : launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io,
+                                        dm.has_mesh != 0)));
       if (timed_c) HIP_TRY(hipEventRecord(e1, cs));
     } else if (!lane) {  // wave-per-instance task kernel on every instance, then the QP
       if (int r = launch_task(cs)) return r;
@@ -989,12 +1007,12 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
                   const double* qdot, const double* xt, const double* xdt, const double* xi, const double* xdi,
                   double* out, int32_t* status, int32_t* iters, double* pose, double* jac, double* man,
                   double* dist, int32_t* pair, double* xdd, void* stream, uint64_t* stamps = nullptr,
-                  const Obst* ob = nullptr) {
+                  const Obst* ob = nullptr, const Rate* rt = nullptr) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
   return launch_locked(m, params, stages, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, pose, jac, man, dist,
-                       pair, xdd, stream, stamps, ob);
+                       pair, xdd, stream, stamps, ob, rt);
 }
 
 // --------------------------------------------------------------------------
@@ -1115,7 +1133,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
                    const double* q0, const double* qdot0, const double* xt, const double* xdt, const double* xi,
                    const double* xdi, int per_step, double* qf, double* vf, double* qdot_traj, int32_t* status_traj,
                    int32_t* iters_traj, double* q_traj, double* pose_traj, double* dist_traj, void* stream,
-                   const Obst* ob = nullptr, int ob_per_step = 0) {
+                   const Obst* ob = nullptr, int ob_per_step = 0, const Rate* rt = nullptr) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
@@ -1123,6 +1141,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   if (ob_per_step != 0 && ob_per_step != 1)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacles_per_step must be 0 or 1");
   if (int rc = check_obstacle_pose(ob, B, "the batch")) return rc;
+  if (int rc = check_rate(rt, ob, params)) return rc;
   if (steps < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "steps must be at least 1");
   if (int rc = check_dt(dt)) return rc;
   if (per_step != 0 && per_step != 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "targets_per_step must be 0 or 1");
@@ -1187,6 +1206,11 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     if (ob)  // this step's pose set: [n][12][ld], or the shared [n][12]
       ob_k = Obst{ob->pose + (ob_per_step ? int64_t(k) * dm.nobst * 12 * (ob->ld ? ob->ld : 1) : 0), ob->ld};
     const Obst* obp = ob ? &ob_k : nullptr;
+    Rate rt_k;
+    if (rt)  // this step's twists, stepping with the poses
+      rt_k = Rate{rt->twist + (ob_per_step ? int64_t(k) * dm.nobst * 6 * (rt->ld ? rt->ld : 1) : 0), rt->ld, nullptr};
+    const Rate* rtp = rt ? &rt_k : nullptr;
+    // (pose_traj / dist_traj: the stage launch without twists -- the geometric d)
     if (pose_traj || dist_traj)
       if (int rc = launch_locked(m, &pk, 1, B, qk, vk, xt_k, xdt_k, xi, xdi, nullptr, nullptr, nullptr,
                                  pose_traj ? pose_traj + int64_t(k) * 12 * B : nullptr, nullptr, nullptr,
@@ -1195,7 +1219,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
         return rc;
     if (int rc = launch_locked(m, &pk, 0, B, qk, vk, xt_k, xdt_k, xi, xdi, eta_k, status_traj + int64_t(k) * B,
                                iters_traj ? iters_traj + int64_t(k) * B : nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, stream, nullptr, obp))
+                               nullptr, nullptr, stream, nullptr, obp, rtp))
       return rc;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_integrate_kernel(
         B, st, m->d_model, dt, qk, eta_k, qf, vf, q_traj ? q_traj + int64_t(k) * nv * B : nullptr)));
@@ -2305,6 +2329,52 @@ int drc_qpik_rollout_obstacles_batch(const drc_model* m, const drc_qpik_params* 
   return drc_amd::rollout(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step, q_final, qdot_final,
                           qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream, &ob,
                           obstacles_per_step);
+}
+
+// ---- moving obstacles: a twist per slot (task_stage.hpp RATE) ------------------------
+// obstacle_twist = NULL: the obstacle entry itself
+int drc_qpik_moving_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
+                                    const double* qdot, const double* xt, const double* xdt, const double* xi,
+                                    const double* xdi, const double* obstacle_pose, const double* obstacle_twist,
+                                    int64_t obstacle_ld, double* out, int32_t* status, int32_t* iters, void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  const drc_amd::Rate rt{obstacle_twist, obstacle_ld, nullptr};
+  return drc_amd::launch(m, p, 0, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, stream, nullptr, &ob, obstacle_twist ? &rt : nullptr);
+}
+
+int drc_qpik_stages_moving_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
+                                           const double* qdot, const double* xt, const double* xdt, const double* xi,
+                                           const double* xdi, const double* obstacle_pose,
+                                           const double* obstacle_twist, int64_t obstacle_ld, double* pose, double* jac,
+                                           double* man, double* dist, int32_t* pair, double* xdd, double* dist_rate,
+                                           void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  const drc_amd::Rate rt{obstacle_twist, obstacle_ld, dist_rate};
+  if (int rc = drc_amd::launch(m, p, 1, B, q, qdot, xt, xdt, xi, xdi, nullptr, nullptr, nullptr, pose, jac, man, dist,
+                               pair, xdd, stream, nullptr, &ob, obstacle_twist ? &rt : nullptr))
+    return rc;
+  if (!obstacle_twist && dist_rate && B > 0) {  // no twist: nothing but the robot moves
+    using drc_amd::set_err;
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemsetAsync(dist_rate, 0, size_t(B) * 8, reinterpret_cast<hipStream_t>(stream)));
+  }
+  return DRC_OK;
+}
+
+int drc_qpik_rollout_moving_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int steps,
+                                            double dt, const double* q0, const double* qdot0, const double* xt,
+                                            const double* xdt, const double* xi, const double* xdi,
+                                            int targets_per_step, const double* obstacle_pose,
+                                            const double* obstacle_twist, int64_t obstacle_ld, int obstacles_per_step,
+                                            double* q_final, double* qdot_final, double* qdot_traj,
+                                            int32_t* status_traj, int32_t* iters_traj, double* q_traj,
+                                            double* pose_traj, double* dist_traj, void* stream) {
+  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
+  const drc_amd::Rate rt{obstacle_twist, obstacle_ld, nullptr};
+  return drc_amd::rollout(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step, q_final, qdot_final,
+                          qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream, &ob,
+                          obstacles_per_step, obstacle_twist ? &rt : nullptr);
 }
 
 // ---- goal-reaching rollouts ------------------------------------------------------

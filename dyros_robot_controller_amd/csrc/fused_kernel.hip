@@ -23,8 +23,9 @@ namespace drc_amd {
 #endif
 // MESH: the build for models with convex-hull geometry (task_stage.hpp)
 // OB: empty, or one ObstIn: the build for models with obstacle slots and the
-// call's poses (task_stage.hpp OBST).  A pack, so that the kernels without
-// obstacles keep their four arguments
+// call's poses (task_stage.hpp OBST), or that and one RateIn: the slots'
+// twists (RATE).  A pack, so that the kernels without obstacles keep their
+// four arguments and those without twists their five
 template <class QD, bool MESH = false, class... OB>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DRC_FUSED_WAVES, 8)))
 fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq, const IO io, const OB... ob) {
@@ -39,7 +40,7 @@ fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     wsync();
   }
   static_assert(QD::gs == 64, "the fused kernel runs one instance per wave");
-  static_assert(sizeof...(OB) <= 1, "at most one set of obstacle poses");
+  static_assert(sizeof...(OB) <= 2, "at most one set of obstacle poses and one of twists");
   const int64_t B = io.B;
   IO iol = io;  // the record lives in LDS: one slot, reused by every instance of the wave
   iol.rec = S + fused_rec_offset(kt, kq);  // (kernel_common.hpp: past the QP plan, in the task plan's dead overlay)
@@ -51,7 +52,7 @@ fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     const int64_t b = io.ordered(jj);
     stage_stamp(io, ST_TASK0, io.b0 + b);
     stage_where(io, ST_WTASK, io.b0 + b);
-    task_instance<0, MESH, sizeof...(OB) != 0>(M0, kt, iol, S, b, ob...);
+    task_instance<0, MESH, sizeof...(OB) != 0, sizeof...(OB) == 2>(M0, kt, iol, S, b, ob...);
     wsync();
     stage_stamp(io, ST_TASK1, io.b0 + b);
     qp_instance<QD>(M0, kq, kpl, iol, S, b);
@@ -72,8 +73,14 @@ static int launch_fused(unsigned grid, size_t lds, hipStream_t st, const DevMode
 // The builds for models with hulls are a translation unit of their own
 // (fused_mesh_kernel.hip includes this file with DRC_FUSED_MESH defined), so
 // this unit compiles to what it was without them.  Likewise the builds for
-// models with obstacle slots (fused_obstacle_kernel.hip, DRC_FUSED_OBST).
-#if defined(DRC_FUSED_OBST)
+// models with obstacle slots (fused_obstacle_kernel.hip, DRC_FUSED_OBST) and
+// those with moving slots (fused_rate_kernel.hip, DRC_FUSED_RATE).
+#if defined(DRC_FUSED_RATE)
+int launch_fused_rate_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                             const KParams& kq, const IO& io, const ObstIn& ob, const RateIn& rt) {
+  return launch_fused<false>(grid, lds, st, m, kt, kq, io, ob, rt);
+}
+#elif defined(DRC_FUSED_OBST)
 int launch_fused_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                                  const KParams& kq, const IO& io, const ObstIn& ob) {
   return launch_fused<false>(grid, lds, st, m, kt, kq, io, ob);

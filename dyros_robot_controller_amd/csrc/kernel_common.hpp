@@ -433,6 +433,18 @@ struct ObstIn {
   const double* pose = nullptr;
   int64_t ld = 0;
 };
+// Twists of the obstacle slots for one call (drc_qpik_*moving_obstacles_batch):
+// twist [nobst][6][ld], the world-frame velocity of the slot pose's origin and
+// the angular velocity, laid out like the poses (ld = 0: one [nobst][6] set
+// for every instance); rate: the stage output dist_rate [B], or NULL.  An
+// argument of its own of the rate builds (task_rate_kernel.hip,
+// fused_rate_kernel.hip), so that ObstIn and the kernels that take it keep
+// their arguments.
+struct RateIn {
+  const double* twist = nullptr;
+  int64_t ld = 0;
+  double* rate = nullptr;
+};
 // six clock stamps, then where the task and the QP stage ran (stage_where)
 constexpr int kTimeStamps = 6, kStamps = 8;
 enum { ST_TASK0 = 0, ST_TASK1 = 1, ST_QP0 = 2, ST_ASM = 3, ST_SOLVED = 4, ST_OUT = 5, ST_WTASK = 6, ST_WQP = 7 };

@@ -59,6 +59,12 @@ int launch_task_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const
                                 const IO& io, const ObstIn& ob);
 int launch_fused_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                                  const KParams& kq, const IO& io, const ObstIn& ob);
+// ... and for moving slots (task_rate_kernel.hip, fused_rate_kernel.hip):
+// task_instance<0, false, OBST = true, RATE = true>, rt the call's twists
+int launch_task_rate_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                            const IO& io, const ObstIn& ob, const RateIn& rt);
+int launch_fused_rate_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                             const KParams& kq, const IO& io, const ObstIn& ob, const RateIn& rt);
 
 // persistent rollout kernel (rollout_kernel.hip; compiled QPIK shapes,
 // hipErrorInvalidValue otherwise): per instance `steps` times task stage, QP

@@ -441,9 +441,15 @@ __device__ __forceinline__ bool revolute(uint32_t rev_mask, int j) { return (rev
 // OBST: the model has obstacle slots (DevModel::nobst): geometries whose pose is
 // an input of the call (ob), among them half-spaces, which pass 1 decides
 // in closed form (halfspace.hpp).  A build of its own again; not with MESH.
-template <int PROBLEM, bool MESH = false, bool OBST = false>
+// RATE (with OBST, QPIK only): the slots move with the call's twists (rt), and
+// the distance the QP reads carries the winner's dd/dt: the record's distance
+// slot holds d + (dd/dt) / alpha_cbf, so that the QP's row -alpha (d - dist_min)
+// becomes -alpha (d - dist_min) - dd/dt without a change to the QP.  The
+// stage outputs keep the geometric d; dd/dt is an output of its own (rt.rate).
+template <int PROBLEM, bool MESH = false, bool OBST = false, bool RATE = false>
 __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, const KParams& kp, const IO& io, double* S,
-                                              int64_t b, [[maybe_unused]] const ObstIn ob = ObstIn()) {
+                                              int64_t b, [[maybe_unused]] const ObstIn ob = ObstIn(),
+                                              [[maybe_unused]] const RateIn rt = RateIn()) {
   const int l = lane_id();
   const int nv = kp.nv;
   EpaPoly* ews = reinterpret_cast<EpaPoly*>(S + kp.kEpa);  // LDS-resident polytope
@@ -490,7 +496,9 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   // x_target (consecutive instances on consecutive addresses); ld = 0 is
   // one pose set for the whole batch
   static_assert(!(MESH && OBST), "no obstacle build for hull models");
+  static_assert(!RATE || (OBST && PROBLEM == 0), "obstacle twists: the QPIK stage of a model with slots");
   [[maybe_unused]] double opl[12];
+  [[maybe_unused]] double otw[6];  // (RATE) the slot's twist: v of the pose origin, then omega
   [[maybe_unused]] const int obst0 = OBST ? M->obst0 : 0;
   if constexpr (OBST) {
     if (l >= obst0 && l < M->ngeom) {
@@ -498,6 +506,12 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       const double* op = ob.pose + (int64_t)(l - obst0) * 12 * os + (ob.ld ? gb : 0);
 #pragma unroll
       for (int i = 0; i < 12; ++i) opl[i] = op[i * os];
+      if constexpr (RATE) {
+        const int64_t ts = rt.ld ? rt.ld : 1;
+        const double* tp = rt.twist + (int64_t)(l - obst0) * 6 * ts + (rt.ld ? gb : 0);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) otw[i] = tp[i * ts];
+      }
     }
   }
   wsync();
@@ -1064,6 +1078,28 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     }
     return g;
   };
+  // (RATE) dd/dt of the winning pair while the joints rest: the B-term of
+  // dist_grad with the slot's rigid motion in place of a joint's column,
+  // s n . (v + omega x (pB - p)), p the slot pose's origin.  Formed by the lane
+  // of the obstacle geometry, which holds the twist, and broadcast; 0 for a
+  // self pair (an obstacle is a pair's b)
+  [[maybe_unused]] auto dist_rate = [&](double dd) {
+    double r = 0;
+    if constexpr (RATE) {
+      const int gB = besti < M->npairs ? M->pair_b[besti] : 0;
+      if (gB >= obst0 && besti < M->npairs) {
+        if (l == gB) {
+          const V3 pA = ld3(red), pB = ld3(red + 3), po = v3(Tg[12 * gB + 9], Tg[12 * gB + 10], Tg[12 * gB + 11]);
+          V3 n = pB - pA;
+          n = (1.0 / sqrt(dot(n, n))) * n;
+          r = dot(n, v3(otw[0], otw[1], otw[2]) + cross(v3(otw[3], otw[4], otw[5]), pB - po));
+          if (dd < 0) r = -r;
+        }
+        r = bcast(r, __builtin_amdgcn_readfirstlane(gB));
+      }
+    }
+    return r;
+  };
   if (myi == besti && myi < M->npairs) {  // the winning lane publishes its witnesses
     st3(red, bpA);
     st3(red + 3, bpB);
@@ -1085,6 +1121,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   bestd = S[kp.oSc + SC_DIST];
   PH(6);
   if (l < nv) dgv[l] = dist_grad(bestd);
+  [[maybe_unused]] const double drate = dist_rate(bestd);
   wsync();
   if constexpr (PROBLEM == 1) qpid_task_extras(M, kp, S, bestd, besti, io.st_gdv != nullptr);
   PH(7);
@@ -1118,7 +1155,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       if (e < kp.rMan) v = J[e];
       else if (e == kp.rMan) v = S[kp.oSc + SC_MAN];
       else if (e < kp.rDist) v = mg[e - kp.rMan - 1];
-      else if (e == kp.rDist) v = bestd;
+      else if (e == kp.rDist) v = RATE ? bestd + drate / kp.alpha_cbf : bestd;
       else if (e < kp.rXdd) v = dgv[e - kp.rDist - 1];
       else if (e < kp.rQ) v = xdd[e - kp.rXdd];
       else if (PROBLEM == 0 || e < kp.rQd) v = qv[e - kp.rQ];
@@ -1142,6 +1179,8 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       if (l == 0) io.st_dist[gb] = bestd;
       if (l < nv) io.st_dist[(int64_t)(1 + l) * LD + gb] = dgv[l];
     }
+    if constexpr (RATE)
+      if (rt.rate && l == 0) rt.rate[gb] = drate;
     if (io.st_pair && l == 0) io.st_pair[gb] = besti < M->npairs ? besti : -1;
     if (io.st_xdd && l < 6) io.st_xdd[l * LD + gb] = xdd[l];
     if constexpr (PROBLEM == 1) {
@@ -1159,14 +1198,17 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       wsync();
       const double dd = S[kp.oSc + SC_DIST];
       const double g = l < nv ? dist_grad(dd) : 0.0;
+      [[maybe_unused]] const double dr = dist_rate(dd);  // (RATE) from the refined witnesses, patched like d
       if (io.rec) {
         double* rec = io.rec + b * io.rec_stride;
-        if (l == 0) rec[kp.rDist] = dd;
+        if (l == 0) rec[kp.rDist] = RATE ? dd + dr / kp.alpha_cbf : dd;
         if (l < nv) rec[kp.rDist + 1 + l] = g;
       } else if (io.st_dist) {
         if (l == 0) io.st_dist[gb] = dd;
         if (l < nv) io.st_dist[(int64_t)(1 + l) * LD + gb] = g;
       }
+      if constexpr (RATE)
+        if (!io.rec && rt.rate && l == 0) rt.rate[gb] = dr;
       wsync();
     }
   }

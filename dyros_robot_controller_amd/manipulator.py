@@ -333,8 +333,10 @@ ROLLOUT_MODES = {"qpik": _capi.MODE_QPIK, "step": _capi.MODE_QPIK_STEP, "cubic":
 
 
 def _rollout(ctrl, kv, q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init, xdot_init, current_time,
-             init_time, duration, targets_per_step, want, obstacle_pose=None):
+             init_time, duration, targets_per_step, want, obstacle_pose=None, obstacle_twist=None):
     """QPIK_rollout_batch of both controllers (``kv``: the task Kv of its QPIK*)."""
+    if obstacle_twist is not None and obstacle_pose is None:
+        raise ValueError("obstacle_twist without obstacle_pose")
     if mode not in ROLLOUT_MODES:
         raise ValueError("mode must be one of %s" % sorted(ROLLOUT_MODES))
     p = ctrl._pb.params(link_name, ROLLOUT_MODES[mode], ctrl.Kp_task_, kv, current_time, init_time, duration)
@@ -342,7 +344,8 @@ def _rollout(ctrl, kv, q, qdot, x_target, xdot_target, link_name, steps, dt, mod
     a = lambda t: _batch.as_device(t, dev)
     return _batch.qpik_rollout_batch(ctrl.robot_data_.model, p, a(q), a(qdot), steps, ctrl.dt_ if dt is None else dt,
                                      None if mode == "qpik" else a(x_target), a(xdot_target), a(x_init), a(xdot_init),
-                                     targets_per_step=targets_per_step, want=want, obstacle_pose=obstacle_pose)
+                                     targets_per_step=targets_per_step, want=want, obstacle_pose=obstacle_pose,
+                                     obstacle_twist=obstacle_twist)
 
 
 def _reach(ctrl, kv, q, qdot, x_target, link_name, max_steps, dt, pos_tol, rot_tol, xdot_target, w_reg,
@@ -488,38 +491,48 @@ class RobotController:
 
     # -- batched entries (device tensors, [field][B]) --------------------------
     def _run(self, mode, link_name, q, qdot, x_target, xdot_target, x_init=None, xdot_init=None,
-             t=0.0, t0=0.0, duration=1.0, iters=None, obstacle_pose=None):
+             t=0.0, t0=0.0, duration=1.0, iters=None, obstacle_pose=None, obstacle_twist=None):
+        if obstacle_twist is not None and obstacle_pose is None:
+            raise ValueError("obstacle_twist without obstacle_pose")
         p = self._pb.params(link_name, mode, self.Kp_task_, self.Kv_task_, t, t0, duration)
         dev = self.robot_data_.device
         return _batch.qpik_batch(self.robot_data_.model, p, _batch.as_device(q, dev), _batch.as_device(qdot, dev),
                                  _batch.as_device(x_target, dev), _batch.as_device(xdot_target, dev),
                                  _batch.as_device(x_init, dev), _batch.as_device(xdot_init, dev), iters=iters,
-                                 obstacle_pose=obstacle_pose)
+                                 obstacle_pose=obstacle_pose, obstacle_twist=obstacle_twist)
 
     # (obstacle_pose: the poses of the model's obstacle slots, RobotData.set_obstacles:
     # [n][12] shared by the batch or [n][12][B], each R column-major then p)
-    def QPIK_batch(self, q, qdot, xdot_target, link_name, obstacle_pose=None):
-        return self._run(_capi.MODE_QPIK, link_name, q, qdot, None, xdot_target, obstacle_pose=obstacle_pose)
+    # (obstacle_twist: their twists, [n][6] or [n][6][B], world frame: the velocity of the
+    # pose origin, then the angular velocity -- the distance row then sees the slot's motion)
+    def QPIK_batch(self, q, qdot, xdot_target, link_name, obstacle_pose=None, obstacle_twist=None):
+        return self._run(_capi.MODE_QPIK, link_name, q, qdot, None, xdot_target, obstacle_pose=obstacle_pose,
+                         obstacle_twist=obstacle_twist)
 
-    def QPIK_step_batch(self, q, qdot, x_target, xdot_target, link_name, iters=None, obstacle_pose=None):
+    def QPIK_step_batch(self, q, qdot, x_target, xdot_target, link_name, iters=None, obstacle_pose=None,
+                        obstacle_twist=None):
         return self._run(_capi.MODE_QPIK_STEP, link_name, q, qdot, x_target, xdot_target, iters=iters,
-                         obstacle_pose=obstacle_pose)
+                         obstacle_pose=obstacle_pose, obstacle_twist=obstacle_twist)
 
     def QPIK_cubic_batch(self, q, qdot, x_target, xdot_target, x_init, xdot_init, current_time, init_time,
-                         duration, link_name, obstacle_pose=None):
+                         duration, link_name, obstacle_pose=None, obstacle_twist=None):
         return self._run(_capi.MODE_QPIK_CUBIC, link_name, q, qdot, x_target, xdot_target, x_init, xdot_init,
-                         current_time, init_time, duration, obstacle_pose=obstacle_pose)
+                         current_time, init_time, duration, obstacle_pose=obstacle_pose,
+                         obstacle_twist=obstacle_twist)
 
     def QPIK_rollout_batch(self, q, qdot, x_target, xdot_target, link_name, steps, dt=None, mode="step",
                            x_init=None, xdot_init=None, current_time=0, init_time=0, duration=1,
-                           targets_per_step=False, want=("qdot_traj", "q_traj"), obstacle_pose=None):
+                           targets_per_step=False, want=("qdot_traj", "q_traj"), obstacle_pose=None,
+                           obstacle_twist=None):
         """``steps`` closed-loop cycles of QPIK / QPIKStep / QPIKCubic (``mode``
         "qpik", "step", "cubic") with q += dt * qdot_desired between them
         (fr3_controller.cpp:123-134), on the device: a _batch.RolloutResult.
         ``obstacle_pose`` as for QPIK_step_batch, or with a leading [steps]
-        axis for obstacles that move."""
+        axis for obstacles that move; ``obstacle_twist`` likewise
+        (_batch.obstacle_trajectory gives the poses of a constant twist)."""
         return _rollout(self, self.Kv_task_, q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init,
-                        xdot_init, current_time, init_time, duration, targets_per_step, want, obstacle_pose)
+                        xdot_init, current_time, init_time, duration, targets_per_step, want, obstacle_pose,
+                        obstacle_twist)
 
     def QPIK_reach_batch(self, q, qdot, x_target, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
                          xdot_target=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_FIELDS):

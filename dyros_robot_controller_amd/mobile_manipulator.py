@@ -463,37 +463,46 @@ class RobotController:
 
     # -- batched entries (device tensors, [field][B]; q is the full joint vector)
     def _run(self, mode, link_name, q, qdot, x_target, xdot_target, x_init=None, xdot_init=None,
-             t=0.0, t0=0.0, duration=1.0, iters=None, obstacle_pose=None):
+             t=0.0, t0=0.0, duration=1.0, iters=None, obstacle_pose=None, obstacle_twist=None):
+        if obstacle_twist is not None and obstacle_pose is None:
+            raise ValueError("obstacle_twist without obstacle_pose")
         p = self._pb.params(link_name, mode, self.Kp_task_, np.zeros(6), t, t0, duration)   # no Kv in QPIKStep
         dev = self.robot_data_.device
         return _batch.qpik_batch(self.robot_data_.model, p, _batch.as_device(q, dev), _batch.as_device(qdot, dev),
                                  _batch.as_device(x_target, dev), _batch.as_device(xdot_target, dev),
                                  _batch.as_device(x_init, dev), _batch.as_device(xdot_init, dev), iters=iters,
-                                 obstacle_pose=obstacle_pose)
+                                 obstacle_pose=obstacle_pose, obstacle_twist=obstacle_twist)
 
     # (obstacle_pose: world-frame poses of the model's obstacle slots, RobotData.set_obstacles)
-    def QPIK_batch(self, q, qdot, xdot_target, link_name, obstacle_pose=None):
-        return self._run(_capi.MODE_QPIK, link_name, q, qdot, None, xdot_target, obstacle_pose=obstacle_pose)
+    # (obstacle_twist: their twists, [n][6] or [n][6][B], world frame: the velocity of the
+    # pose origin, then the angular velocity -- the distance row then sees the slot's motion)
+    def QPIK_batch(self, q, qdot, xdot_target, link_name, obstacle_pose=None, obstacle_twist=None):
+        return self._run(_capi.MODE_QPIK, link_name, q, qdot, None, xdot_target, obstacle_pose=obstacle_pose,
+                         obstacle_twist=obstacle_twist)
 
-    def QPIK_step_batch(self, q, qdot, x_target, xdot_target, link_name, iters=None, obstacle_pose=None):
+    def QPIK_step_batch(self, q, qdot, x_target, xdot_target, link_name, iters=None, obstacle_pose=None,
+                        obstacle_twist=None):
         return self._run(_capi.MODE_QPIK_STEP, link_name, q, qdot, x_target, xdot_target, iters=iters,
-                         obstacle_pose=obstacle_pose)
+                         obstacle_pose=obstacle_pose, obstacle_twist=obstacle_twist)
 
     def QPIK_cubic_batch(self, q, qdot, x_target, xdot_target, x_init, xdot_init, current_time, init_time,
-                         duration, link_name, obstacle_pose=None):
+                         duration, link_name, obstacle_pose=None, obstacle_twist=None):
         return self._run(_capi.MODE_QPIK_CUBIC, link_name, q, qdot, x_target, xdot_target, x_init, xdot_init,
-                         current_time, init_time, duration, obstacle_pose=obstacle_pose)
+                         current_time, init_time, duration, obstacle_pose=obstacle_pose,
+                         obstacle_twist=obstacle_twist)
 
     def QPIK_rollout_batch(self, q, qdot, x_target, xdot_target, link_name, steps, dt=None, mode="step",
                            x_init=None, xdot_init=None, current_time=0, init_time=0, duration=1,
-                           targets_per_step=False, want=("qdot_traj", "q_traj"), obstacle_pose=None):
+                           targets_per_step=False, want=("qdot_traj", "q_traj"), obstacle_pose=None,
+                           obstacle_twist=None):
         """``steps`` closed-loop cycles of QPIK / QPIKStep / QPIKCubic (``mode``
         "qpik", "step", "cubic") on the device: qdot = S(q) eta (the virtual
         joints follow Rz(yaw) J_mobile, robot_data.cpp:115-120) and
         q += dt * qdot between them.  Returns a _batch.RolloutResult
         (``qdot_traj``: eta in ActuatorIndex order, as QPIK_step_batch)."""
         return _rollout(self, np.zeros(6), q, qdot, x_target, xdot_target, link_name, steps, dt, mode, x_init,
-                        xdot_init, current_time, init_time, duration, targets_per_step, want, obstacle_pose)
+                        xdot_init, current_time, init_time, duration, targets_per_step, want, obstacle_pose,
+                        obstacle_twist)
 
     def QPIK_reach_batch(self, q, qdot, x_target, link_name, max_steps, dt=None, pos_tol=1e-4, rot_tol=1e-3,
                          xdot_target=None, w_reg=None, obstacle_pose=None, want=_batch.REACH_FIELDS):

@@ -358,6 +358,69 @@ int drc_qpik_rollout_obstacles_batch(const drc_model* model, const drc_qpik_para
                                      double* q_traj, double* pose_traj, double* dist_traj,
                                      void* stream);
 
+/* Moving obstacles: the three obstacle entries with a twist per slot, so that
+ * the distance constraint sees where an obstacle is going and not only where
+ * it is.
+ *   obstacle_twist [n][6][obstacle_ld] (or [n][6] with obstacle_ld = 0), laid
+ *       out like obstacle_pose with 6 values in place of 12: v (3), the velocity
+ *       of the slot pose's origin p, then omega (3), the angular velocity.
+ * Frame: both are expressed in the world frame and v is taken at the pose's
+ * origin -- world-aligned at the local origin, the convention of the frame
+ * Jacobian (LOCAL_WORLD_ALIGNED).  For mobile manipulators it is the world
+ * frame too, like the poses.
+ * With the closest pair's witnesses pA (robot) and pB (obstacle), n = (pB - pA)
+ * / |pB - pA| and s = +1 (d >= 0) or -1 (d < 0),
+ *   dist_rate = dd/dt at rest = s n . (v + omega x (pB - p)),
+ * exact for a half-space too (pB the projection onto the plane), and 0 when a
+ * self pair is the closest.  The QP's distance row becomes
+ *   grad d . qdot (+ slack) >= -alpha_cbf (d - dist_min) - dist_rate;
+ * nothing else changes.  The term reaches the QP as the distance d + dist_rate
+ * / alpha_cbf, so a call with twists needs alpha_cbf > 0
+ * (DRC_ERR_INVALID_ARGUMENT otherwise).  Every distance a caller sees (dist,
+ * dist_traj) stays the geometric d.
+ * Mobile manipulators: the row keeps the reference's arm-only columns; the
+ * base's own motion is not part of it, with or without twists.
+ * obstacle_twist = NULL: the obstacle entry itself, bit for bit (dist_rate 0).
+ * drc_qpik_stages_moving_obstacles_batch: dist_rate [B] (may be NULL) is the
+ * one new output.  drc_qpik_rollout_moving_obstacles_batch: obstacle_twist
+ * gets the leading [steps] axis with obstacles_per_step = 1, like the poses;
+ * bit-identical to `steps` drc_qpik_moving_obstacles_batch calls with the state
+ * update of drc_qpik_rollout_batch.  The poses are the caller's: nothing
+ * integrates them on the device.
+ * Error codes as the obstacle entries (a model without slots, a bad
+ * obstacle_ld: DRC_ERR_INVALID_ARGUMENT); a refused call writes nothing.
+ * The reach entries take one static scene per call and no twists.
+ * (Reference: no counterpart.) */
+int drc_qpik_moving_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                    int64_t B, const double* q, const double* qdot,
+                                    const double* x_target, const double* xdot_target,
+                                    const double* x_init, const double* xdot_init,
+                                    const double* obstacle_pose, const double* obstacle_twist,
+                                    int64_t obstacle_ld, double* qdot_out, int32_t* status,
+                                    int32_t* iters, void* stream);
+int drc_qpik_stages_moving_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                           int64_t B, const double* q, const double* qdot,
+                                           const double* x_target, const double* xdot_target,
+                                           const double* x_init, const double* xdot_init,
+                                           const double* obstacle_pose,
+                                           const double* obstacle_twist, int64_t obstacle_ld,
+                                           double* pose, double* jac, double* man, double* dist,
+                                           int32_t* pair, double* xdot_des, double* dist_rate,
+                                           void* stream);
+int drc_qpik_rollout_moving_obstacles_batch(const drc_model* model, const drc_qpik_params* params,
+                                            int64_t B, int steps, double dt,
+                                            const double* q0, const double* qdot0,
+                                            const double* x_target, const double* xdot_target,
+                                            const double* x_init, const double* xdot_init,
+                                            int targets_per_step,
+                                            const double* obstacle_pose,
+                                            const double* obstacle_twist, int64_t obstacle_ld,
+                                            int obstacles_per_step,
+                                            double* q_final, double* qdot_final,
+                                            double* qdot_traj, int32_t* status_traj,
+                                            int32_t* iters_traj, double* q_traj, double* pose_traj,
+                                            double* dist_traj, void* stream);
+
 /* ---- goal-reaching rollouts: how an instance of drc_qpik_reach_batch stopped */
 enum {
     DRC_REACH_REACHED = 0,       /* pose within pos_tol and rot_tol of x_target        */
