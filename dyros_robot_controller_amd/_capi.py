@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "drc_default_qpik_params", "drc_qpik_batch", "drc_qpik_stages_batch", "drc_debug_kernel_timing", "drc_debug_lds_plan",
     "drc_debug_host_timeline", "drc_debug_waves", "drc_debug_qpik_stamps",
     "drc_debug_kernel_times", "drc_debug_instance_order", "drc_set_concurrency", "drc_set_fusion", "drc_model_release_stream", "drc_debug_lane_stage", "drc_debug_eqp_small_cap",
+    "drc_debug_task_plan_wide",
     "drc_debug_qp_dense", "drc_debug_qp_dense_launches", "drc_qpik_host", "drc_qpik_stages_host",
     "drc_dynamics_batch", "drc_dynamics_host", "drc_joint_torque_step_batch", "drc_joint_torque_step_host",
     "drc_default_qpid_params", "drc_qpid_batch", "drc_qpid_stages_batch", "drc_qpid_host",
@@ -230,6 +231,8 @@ def _load():
     lib.drc_debug_lane_stage.argtypes = [vp, C.c_int]
     if hasattr(lib, "drc_debug_eqp_small_cap"):  # absent from older A/B builds
         lib.drc_debug_eqp_small_cap.argtypes = [vp, C.c_int]
+    if hasattr(lib, "drc_debug_task_plan_wide"):  # absent from older A/B builds
+        lib.drc_debug_task_plan_wide.argtypes = [vp, C.c_int]
     if hasattr(lib, "drc_debug_qp_dense"):  # absent from older A/B builds
         lib.drc_debug_qp_dense.argtypes = [vp, C.c_int]
         lib.drc_debug_qp_dense_launches.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -259,7 +262,7 @@ def _load():
     lib.drc_closed_form_host.argtypes = [vp, C.POINTER(QPIKParams), C.c_int, C.c_int64, dp, dp, dp, dp, dp, dp, dp, dp]
     for name in EXPORTED_SYMBOLS:
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
-                    "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info",
+                    "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info", "drc_debug_task_plan_wide",
                     "drc_mesh_convex_hull", "drc_qpik_rollout_batch") + OBSTACLE_SYMBOLS + MOVING_OBSTACLE_SYMBOLS + REACH_SYMBOLS + REACH_PATH_SYMBOLS \
                 + REACH_SEEDS_SYMBOLS + QP_DENSE_SYMBOLS \
                 and not hasattr(lib, name):

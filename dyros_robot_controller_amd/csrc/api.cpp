@@ -92,6 +92,7 @@ struct drc_model_impl {
   Lanes ln;
   int timing = 0;  // drc_debug_kernel_timing: HIP events around each launch
   int lane_stage = 0;  // drc_debug_lane_stage: 0 off, 1 lane stage + side-stream hard path, 2 + serial hard path, 3 auto
+  bool task_plan_wide = false;  // drc_debug_task_plan_wide: geometry poses outside the polytope overlay
   int eqp_small_cap = -1;  // drc_debug_eqp_small_cap: -1 the compiled tiers, 0 general EQP only, k small EQP for N <= k
   bool qp_dense = false;   // drc_debug_qp_dense: the manipulator shapes' QP kernel with dense G loops
   int64_t qp_dense_launches = 0;
@@ -450,7 +451,9 @@ static int upload(drc_model_impl* m) {
 // per-group instance sequence and LDS plan; parity tests green) but measured
 // slower on FR3: 13.7 M solves/s at two waves per SIMD, 13.4 M at one,
 // against 15.9 M for 64.  The compiled QP shapes: qp_compiled().
-static int plan_layout(const DevModel& M, KParams* k, bool task_only) {
+// (poses_beside: the geometry poses outside the polytope overlay although the plan is narrow; plan_layout
+// lays the plan out again with it when the poses do not fit under the polytope)
+static int plan_layout(const DevModel& M, KParams* k, bool task_only, bool wide, bool poses_beside = false) {
   int off = 0;
   auto take = [&](int n) {
     int o = off;
@@ -458,8 +461,8 @@ static int plan_layout(const DevModel& M, KParams* k, bool task_only) {
     return o;
   };
   const int nx = k->nx, ng = k->ng, np = k->np, m = k->m, nv = M.nv;
-  if (task_only) {  // task_kernel: scalars + kinematics only
-    k->oRed = take(64);
+  if (task_only) {  // task_kernel: scalars + kinematics only (oRed: the winner's two witness points)
+    k->oRed = take(wide ? 64 : 8);
     k->oSc = take(32);
   } else {
   k->oP = take(np * np);
@@ -545,8 +548,15 @@ static int plan_layout(const DevModel& M, KParams* k, bool task_only) {
   k->kZ = takeu((nv + 1) * 3);
   k->kTe = takeu(12);
   k->kJ = takeu(6 * nv);
-  const int ng_ = M.ngeom > nv ? M.ngeom : nv;
-  k->kTg = takeu(ng_ * 12);
+  const int ng_ = M.ngeom > nv ? M.ngeom : nv;  // (nv: the FK's local transforms, loc, use the poses' space first)
+  const bool epa = task_only && !k->cf;
+  // The geometry poses are read by the broad phase and the candidate GJKs;
+  // after those only EPA and the winner's refinement want the poses of one
+  // pair: EPA forms its pair's again in kPp and puts the winner's back in
+  // place when it is done.  So with EPA the poses go into the overlay below,
+  // under polytope fields that are written only once EPA runs.
+  const bool tg_over = epa && !wide && !poses_beside;
+  if (!tg_over) k->kTg = takeu(ng_ * 12);
   k->kq = takeu(nv);
   k->kqd = takeu(nv);
   k->kPd = takeu(M.npairs);
@@ -555,7 +565,11 @@ static int plan_layout(const DevModel& M, KParams* k, bool task_only) {
   k->kmg = takeu(k->narm);
   k->kdg = takeu(nv);
   k->kSv = takeu(3 * kMaxWheels);
-  const bool epa = task_only && !k->cf;
+  // the pose pair of the pair EPA expands (2 x 12).  The QPIK task
+  // stage never stages the mobile Jacobian (QPID's extras and the QP kernels do),
+  // so there the pair takes kSv's place
+  static_assert(3 * kMaxWheels >= 24, "kSv holds the pose pair");
+  k->kPp = epa && k->problem == 1 ? takeu(24) : k->kSv;
   // QPID's task extras read Ai and W after the collision stage
   if (!epa || k->problem == 1) {
     k->kAi = takeu(36);
@@ -589,15 +603,19 @@ static int plan_layout(const DevModel& M, KParams* k, bool task_only) {
   k->kPart = takeu(k->narm * k->narm);
   k->kJt = takeu(6 * np);
   k->kScr = takeu(160);  // serial 6x6 COD work (pinv_cod_serial: 3n^2 + 3n)
+  k->kOvl = 0;
   if (epa) {
     k->kEpa = scr0;
-    const int ep = scr0 + ((static_cast<int>((sizeof(EpaPoly) + 7) / 8) + 1) & ~1);
+    // (wide: the polytope's footprint before its index fields were narrowed, so
+    // that the wide plan has the former size and residency: A/B runs)
+    const int ep = scr0 + (wide ? 1178 : ((static_cast<int>((sizeof(EpaPoly) + 7) / 8) + 1) & ~1));
     u = u > ep ? u : ep;
     // int list of the GJK candidates, in the polytope's face planes (fn, fd):
     // the candidate GJKs write the EPA seed stash (epa_stash: vertex slots
     // kEpaStashV0.., out[], nv) while later candidates are still being read,
     // so the list must not overlap those; the face planes are only written
     // once EPA starts, after the last candidate is consumed
+    static_assert(sizeof(EpaPoly) <= 1178 * 8, "the wide plan's polytope footprint");
     static_assert(offsetof(EpaPoly, fn) % 8 == 0 && offsetof(EpaPoly, fd) == offsetof(EpaPoly, fn) + sizeof(EpaPoly::fn),
                   "face planes: one contiguous double-aligned region");
     static_assert(sizeof(EpaPoly::fn) + sizeof(EpaPoly::fd) >= kMaxPairs * sizeof(int),
@@ -607,7 +625,30 @@ static int plan_layout(const DevModel& M, KParams* k, bool task_only) {
                       offsetof(EpaPoly, nv) > offsetof(EpaPoly, out),
                   "stash (vw / va slots, out[], nv) outside the candidate list");
     k->kCand = scr0 + static_cast<int>(offsetof(EpaPoly, fn) / 8);
+    k->kOvl = scr0;
+    if (tg_over) {
+      // The poses, then the candidate list, from the face planes on.  While the
+      // candidate GJKs read the poses, the stage writes the list (before),
+      // the stash and pd / pf (live region): poses and list may share bytes
+      // only with fields EPA writes later, [fn, out); and the poses start past
+      // the manipulability scratch (kAi .. kScr, written after the poses).
+      static_assert(offsetof(EpaPoly, out) % 8 == 0 && offsetof(EpaPoly, out) > offsetof(EpaPoly, alive) &&
+                        offsetof(EpaPoly, alive) > offsetof(EpaPoly, adj) && offsetof(EpaPoly, hl) > offsetof(EpaPoly, fd) &&
+                        offsetof(EpaPoly, fv) > offsetof(EpaPoly, fd) && offsetof(EpaPoly, freel) > offsetof(EpaPoly, fd) &&
+                        offsetof(EpaPoly, vout) > offsetof(EpaPoly, fd) && offsetof(EpaPoly, vin) > offsetof(EpaPoly, fd) &&
+                        offsetof(EpaPoly, adj) == offsetof(EpaPoly, fd) + sizeof(EpaPoly::fd),
+                    "fn .. alive: the fields EPA writes after the last candidate, then out[] and the counters");
+      const int scr_end = k->kScr + 160;
+      k->kTg = k->kCand > scr_end ? k->kCand : scr_end;
+      k->kCand = k->kTg + ng_ * 12;
+      // the fused kernels' record must leave the poses alone (an instance that
+      // ran no EPA refines its winner on them after the record is written);
+      // the list is dead by then
+      k->kOvl = k->kCand;
+    }
     const int ce = k->kCand + (M.npairs + 1) / 2;
+    if (tg_over && ce > scr0 + static_cast<int>(offsetof(EpaPoly, out) / 8))  // a model with many geometries
+      return plan_layout(M, k, task_only, wide, true);
     u = u > ce ? u : ce;
   } else {
     k->kEpa = 0;
@@ -703,7 +744,7 @@ static int make_kparams(const drc_model_impl* mm, const drc_qpik_params* p, int 
   if (k->nx > 64 || k->ng > 64 || k->narm > 8 || k->m > 128)
     return set_err(DRC_ERR_UNSUPPORTED, "QP larger than one wavefront's row mapping");
   if (k->s.max_iter < 1 || k->s.check_termination < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "bad solver settings");
-  return plan_layout(M, k, stages != 0);
+  return plan_layout(M, k, stages != 0, mm->task_plan_wide);
 }
 
 // (the caller holds m->launch_mu: launch() for one call, the stepwise rollout
@@ -1937,6 +1978,13 @@ int drc_debug_eqp_small_cap(drc_model* m, int cap) {
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
   std::lock_guard<std::mutex> g(m->launch_mu);
   m->eqp_small_cap = cap < 0 ? -1 : cap;
+  return DRC_OK;
+}
+
+int drc_debug_task_plan_wide(drc_model* m, int on) {
+  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  std::lock_guard<std::mutex> g(m->launch_mu);
+  m->task_plan_wide = on != 0;
   return DRC_OK;
 }
 

@@ -59,6 +59,8 @@ struct KParams {
   int oU0;
   int oHi;  // whole-body polish: cached rows of (P + delta I)^-1 (persistent, nx * nx), -1 if unused
   int kT, kZ, kTe, kJ, kTg, kq, kqd, kA6, kAi, kW, kPart, kPd, kPf, kCand, kxdd, kmg, kdg, kJt, kSv, kScr, kEpa;
+  int kPp;   // pose pair (2 x 12) of the pair EPA expands (task_stage.hpp)
+  int kOvl;  // first offset of the task plan's overlay that nothing reads once the task record is written
   int kJd, kDa, kVf, kX6, kBias, kMq, kGq;  // QPID: Jdot, arm-only Jdot, S eta, 6x6 scratch, bias | M, g
   int kGdv;                                 // QPID stage: grad_dot vectors
   int cf;                                   // closed-form controller: 1 CLIK, 2 OSF (task_kernel<2>)
@@ -352,7 +354,7 @@ struct InstSeqG {
 // memory path and its waits) instead of a ds_read / ds_write
 // The fused kernel's LDS: the task plan (kt) and the QP plan (kq) overlay each
 // other from offset 0, and the task record sits where neither stage touches it
-// while the other reads it: in the task plan's overlay region (kEpa: EPA
+// while the other reads it: in the task plan's overlay region (from kOvl: EPA
 // polytope, GJK candidates, manipulability scratch -- dead once the record is
 // written, task_stage.hpp "task data out") when that region lies past the QP
 // plan and holds the record, else past both plans.  Whole-body plans then need
@@ -361,7 +363,7 @@ struct InstSeqG {
 __host__ __device__ __forceinline__ int fused_rec_offset(const KParams& kt, const KParams& kq) {
   const int rec = (kt.rLen + 1) & ~1;
   const int plans = kt.lds_doubles > kq.lds_doubles ? kt.lds_doubles : kq.lds_doubles;
-  const int inside = kt.kEpa > kq.lds_doubles ? kt.kEpa : kq.lds_doubles;
+  const int inside = kt.kOvl > kq.lds_doubles ? kt.kOvl : kq.lds_doubles;
   return kt.kEpa > 0 && inside + rec <= kt.lds_doubles ? inside : plans;
 }
 __host__ __device__ __forceinline__ int fused_lds_doubles(const KParams& kt, const KParams& kq) {

@@ -750,15 +750,19 @@ static_assert(kEpaMaxF <= 256 && kEpaMaxV <= 127, "EpaPoly's 8-bit face and hori
 struct EpaPoly {
   double vw[kEpaMaxV][3], va[kEpaMaxV][3];
   double fn[kEpaMaxF][3], fd[kEpaMaxF];
-  double out[6];
-  // narrow index types (faces < 128, edges < 3, horizon positions < 64): the
-  // polytope is most of the task kernel's per-wave LDS
+  // narrow index types (faces < 128, edges < 3, vertices and horizon positions
+  // < 64): the polytope is most of the task kernel's per-wave LDS
+  // From fn to alive: written only once EPA runs, after the last GJK candidate
+  // is consumed.  The task plan lays the candidate list and the geometry poses
+  // over these fields (api.cpp plan_layout); what the candidate GJKs write
+  // (epa_stash: vertex slots, out[], nv) lies outside them.
   int16_t adj[kEpaMaxF][3];  // neighbour across edge e: face | (its edge << 8)
   int16_t hl[kEpaMaxV];      // a step's horizon edges: face | (edge << 8)
+  uint8_t fv[kEpaMaxF][3];
+  uint8_t freel[kEpaMaxF];  // recycled slots, last freed first
   int8_t vout[kEpaMaxV], vin[kEpaMaxV];  // horizon edge leaving / entering each vertex (-1: none)
-  int16_t fv[kEpaMaxF][3];
-  int16_t freel[kEpaMaxF];  // recycled slots, last freed first
   int8_t alive[kEpaMaxF];
+  double out[6];
   int nv, nf, fail, stop, nfree;
 };
 DRC_HD __forceinline__ V3 epa_vw(const EpaPoly* E, int i) { return v3(E->vw[i][0], E->vw[i][1], E->vw[i][2]); }

@@ -58,6 +58,11 @@ int task_waves_per_simd(int problem, size_t lds) {
     const char* e = std::getenv("DRC_TASK_W3");
     return e ? std::atoi(e) : -1;
   }();
+  // Whole-body plans came under 160 KB / 9 when the geometry poses moved under
+  // the polytope (14.7-15.3 KB from 19.4-20.1 KB: 10-11 waves per CU by LDS), and
+  // the same rule holds for them: B = 65 536, two- against three-wave build,
+  // XLS-FR3 25.38 -> 26.45 M solves/s, Caster-FR3 22.58 -> 23.48, Husky-FR3
+  // 22.28 -> 23.48 (profiles/task_plan_overlay_w3.json)
   const bool w3 = w3_env >= 0 ? w3_env != 0 : lds * 9 <= 160 * 1024;
   return problem == 0 && w3 ? 3 : DRC_TASK_WAVES;
 }

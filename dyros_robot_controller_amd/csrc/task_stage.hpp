@@ -434,6 +434,53 @@ __device__ __forceinline__ bool supports(const AncBits& ab, int k, int j) {
 }
 __device__ __forceinline__ bool revolute(uint32_t rev_mask, int j) { return (rev_mask >> (j - 1)) & 1u; }
 
+// Pose of a geometry (R row-major | p): a link's geometry rides on its joint's
+// frame; an obstacle slot's is the call's pose (R column-major there, no
+// product).  The geometry-pose stage and the pose pairs that EPA and the
+// winner's refinement form again go through these, so that both have the
+// same bits from one source expression.
+__device__ __forceinline__ void link_geom_pose(const double* T, int gpar, const double* gpl, double* dst) {
+  double out[12];
+  tmul(T + 12 * gpar, gpl, out);
+  for (int i = 0; i < 12; ++i) dst[i] = out[i];
+}
+__device__ __forceinline__ void slot_geom_pose(const double* opl, double* dst) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) dst[i] = opl[(i % 3) * 3 + i / 3];
+#pragma unroll
+  for (int i = 9; i < 12; ++i) dst[i] = opl[i];
+}
+
+// The poses of geometries g0 and g1 into d0 and d1 (12 each), by the calling
+// lane (gb: the instance's position in the call's arrays).  Out of line: it is
+// called only in the branch of an instance that runs EPA, and the stage's
+// register allocation should not see it.
+template <bool OBST>
+__device__ __noinline__ void pose_pair(const DevModel* M, const double* T, double* d0, double* d1, int g0, int g1,
+                                       [[maybe_unused]] const ObstIn ob, [[maybe_unused]] int obst0,
+                                       [[maybe_unused]] int64_t gb) {
+  for (int s_ = 0; s_ < 2; ++s_) {
+    const int g = s_ == 0 ? g0 : g1;
+    double* dst = s_ == 0 ? d0 : d1;
+    bool slot = false;
+    if constexpr (OBST) {
+      if (g >= obst0) {  // the call's pose again, as the state-in loads read it
+        slot = true;
+        const int64_t os = ob.ld ? ob.ld : 1;
+        const double* op = ob.pose + (int64_t)(g - obst0) * 12 * os + (ob.ld ? gb : 0);
+        double o[12];
+        for (int i = 0; i < 12; ++i) o[i] = op[i * os];
+        slot_geom_pose(o, dst);
+      }
+    }
+    if (!slot) {
+      double gp[12];
+      for (int i = 0; i < 12; ++i) gp[i] = M->gplace[g][i];
+      link_geom_pose(T, M->gparent[g], gp, dst);
+    }
+  }
+}
+
 // One instance b of the task stage on this wave (S: the wave's LDS plan kp).
 // PROBLEM 0: QPIK stage data; 1: also the QPID extras; 2: closed-form CLIK / OSF.
 // MESH: the model has convex-hull geometry (GeomType kMesh).  A build of its
@@ -574,17 +621,10 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     if constexpr (OBST) {
       if (l >= obst0) {  // the call's pose is the geometry's row (R column-major -> row-major): no tmul
         slot = true;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Tg[l * 12 + i] = opl[(i % 3) * 3 + i / 3];
-#pragma unroll
-        for (int i = 9; i < 12; ++i) Tg[l * 12 + i] = opl[i];
+        slot_geom_pose(opl, Tg + l * 12);
       }
     }
-    if (!slot) {
-      double out[12];
-      tmul(T + 12 * gpar, gpl, out);
-      for (int i = 0; i < 12; ++i) Tg[l * 12 + i] = out[i];
-    }
+    if (!slot) link_geom_pose(T, gpar, gpl, Tg + l * 12);
   }
   PH(0);
   // ---------------- frame Jacobian (LWA), 6 x nv row-major -------------
@@ -809,8 +849,8 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   // (MESH) a hull with its pose, for the whole wave; the broad phase takes a
   // hull for its bounding box (gparam: a lower bound on the box holds for the
   // hull inside it, penetration included)
-  [[maybe_unused]] auto hull_shape = [&](int g) {
-    return ShapeMT<lds_pose*, true>{M->gtype[g], (lds_pose*)(Tg + 12 * g), M->gparam[g][0], M->gparam[g][1],
+  [[maybe_unused]] auto hull_shape = [&](int g, const double* pose) {
+    return ShapeMT<lds_pose*, true>{M->gtype[g], (lds_pose*)pose, M->gparam[g][0], M->gparam[g][1],
                                     M->gparam[g][2], M->mesh_verts + 3 * M->gmesh_first[g], M->gmesh_count[g]};
   };
   const PairTab ptab = pair_tab(M);
@@ -921,7 +961,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       for (int c = 0; c < nhull; ++c) {
         const int p = cand[M->npairs - 1 - c];
         const int ga = M->pair_a[p], gb = M->pair_b[p];
-        const auto A = hull_shape(ga), Bs = hull_shape(gb);
+        const auto A = hull_shape(ga, Tg + 12 * ga), Bs = hull_shape(gb, Tg + 12 * gb);
         const double rs = A.type == kSphere ? A.p0 : (Bs.type == kSphere ? Bs.p0 : 0.0);
         const bool poly = A.type != kCylinder && Bs.type != kCylinder;
         const GjkDist g = gjk_wave(A, Bs, ub + 1e-9 + rs, poly ? 0.0 : kGjkTol, ews, p);
@@ -955,6 +995,12 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   // lane expands the polytope, the whole wave scans for the closest face.
   // (Only pairs whose GJK intersected are searched: none, no search.)
   if (__any(pen)) {
+    // The task plan may lay the polytope over Tg (api.cpp plan_layout): from
+    // here on the poses in Tg are gone.  EPA works on the poses of its pair,
+    // formed again in Pp; after the search the winner's two poses go back to
+    // their places in Tg, where the refinement (and dist_rate) read them as
+    // they do for an instance without EPA.
+    double* Pp = S + kp.kPp;
 #ifdef DRC_EPA_PRIO  // A/B variant: an EPA wave takes issue priority on its SIMD
     __builtin_amdgcn_s_setprio(DRC_EPA_PRIO);
 #endif
@@ -978,13 +1024,15 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       wave_argmin(cpd, cp);
       if (cp == 0x7fffffff || cpd > gbd || (cpd == gbd && cp > gbi)) break;
       const int p = cp, ln = p & 63, ga = M->pair_a[p], gb = M->pair_b[p];
-      const ShapeL A{M->gtype[ga], (lds_pose*)(Tg + 12 * ga), M->gparam[ga][0], M->gparam[ga][1], M->gparam[ga][2]};
-      const ShapeL Bs{M->gtype[gb], (lds_pose*)(Tg + 12 * gb), M->gparam[gb][0], M->gparam[gb][1], M->gparam[gb][2]};
+      if (l == 0) pose_pair<OBST>(M, T, Pp, Pp + 12, ga, gb, ob, obst0, io.b0 + b);  // (the loop's closing barrier: the last pair's readers are done)
+      wsync();
+      const ShapeL A{M->gtype[ga], (lds_pose*)Pp, M->gparam[ga][0], M->gparam[ga][1], M->gparam[ga][2]};
+      const ShapeL Bs{M->gtype[gb], (lds_pose*)(Pp + 12), M->gparam[gb][0], M->gparam[gb][1], M->gparam[gb][2]};
       PH_ONLY(epa_calls++; unsigned long long est[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};)
       const int sk = p == sp0 ? 0 : (p == sp1 ? 1 : -1);
       double dall_;
       if constexpr (MESH) {  // the same EPA with the hulls' cooperative support
-        dall_ = epa_run_wave(hull_shape(ga), hull_shape(gb), ews, ln, sk, sk == 0 ? sn0 : sn1 PH_ONLY(, est));
+        dall_ = epa_run_wave(hull_shape(ga, Pp), hull_shape(gb, Pp + 12), ews, ln, sk, sk == 0 ? sn0 : sn1 PH_ONLY(, est));
         const double rs = A.type == kSphere ? A.p0 : (Bs.type == kSphere ? Bs.p0 : 0.0);
         if (rs > 0) {  // sphere centre inside a hull: the radius comes off, the sphere's witness moves out
           wsync();
@@ -1019,6 +1067,16 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
       if (l == ln) pf[p] = 1;
       wsync();
     }
+    {  // the polytope is dead: the winner's poses back into Tg (the argmin of the lines below)
+      double wd = bestd;
+      int wi = besti;
+      wave_argmin(wd, wi);
+      if (l == 0 && wi < M->npairs) {
+        const int wa = M->pair_a[wi], wb = M->pair_b[wi];
+        pose_pair<OBST>(M, T, Tg + 12 * wa, Tg + 12 * wb, wa, wb, ob, obst0, io.b0 + b);
+      }
+      wsync();
+    }
 #ifdef DRC_EPA_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
@@ -1042,7 +1100,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     V3 rA = ld3(red), rB = ld3(red + 3);
     if constexpr (MESH) {
       if (A.type == kMesh || Bs.type == kMesh) {  // a pair with a hull (refine_witness_hull)
-        if (refine_witness_hull(serial_shape(hull_shape(ga)), serial_shape(hull_shape(gb)), &dref, &rA, &rB)) {
+        if (refine_witness_hull(serial_shape(hull_shape(ga, Tg + 12 * ga)), serial_shape(hull_shape(gb, Tg + 12 * gb)), &dref, &rA, &rB)) {
           st3(red, rA);
           st3(red + 3, rB);
           S[kp.oSc + SC_DIST] = dref;

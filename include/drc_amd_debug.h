@@ -82,6 +82,15 @@ int drc_debug_instance_order(drc_model* model, const int32_t* order, int64_t n);
  * identical inputs and exercise each size boundary. */
 int drc_debug_eqp_small_cap(drc_model* model, int cap);
 
+/* LDS plan of the task kernels that run EPA.  By default the geometry poses
+ * lie under the EPA polytope (EPA and the winner's refinement form the poses
+ * of their pair again), which lets a CU hold more task waves.  With `on` != 0
+ * later calls place the poses beside the polytope and keep the former plan
+ * sizes.  The device code is the same either way and so are the results; the
+ * switch lets tests compare the two layouts on identical inputs and
+ * benchmarks measure what the residency pays. */
+int drc_debug_task_plan_wide(drc_model* model, int on);
+
 /* The dense reference build of the manipulator QP kernels.  The shipped QP
  * code of the fixed-base shapes (FR3, UR5e) visits only the entries of G that
  * qp_assemble can make nonzero; with `on` != 0 a QPIK call of the two-kernel
