@@ -19,6 +19,7 @@
 
 #include "../../include/drc_amd.h"
 #include "../../include/drc_amd_debug.h"
+#include "call_plan.hpp"
 #include "dynamics.hpp"
 #include "kernel_common.hpp"
 #include "launch.hpp"
@@ -48,9 +49,16 @@ struct StreamCtx {
   uint64_t last_use = 0;
   void* pool = nullptr;  // task records / QPID dynamics / OSF M^-1, g
   int64_t pool_bytes = 0;
-  // work-queue counters: [slot][kernel (task, QP)][8 XCD classes]; slots
-  // 0..15 the QPIK sub-batches, 16 QPID, 17 the closed-form controllers
-  static constexpr int kSlotInts = 32;  // task queue 8, QP queue 8, lane-stage hard count 1
+  // work-queue counters, one slot of kSlotInts per launch sequence: slots
+  // 0..15 the QPIK sub-batches, 16 QPID, 17 the closed-form controllers.  In a
+  // slot: the task (or fused) kernel's queue and the QP kernel's, one counter
+  // per XCD class each, then the lane stage's hard count and the order
+  // kernel's hot count
+  static constexpr int kSlotInts = 32, kXcdClasses = 8;
+  static constexpr int kSlotTask = 0, kSlotQp = 8, kSlotHard = 16, kSlotHot = 24;
+  static_assert(kSlotQp >= kSlotTask + kXcdClasses && kSlotHard >= kSlotQp + kXcdClasses && kSlotHot > kSlotHard &&
+                    kSlotHot < kSlotInts,
+                "the users of a queue slot do not overlap and fit it");
   static constexpr int kQueueSlotQpid = 16, kQueueSlotCf = 17, kQueueInts = 18 * kSlotInts;
   int* d_queue = nullptr;
   int* dyn_list = nullptr;  // instances whose M_inv needs the serial COD
@@ -96,9 +104,10 @@ struct drc_model_impl {
   int eqp_small_cap = -1;  // drc_debug_eqp_small_cap: -1 the compiled tiers, 0 general EQP only, k small EQP for N <= k
   bool qp_dense = false;   // drc_debug_qp_dense: the manipulator shapes' QP kernel with dense G loops
   int64_t qp_dense_launches = 0;
-  // timed calls: {caller-stream start, caller-stream end, per chunk: task start, task end, qp end}
-  // timed calls: {call start, call end, task start, task end, QP end of the
-  // sub-batch on the caller's stream} and the call's sub-batch count
+  // timed calls: the events and the call's sub-batch count S.  S > 1: {call
+  // start, call end, then per sub-batch task start, task end, QP end}; S = 1:
+  // {task start, last, task start, task end, last} (last: the QP's end, or the
+  // fused kernel's)
   std::vector<std::pair<std::vector<hipEvent_t>, int>> events;
   std::vector<hipEvent_t> evpool;  // timing events returned by drc_debug_kernel_times, reused
   // concurrent sub-batches: the batch is cut into `chunks` contiguous ranges,
@@ -747,13 +756,89 @@ static int make_kparams(const drc_model_impl* mm, const drc_qpik_params* p, int 
   return plan_layout(M, k, stages != 0, mm->task_plan_wide);
 }
 
+// The record of a call: kernel_common.hpp's IO, filled by field name.  The
+// entries set the caller's arrays; the launch functions add the scratch, the
+// queue and the order of each launch
+static IO make_io(int64_t B) {
+  IO io{};
+  io.B = B;
+  io.b0 = 0;
+  io.ld = B;
+  return io;
+}
+// ... with the six task inputs that every controller entry of the C ABI
+// takes, in the ABI's order.  Everything else is assigned by name
+static IO task_io(int64_t B, const double* q, const double* qdot, const double* xt, const double* xdt,
+                  const double* xi, const double* xdi) {
+  IO io = make_io(B);
+  io.q = q;
+  io.qdot = qdot;
+  io.xt = xt;
+  io.xdt = xdt;
+  io.xi = xi;
+  io.xdi = xdi;
+  return io;
+}
+
+// The inputs a mode needs: the state and xdot_target (state_msg names them as
+// the entry does), x_target for Step / Cubic, x_init / xdot_init for Cubic
+// (family: QPIK or QPID)
+static int check_mode_inputs(const IO& io, int mode, const char* state_msg, const char* family) {
+  if (!io.q || !io.qdot || !io.xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, state_msg);
+  if (mode != DRC_MODE_QPIK && !io.xt)
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   std::string("x_target required for ") + family + "Step/" + family + "Cubic");
+  if (mode == DRC_MODE_QPIK_CUBIC && (!io.xi || !io.xdi))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, std::string("x_init/xdot_init required for ") + family + "Cubic");
+  return DRC_OK;
+}
+
+// The knobs of the dispatch plan (call_plan.hpp), read once
+static const PlanKnobs& plan_knobs() {
+  static const PlanKnobs k = [] {
+    PlanKnobs v;
+    v.fuse_max = env_int("DRC_FUSE_MAX", v.fuse_max, 0);
+    v.order_min = env_int("DRC_ORDER_MIN", v.order_min, 0);
+    v.order_max = env_int("DRC_ORDER_MAX", v.order_max, 0);
+    v.min_subbatch = env_int("DRC_MIN_SUBBATCH", v.min_subbatch, 1);
+    v.grid_task = env_int("DRC_GRID_TASK", v.grid_task, 8);
+    v.grid_qp = env_int("DRC_GRID_QP", v.grid_qp, 8);
+    v.grid_fused = env_int("DRC_GRID_FUSED", v.grid_fused, 8);
+    return v;
+  }();
+  return k;
+}
+// ... and its view of a call of B instances on the model (kq: the QP's
+// parameters, none for a stage call)
+static PlanIn plan_in(const drc_model_impl* m, int64_t B, int stages, const KParams* kq) {
+  const DevModel& dm = m->hm.dev;
+  PlanIn in;
+  in.B = B;
+  in.stages = stages;
+  in.fused = m->fused;
+  in.lane_stage = m->lane_stage;
+  in.chunks = m->chunks;
+  in.caller_order = m->d_order && m->order_n == B;
+  in.kind = dm.kind;
+  in.nv = dm.nv;
+  in.ncand_slots = dm.ncand_slots;
+  in.has_mesh = dm.has_mesh != 0;
+  in.slots = dm.nobst > 0;
+  in.qp_compiled = kq && qp_compiled(kq->nx, kq->ng, kq->np);
+  in.qp_group = kQpGroup;
+  in.max_cand_slots = kMaxCandSlots;
+  in.knobs = plan_knobs();
+  return in;
+}
+
+// One QPIK call (stages: the task stage's outputs only) of call.B instances:
+// the checks, the plan (call_plan.hpp), scratch and streams, then one pass
+// that enqueues each sub-batch.
 // (the caller holds m->launch_mu: launch() for one call, the stepwise rollout
 // for its whole sequence of steps)
-static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int stages, int64_t B, const double* q,
-                         const double* qdot, const double* xt, const double* xdt, const double* xi,
-                         const double* xdi, double* out, int32_t* status, int32_t* iters, double* pose, double* jac,
-                         double* man, double* dist, int32_t* pair, double* xdd, void* stream,
-                         uint64_t* stamps = nullptr, const Obst* ob = nullptr, const Rate* rt = nullptr) {
+static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int stages, const IO& call, void* stream,
+                         const Obst* ob = nullptr, const Rate* rt = nullptr) {
+  const int64_t B = call.B;
   if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   const bool slots = m->hm.dev.nobst > 0;
   if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsPlainMsg);
@@ -764,11 +849,9 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
   if (int r = check_rate(rt, ob, params)) return r;
   if (B == 0) return DRC_OK;
   if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
-  if (!q || !qdot || !xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, "q, qdot and xdot_target are required");
-  if (params->mode != DRC_MODE_QPIK && !xt) return set_err(DRC_ERR_INVALID_ARGUMENT, "x_target required for QPIKStep/QPIKCubic");
-  if (params->mode == DRC_MODE_QPIK_CUBIC && (!xi || !xdi))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "x_init/xdot_init required for QPIKCubic");
-  if (!stages && (!out || !status)) return set_err(DRC_ERR_INVALID_ARGUMENT, "qdot_out and status are required");
+  if (int r = check_mode_inputs(call, params->mode, "q, qdot and xdot_target are required", "QPIK")) return r;
+  if (!stages && (!call.out || !call.status))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "qdot_out and status are required");
   KParams kt, kq;
   int rc = make_kparams(m, params, 1, &kt);
   if (rc) return rc;
@@ -786,42 +869,11 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
   uint8_t* hard_flag = nullptr;  // and its per-instance flags
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
-  // lane-per-instance task stage (lane_task.hpp) for the compiled joint counts
   const DevModel& dm = m->hm.dev;
-  // (3, auto: stage-only calls, where nothing overlaps the task stage.  The
-  // default is 0: a full QPIK call is faster with the wave-per-instance
-  // kernel, which shares the CUs with the QP kernels of the other sub-batches
-  // (DESIGN.md), and stage and QPIK calls then see the same GJK witnesses)
-  const int ls = m->lane_stage;
-  const bool lane = (ls == 1 || ls == 2 || (ls == 3 && stages)) && (dm.nv == 6 || dm.nv == 7) &&
-                    dm.ncand_slots <= kMaxCandSlots && !dm.has_mesh && !slots;
-  // fused up to 16 Ki instances: there a call is a few instances per wave, its
-  // makespan the tail the fused kernel and the EPA-first order below shorten;
-  // at full batch the overlapped sub-batch pipeline wins.  Measured at
-  // B = 16 384 (fused / pipeline): FR3 +10.5 % (+33 % with the order), UR5e
-  // +10 % with the order (-4.1 % without), XLS-FR3 +4.3 %, Husky-FR3 +5.9 %;
-  // B = 32 768: FR3 +3.7 %, UR5e -13 %, XLS-FR3 -12 %; B = 65 536: FR3 -13 %,
-  // UR5e -21 % (profiles/r06t_envab_fuse_*.jsonl, r06x_*, r06y_*).
-  // DRC_FUSE_MAX overrides
-  static const int64_t fuse_max = env_int("DRC_FUSE_MAX", 16384, 0);
-  const bool fuse =
-      m->fused && !stages && !lane && B <= fuse_max && kQpGroup == 64 && qp_compiled(kq.nx, kq.ng, kq.np);
-  // penetration-prone instances first (order_kernel.hip) for calls whose
-  // makespan is the EPA tail: manipulator calls of 2 049 .. 8 192 instances
-  // (DRC_ORDER_MIN / _MAX), and every fused manipulator call above that (FR3
-  // fused at B = 12 288 +38 %, 16 384 +20 %, profiles/r06v_envab_order*.jsonl).
-  // Fewer: the 2 048-wave fused grid starts every instance at once anyway.
-  // Pipeline calls above 8 192: the order gains less than it costs
-  // (profiles/r06f_envab_order_*.jsonl).  Whole-body robots: their predictor
-  // flags ~60 % of the instances, which orders nothing (XLS-FR3 B = 4 096
-  // -2.6 %, profiles/r06j_envab_order_b4096.jsonl; FR3 +15.7 %, UR5e +7.7 %).
-  // A caller's explicit order (drc_debug_instance_order) wins
-  static const int64_t order_max = env_int("DRC_ORDER_MAX", 8192, 0);
-  static const int64_t order_min = env_int("DRC_ORDER_MIN", 2049, 0);
-  const bool dbg_order = m->d_order && m->order_n == B;
-  // (not with obstacle slots: the order kernel's predictor knows no poses)
-  const bool auto_order = !stages && !lane && !dbg_order && !slots && B >= order_min && (B <= order_max || fuse) &&
-                          dm.kind == 0 && dm.ncand_slots > 0 && dm.ncand_slots <= kMaxCandSlots;
+  const PlanIn pin = plan_in(m, B, stages, stages ? nullptr : &kq);
+  const CallPlan plan = plan_call(pin);
+  const bool lane = plan.lane, fuse = plan.fuse, auto_order = plan.auto_order;
+  const int ls = m->lane_stage, S = plan.S;
   int32_t* order_buf = nullptr;
   {
     std::lock_guard<std::mutex> g(m->mu);
@@ -836,20 +888,6 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
       if (auto_order) order_buf = reinterpret_cast<int32_t*>(static_cast<char*>(cx->pool) + ord_off);
     }
   }
-  // sub-batches of >= 4 Ki instances (a chunk of >= 16 Ki keeps the XCD-aware
-  // order; smaller ones run grid-stride order): with one sub-batch the QP
-  // kernel waits for the whole task kernel, with several they overlap
-  // (Husky-FR3's 16 Ki batch)
-  static const int64_t min_sub = env_int("DRC_MIN_SUBBATCH", 4096, 1);
-  int S = 1;
-  if (!stages && !fuse)
-    for (int c = m->chunks; c > 1; --c)
-      // four sub-batches only of >= 16 Ki instances each (Husky-FR3, B = 16 384:
-      // 4 x 4 Ki 10.49 M against 3 x 5.5 Ki 11.14 M solves/s, r04z)
-      if (B / c >= min_sub && (c < 4 || B / c >= 16384)) {
-        S = c;
-        break;
-      }
   const bool timed = m->timing && !stages;
   std::vector<hipEvent_t> tev;
   // (timing events come from the model's pool: creating five to fourteen
@@ -901,43 +939,37 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
   done_guard.forks = &m->ln;  // (launch_mu held: the stream lists do not change under it)
   if (S > 1) HIP_TRY(hipEventRecord(m->ln.fork, st));
   for (int c = 0; c < S; ++c) {
-    const int64_t b0 = B * c / S, b1 = B * (c + 1) / S, Bc = b1 - b0;
+    const SubBatch sb = plan_sub_batch(pin, plan, c);
+    const int64_t b0 = sb.b0, Bc = sb.Bc;
     // the last sub-batch runs on the caller's stream itself: S sub-batches take
     // S streams, so S = 4 still fits HIP's default 4 hardware queues per process
     const bool own = S > 1 && c < S - 1;
     hipStream_t cs = own ? m->ln.lanes[c] : st;
     if (own) HIP_TRY(hipStreamWaitEvent(cs, m->ln.fork, 0));
     KParams kt_c = kt, kq_c = kq;
-    kt_c.xcd_map = kq_c.xcd_map = Bc >= 16384 ? 1 : 0;
-    // persistent grids (work queues hand out the instances): 1 024 task and
-    // 4 096 QP waves per sub-batch.  Re-swept on the r06 kernels (the QP
-    // kernel's instances are now cheaper than the task kernel's): against
-    // 2 048 / 2 048, FR3 +2.8 %, UR5e +2.0 %, XLS-FR3 +1.4 %
-    // (profiles/r06ae_envab_grid.jsonl, r06af_envab_grid2.jsonl); DRC_GRID_TASK
-    // / _QP override for such experiments
-    // (clamped to >= 8 and a multiple of 8: with the XCD-aware order every
-    // residue class blockIdx & 7 needs waves to drain its queue)
-    static const int64_t cap_t = env_int("DRC_GRID_TASK", 1024, 8) & ~int64_t(7);
-    static const int64_t cap_q = env_int("DRC_GRID_QP", 4096, 8) & ~int64_t(7);
-    const int64_t gq = Bc < cap_q ? Bc : cap_q, gt = Bc < cap_t ? Bc : cap_t;
-    IO io{Bc, b0, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, pose, jac, man, dist, xdd, pair,
-          rec ? rec + b0 * stride : nullptr, stride};
-    io.stamps = stages ? nullptr : stamps;
-    io.order = (!stages && !lane && dbg_order) ? m->d_order : nullptr;
+    kt_c.xcd_map = kq_c.xcd_map = sb.xcd_map;
+    const int64_t gq = sb.grid_qp, gt = sb.grid_task;
+    // this sub-batch's record: the caller's arrays, its range, its scratch
+    IO io = call;
+    io.B = Bc;
+    io.b0 = b0;
+    io.rec = rec ? rec + b0 * stride : nullptr;
+    io.rec_stride = stride;
+    if (stages) io.stamps = nullptr;
+    io.order = plan.use_caller_order ? m->d_order : nullptr;
     const ObstIn obin = ob ? *ob : ObstIn();
     const RateIn rtin = rt ? *rt : RateIn();  // (twists: the rate builds; without, the obstacle builds as ever)
     int* qc = cx->d_queue + c * StreamCtx::kSlotInts;  // c < 16 (drc_set_concurrency)
     // the whole slot (128 B, one aligned fill; 17 ints took two fill kernels)
     HIP_TRY(hipMemsetAsync(qc, 0, StreamCtx::kSlotInts * sizeof(int), cs));
-    io.queue = qc;
+    io.queue = qc + StreamCtx::kSlotTask;
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     // kernel timing: every sub-batch's task and QP launches (each marker is a
     // queue packet between two kernels; a call of one sub-batch records two or
     // three: the five of r05 cost 6 % at FR3 B = 4 096.  Timing only the
     // caller-stream sub-batch of a four-sub-batch call saved 1.5 % but its
     // events then disagreed with rocprofv3's kernel averages by ~40 %, r05fin)
-    const bool timed_c = timed;
-    if (timed_c) {
+    if (timed) {
       if (int r = mkev(&e0)) return r;
       if (int r = mkev(&e1)) return r;
       if (!fuse)  // the fused kernel has no QP launch of its own: its end is e1
@@ -962,7 +994,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
       return DRC_OK;
     };
     auto launch_qp = [&]() -> int {
-      io.queue = qc + 8;
+      io.queue = qc + StreamCtx::kSlotQp;
       // compile-time QP shapes of the bundled robots; anything else runs the
       // runtime-sized instantiation (one LDS plan per lane group)
       if (m->qp_dense && dm.kind == 0 && qp_compiled(kq_c.nx, kq_c.ng, kq_c.np)) {  // the dense reference build
@@ -977,37 +1009,35 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     if (order_buf) {  // this sub-batch's order (hot count in the zeroed queue slot; hot list / flags after it)
       int32_t* hl = order_buf + B + b0;
       uint8_t* hf = reinterpret_cast<uint8_t*>(order_buf + 2 * B) + b0;
-      HIP_TRY(static_cast<hipError_t>(launch_order_kernel(Bc, cs, m->d_model, io, qc + 24, hl, hf, order_buf)));
+      HIP_TRY(static_cast<hipError_t>(
+          launch_order_kernel(Bc, cs, m->d_model, io, qc + StreamCtx::kSlotHot, hl, hf, order_buf)));
       io.order = order_buf;
     }
     if (fuse) {  // one fused task + QP kernel, the record in LDS
-      static const int64_t cap_f = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
-      const int64_t gf = Bc < cap_f ? Bc : cap_f;
-      const size_t lds_f =
-          static_cast<size_t>(fused_lds_doubles(kt_c, kq_c)) *
-          sizeof(double);
-      io.queue = qc;
+      const int64_t gf = sb.grid_fused;
+      const size_t lds_f = static_cast<size_t>(fused_lds_doubles(kt_c, kq_c)) * sizeof(double);
+      io.queue = qc + StreamCtx::kSlotTask;
       HIP_TRY(static_cast<hipError_t>(
           slots && rt
               ? launch_fused_rate_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin, rtin)
           : slots ? launch_fused_obstacle_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin)
                   : launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io,
                                         dm.has_mesh != 0)));
-      if (timed_c) HIP_TRY(hipEventRecord(e1, cs));
+      if (timed) HIP_TRY(hipEventRecord(e1, cs));
     } else if (!lane) {  // wave-per-instance task kernel on every instance, then the QP
       if (int r = launch_task(cs)) return r;
-      if (timed_c) HIP_TRY(hipEventRecord(e1, cs));
+      if (timed) HIP_TRY(hipEventRecord(e1, cs));
       if (!stages)
         if (int r = launch_qp()) return r;
     } else {
       // lane stage for every instance; the wave-per-instance task kernel only
       // for the instances it hands back (hard list)
       io.hard_list = hard + b0;
-      io.hard_n = qc + 16;
+      io.hard_n = qc + StreamCtx::kSlotHard;
       io.hard_flag = stages ? nullptr : hard_flag + b0;
       const unsigned gl = static_cast<unsigned>((Bc + 63) / 64);  // one lane per instance
       HIP_TRY(static_cast<hipError_t>(launch_lane_task_kernel(dm.nv, gl, cs, m->d_model, kt_c, io)));
-      if (timed_c) HIP_TRY(hipEventRecord(e1, cs));
+      if (timed) HIP_TRY(hipEventRecord(e1, cs));
       io.hard_mode = 1;
       if (stages || ls != 1) {  // hard task kernel, then one QP pass over every instance
         if (int r = launch_task(cs)) return r;
@@ -1030,7 +1060,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
       }
       io.hard_mode = 0;
     }
-    if (timed_c && !fuse) HIP_TRY(hipEventRecord(e2, cs));
+    if (timed && !fuse) HIP_TRY(hipEventRecord(e2, cs));
     if (own) HIP_TRY(hipEventRecord(m->ln.joins[c], cs));
   }
   for (int c = 0; c < S - 1; ++c) HIP_TRY(hipStreamWaitEvent(st, m->ln.joins[c], 0));
@@ -1044,16 +1074,12 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
   return DRC_OK;
 }
 
-static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int stages, int64_t B, const double* q,
-                  const double* qdot, const double* xt, const double* xdt, const double* xi, const double* xdi,
-                  double* out, int32_t* status, int32_t* iters, double* pose, double* jac, double* man,
-                  double* dist, int32_t* pair, double* xdd, void* stream, uint64_t* stamps = nullptr,
+static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int stages, const IO& call, void* stream,
                   const Obst* ob = nullptr, const Rate* rt = nullptr) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  return launch_locked(m, params, stages, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, pose, jac, man, dist,
-                       pair, xdd, stream, stamps, ob, rt);
+  return launch_locked(m, params, stages, call, stream, ob, rt);
 }
 
 // --------------------------------------------------------------------------
@@ -1103,16 +1129,6 @@ static int make_kparams_pair(const drc_model_impl* m, const drc_qpik_params* par
   return make_kparams(m, params, 0, kq);
 }
 
-// The fusion rule (launch_locked) selects an entry's persistent kernel: the
-// compiled QP shapes up to max_b instances, where the entry has a build that
-// serves the model's hulls / obstacle slots
-static bool persistent_path(const drc_model_impl* m, const KParams& kq, int64_t B, int64_t max_b, bool serves_hulls,
-                            bool serves_slots) {
-  const DevModel& dm = m->hm.dev;
-  return m->fused && m->lane_stage == 0 && B <= max_b && kQpGroup == 64 && qp_compiled(kq.nx, kq.ng, kq.np) &&
-         (serves_slots || dm.nobst == 0) && (serves_hulls || !dm.has_mesh);
-}
-
 // Grows a stream context's scratch block (cx->roll, cx->seeds) to `bytes`; the
 // caller holds m->mu
 static int grow_scratch(void** p, int64_t* have, int64_t bytes) {
@@ -1141,11 +1157,10 @@ struct Carver {
 // the targets, eta / status / iters -- one step's scratch or the trajectories;
 // every other member null)
 static int persistent_setup(StreamCtx* cx, hipStream_t st, KParams* kt, KParams* kq, IO* io, unsigned* grid) {
-  static const int64_t cap = env_int("DRC_GRID_FUSED", 2048, 8) & ~int64_t(7);
-  *grid = static_cast<unsigned>(io->B < cap ? io->B : cap);
-  kt->xcd_map = kq->xcd_map = io->B >= 16384 ? 1 : 0;
-  io->queue = cx->d_queue;  // slot 0, as a fused call's single sub-batch
-  HIP_TRY(hipMemsetAsync(io->queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+  *grid = static_cast<unsigned>(persistent_grid(io->B, plan_knobs().grid_fused));
+  kt->xcd_map = kq->xcd_map = xcd_map_for(io->B);
+  HIP_TRY(hipMemsetAsync(cx->d_queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+  io->queue = cx->d_queue + StreamCtx::kSlotTask;  // slot 0, as a fused call's single sub-batch
   return DRC_OK;
 }
 
@@ -1191,13 +1206,10 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   if (!qf || !vf || !status_traj)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q_final, qdot_final and status_traj are required");
   if (int rc = check_batch(B)) return rc;
-  if (B > 0) {
-    if (!q0 || !qdot0 || !xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0 and xdot_target are required");
-    if (params->mode != DRC_MODE_QPIK && !xt)
-      return set_err(DRC_ERR_INVALID_ARGUMENT, "x_target required for QPIKStep/QPIKCubic");
-    if (params->mode == DRC_MODE_QPIK_CUBIC && (!xi || !xdi))
-      return set_err(DRC_ERR_INVALID_ARGUMENT, "x_init/xdot_init required for QPIKCubic");
-  }
+  // the inputs at step 0: the persistent kernel's record, the template of a step's
+  const IO in = task_io(B, q0, qdot0, xt, xdt, xi, xdi);
+  if (B > 0)
+    if (int rc = check_mode_inputs(in, params->mode, "q0, qdot0 and xdot_target are required", "QPIK")) return rc;
   KParams kt, kq;
   if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (B == 0) return DRC_OK;
@@ -1214,7 +1226,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   // overrides (read per call, so that one process can measure both paths)
   const int64_t rollout_max = env_int("DRC_ROLLOUT_MAX", dm.kind == 0 ? 4096 : 65536, 0);
   // (models with obstacle slots: the stepwise path; no persistent build takes poses)
-  const bool persistent = persistent_path(m, kq, B, rollout_max, true, false);
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), rollout_max, true, false);
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
   double* eta = qdot_traj;  // without qdot_traj: one step's eta in stream scratch
@@ -1228,7 +1240,10 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   }
   const int64_t out_step = qdot_traj ? int64_t(na) * B : 0;
   if (persistent) {
-    IO io{B, 0, B, q0, qdot0, xt, xdt, xi, xdi, eta, status_traj, iters_traj};
+    IO io = in;
+    io.out = eta;
+    io.status = status_traj;
+    io.iters = iters_traj;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_kernel(grid, st, m->d_model, kt, kq, io, steps, per_step, dt, qf, vf,
@@ -1251,17 +1266,22 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     if (rt)  // this step's twists, stepping with the poses
       rt_k = Rate{rt->twist + (ob_per_step ? int64_t(k) * dm.nobst * 6 * (rt->ld ? rt->ld : 1) : 0), rt->ld, nullptr};
     const Rate* rtp = rt ? &rt_k : nullptr;
+    IO step = in;
+    step.q = qk;
+    step.qdot = vk;
+    step.xt = xt_k;
+    step.xdt = xdt_k;
     // (pose_traj / dist_traj: the stage launch without twists -- the geometric d)
-    if (pose_traj || dist_traj)
-      if (int rc = launch_locked(m, &pk, 1, B, qk, vk, xt_k, xdt_k, xi, xdi, nullptr, nullptr, nullptr,
-                                 pose_traj ? pose_traj + int64_t(k) * 12 * B : nullptr, nullptr, nullptr,
-                                 dist_traj ? dist_traj + int64_t(k) * (1 + nv) * B : nullptr, nullptr, nullptr, stream,
-                                 nullptr, obp))
-        return rc;
-    if (int rc = launch_locked(m, &pk, 0, B, qk, vk, xt_k, xdt_k, xi, xdi, eta_k, status_traj + int64_t(k) * B,
-                               iters_traj ? iters_traj + int64_t(k) * B : nullptr, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, stream, nullptr, obp, rtp))
-      return rc;
+    if (pose_traj || dist_traj) {
+      IO sg = step;
+      sg.st_pose = pose_traj ? pose_traj + int64_t(k) * 12 * B : nullptr;
+      sg.st_dist = dist_traj ? dist_traj + int64_t(k) * (1 + nv) * B : nullptr;
+      if (int rc = launch_locked(m, &pk, 1, sg, stream, obp)) return rc;
+    }
+    step.out = eta_k;
+    step.status = status_traj + int64_t(k) * B;
+    step.iters = iters_traj ? iters_traj + int64_t(k) * B : nullptr;
+    if (int rc = launch_locked(m, &pk, 0, step, stream, obp, rtp)) return rc;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_integrate_kernel(
         B, st, m->d_model, dt, qk, eta_k, qf, vf, q_traj ? q_traj + int64_t(k) * nv * B : nullptr)));
   }
@@ -1319,7 +1339,7 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   // measure both paths).  No persistent build has the hull narrow phase or
   // takes obstacle poses
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(m, kq, B, reach_max, false, false);
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, false);
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
   // one step's scratch: eta [na][B], then (stepwise) pose [12][B] and dist
@@ -1339,7 +1359,10 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   const ReachArgs re{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
                      err_final, dist_final};
   if (persistent) {
-    IO io{B, 0, B, q0, qdot0, xt, xdt, nullptr, nullptr, eta, s_status, s_iters};
+    IO io = task_io(B, q0, qdot0, xt, xdt, nullptr, nullptr);
+    io.out = eta;
+    io.status = s_status;
+    io.iters = s_iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(grid, st, m->d_model, kt, kq, io, re)));
@@ -1347,15 +1370,18 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
     return DRC_OK;
   }
   if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, re)) return r;
+  IO qp = task_io(B, qf, vf, xt, xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
+  IO sg = qp;
+  sg.st_pose = s_pose;
+  sg.st_dist = s_dist;
+  qp.out = eta;
+  qp.status = s_status;
+  qp.iters = s_iters;
   for (int k = 0; k <= max_steps; ++k) {
     const int last = k == max_steps;
-    if (int rc = launch_locked(m, params, 1, B, qf, vf, xt, xdt, nullptr, nullptr, nullptr, nullptr, nullptr, s_pose,
-                               nullptr, nullptr, s_dist, nullptr, nullptr, stream, nullptr, ob))
-      return rc;
+    if (int rc = launch_locked(m, params, 1, sg, stream, ob)) return rc;
     if (!last)
-      if (int rc = launch_locked(m, params, 0, B, qf, vf, xt, xdt, nullptr, nullptr, eta, s_status, s_iters, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, stream, nullptr, ob))
-        return rc;
+      if (int rc = launch_locked(m, params, 0, qp, stream, ob)) return rc;
     HIP_TRY(static_cast<hipError_t>(launch_reach_update_kernel(B, st, m->d_model, k, last, re, xt, s_pose, s_dist, eta,
                                                                s_status, s_iters)));
   }
@@ -1431,7 +1457,7 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   // Husky-FR3 129 against 570 ms) and with four slots and one waypoint (FR3 565
   // against 1 786 ms; profiles/reach_path_bench.json, DESIGN.md "Reach paths")
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(m, kq, B, reach_max, false, true);
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, true);
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
   // scratch: one step's eta [na][B], then (stepwise) pose [12][B], dist
@@ -1456,7 +1482,10 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
                           err_final, dist_final},
                          W, x_path, xdot_path, waypoints_reached, dist_min, steps_at, s_xt, s_xdt, s_seg};
   if (persistent) {
-    IO io{B, 0, B, q0, qdot0, x_path, xdot_path, nullptr, nullptr, eta, s_status, s_iters};
+    IO io = task_io(B, q0, qdot0, x_path, xdot_path, nullptr, nullptr);
+    io.out = eta;
+    io.status = s_status;
+    io.iters = s_iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(static_cast<hipError_t>(slots ? launch_reach_path_obstacle_kernel(grid, st, m->d_model, kt, kq, io, rp, *ob)
@@ -1473,15 +1502,18 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   HIP_TRY(hipMemsetAsync(s_seg, 0, size_t(B) * 4, st));
   if (steps_at) HIP_TRY(hipMemsetAsync(steps_at, 0xff, size_t(W) * B * 4, st));  // -1: never reached
   const int64_t rounds = int64_t(W) * (int64_t(max_steps) + 1);
+  IO qp = task_io(B, qf, vf, s_xt, s_xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
+  IO sg = qp;
+  sg.st_pose = s_pose;
+  sg.st_dist = s_dist;
+  qp.out = eta;
+  qp.status = s_status;
+  qp.iters = s_iters;
   for (int64_t r = 0; r <= rounds; ++r) {
     const int last = r == rounds;
-    if (int rc = launch_locked(m, params, 1, B, qf, vf, s_xt, s_xdt, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               s_pose, nullptr, nullptr, s_dist, nullptr, nullptr, stream, nullptr, ob))
-      return rc;
+    if (int rc = launch_locked(m, params, 1, sg, stream, ob)) return rc;
     if (!last)
-      if (int rc = launch_locked(m, params, 0, B, qf, vf, s_xt, s_xdt, nullptr, nullptr, eta, s_status, s_iters,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, nullptr, ob))
-        return rc;
+      if (int rc = launch_locked(m, params, 0, qp, stream, ob)) return rc;
     HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, s_pose, s_dist,
                                                                     eta, s_status, s_iters)));
   }
@@ -1547,7 +1579,7 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   double tau[2];
   reach_thresholds(pos_tol, rot_tol, tau);
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(m, kq, B, reach_max, false, true);
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, true);
   const bool ob_expand = ob && ob->ld != 0;
   StreamCtx* cx = nullptr;
   DoneGuard done_guard{cx, st};
@@ -1594,7 +1626,10 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
                           T, S, rule, persistent && cancel ? 1 : 0, s_word};
   const ReachArgs& re = rs.re;
   if (persistent) {
-    IO io{B, 0, B, q0, qdot0, s_xt, s_xdt, nullptr, nullptr, s_eta, s_status, s_iters};
+    IO io = task_io(B, q0, qdot0, s_xt, s_xdt, nullptr, nullptr);
+    io.out = s_eta;
+    io.status = s_status;
+    io.iters = s_iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(hipMemsetAsync(s_word, 0xff, size_t(T) * 4, st));  // kSeedsNoKey
@@ -1616,23 +1651,20 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
 // data into the records) -> QPID kernel; or, with stages, the task kernel
 // writing the stage outputs.  Model-owned scratch holds the records and the
 // dynamics ([na*na][B] M, [na][B] g, MoMa also [nv][B] joint-order g).
-static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, int stages, int64_t B,
-                       const double* q, const double* qdot, const double* xt, const double* xdt, const double* xi,
-                       const double* xdi, double* qdd, double* tau, int32_t* status, int32_t* iters, double* pose,
-                       double* jac, double* man, double* dist, int32_t* pair, double* xdd, double* jdot,
-                       double* qpid_st, double* gdv, void* stream) {
+// (call: out = qddot, out2 = tau; the stage outputs with st_jdot, st_qpid, st_gdv)
+static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, int stages, const IO& call,
+                       void* stream) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  const int64_t B = call.B;
+  const double *q = call.q, *qdot = call.qdot;
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
   if (m->hm.dev.nobst > 0) return set_err(DRC_ERR_UNSUPPORTED, kSlotsUnsupportedMsg);
-  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (int rc = check_batch(B)) return rc;
   if (B == 0) return DRC_OK;
-  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");
-  if (!q || !qdot || !xdt) return set_err(DRC_ERR_INVALID_ARGUMENT, "q, qdot and xdot_target are required");
-  if (params->mode != DRC_MODE_QPIK && !xt) return set_err(DRC_ERR_INVALID_ARGUMENT, "x_target required for QPIDStep/QPIDCubic");
-  if (params->mode == DRC_MODE_QPIK_CUBIC && (!xi || !xdi))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "x_init/xdot_init required for QPIDCubic");
-  if (!stages && (!qdd || !tau || !status)) return set_err(DRC_ERR_INVALID_ARGUMENT, "qddot_out, tau_out and status are required");
+  if (int r = check_mode_inputs(call, params->mode, "q, qdot and xdot_target are required", "QPID")) return r;
+  if (!stages && (!call.out || !call.out2 || !call.status))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "qddot_out, tau_out and status are required");
   KParams kt, kq;
   int rc = make_kparams(m, params, 1, &kt, 1);
   if (rc) return rc;
@@ -1667,23 +1699,22 @@ static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, 
   }
   const int64_t grid = B < 8192 ? B : 8192;
   KParams kt_c = kt, kq_c = kq;
-  kt_c.xcd_map = kq_c.xcd_map = B >= 16384 ? 1 : 0;
-  IO io{B, 0, B, q, qdot, xt, xdt, xi, xdi, qdd, status, iters, pose, jac, man, dist, xdd, pair, rec, stride};
+  kt_c.xcd_map = kq_c.xcd_map = xcd_map_for(B);
+  IO io = call;
+  io.rec = rec;
+  io.rec_stride = stride;
   io.dM = dM;
   io.dG = dG;
   io.dGf = dGf;
-  io.out2 = tau;
-  io.st_jdot = jdot;
-  io.st_qpid = qpid_st;
-  io.st_gdv = gdv;
   int* qc = cx->d_queue + StreamCtx::kQueueSlotQpid * StreamCtx::kSlotInts;
-  HIP_TRY(hipMemsetAsync(qc, 0, 16 * sizeof(int), st));
-  io.queue = qc;
+  // the task and the QP queue
+  HIP_TRY(hipMemsetAsync(qc, 0, (StreamCtx::kSlotQp + StreamCtx::kXcdClasses) * sizeof(int), st));
+  io.queue = qc + StreamCtx::kSlotTask;
   HIP_TRY(static_cast<hipError_t>(launch_task_kernel(1, static_cast<unsigned>(grid),
                                                      static_cast<size_t>(kt_c.lds_doubles) * sizeof(double), st,
                                                      m->d_model, kt_c, io, m->hm.dev.has_mesh != 0)));
   if (!stages) {
-    io.queue = qc + 8;
+    io.queue = qc + StreamCtx::kSlotQp;
     const size_t lds = static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
     HIP_TRY(static_cast<hipError_t>(launch_qpid_kernel(static_cast<unsigned>(grid), lds, st, m->d_model, kq_c, io)));
   }
@@ -1692,19 +1723,20 @@ static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, 
 }
 
 // Closed-form controllers: [dynamics (OSF: M^-1, g)] -> task_kernel<2>.
-static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* params, int cf, int64_t B,
-                              const double* q, const double* qdot, const double* xt, const double* xdt,
-                              const double* xi, const double* xdi, const double* nullv, double* out, void* stream,
-                              double* pose = nullptr, double* jac = nullptr, double* xdot = nullptr) {
+// (call: cf 1, 2 the targets, cf_null and out; cf 3 the state and st_pose,
+// st_jac, st_xdd = xdot)
+static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* params, int cf, const IO& call,
+                              void* stream) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  const int64_t B = call.B;
+  const double *q = call.q, *qdot = call.qdot;
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
   if (cf != 3 && m->hm.dev.nobst > 0) return set_err(DRC_ERR_UNSUPPORTED, kSlotsUnsupportedMsg);
   if (cf == 3) {  // kinematics only (drc_kinematics_batch): any model kind, no task targets
-    if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+    if (int rc = check_batch(B)) return rc;
     if (B == 0) return DRC_OK;
-    if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");
-    if (!q || (xdot && !qdot)) return set_err(DRC_ERR_INVALID_ARGUMENT, "q (and qdot for xdot) required");
+    if (!q || (call.st_xdd && !qdot)) return set_err(DRC_ERR_INVALID_ARGUMENT, "q (and qdot for xdot) required");
     KParams kt;
     drc_qpik_params pp = *params;
     pp.mode = DRC_MODE_QPIK;
@@ -1719,16 +1751,16 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
       if (int r = stream_ctx(m, st, &cx)) return r;
     }
     const int64_t grid = B < 8192 ? B : 8192;
-    kt.xcd_map = B >= 16384 ? 1 : 0;
+    kt.xcd_map = xcd_map_for(B);
     // qdot may be NULL when xdot is not requested.  The stage still loads a
     // qdot vector (its J qdot product is then discarded, never stored), so q
     // stands in as a readable buffer of the same shape; with xdot requested
     // the caller's qdot is required (checked above)
-    IO io{B, 0, B, q, qdot ? qdot : q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pose, jac,
-          nullptr, nullptr, xdot, nullptr, nullptr, 0};
+    IO io = call;
+    if (!qdot) io.qdot = q;
     // fixed assignment when every wave has one instance: no counter reset to enqueue
-    io.queue = B > grid ? cx->d_queue + StreamCtx::kQueueSlotCf * StreamCtx::kSlotInts : nullptr;
-    if (io.queue) HIP_TRY(hipMemsetAsync(io.queue, 0, 8 * sizeof(int), st));
+    io.queue = B > grid ? cx->d_queue + StreamCtx::kQueueSlotCf * StreamCtx::kSlotInts + StreamCtx::kSlotTask : nullptr;
+    if (io.queue) HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kXcdClasses * sizeof(int), st));
     HIP_TRY(static_cast<hipError_t>(launch_task_kernel(2, static_cast<unsigned>(grid),
                                                        static_cast<size_t>(kt.lds_doubles) * sizeof(double), st,
                                                        m->d_model, kt, io)));
@@ -1736,13 +1768,14 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
     return DRC_OK;
   }
   if (m->hm.dev.kind != 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "CLIK / OSF are Manipulator::RobotController entries");
-  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (int rc = check_batch(B)) return rc;
   if (B == 0) return DRC_OK;
-  if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");
-  if (!q || !qdot || !xdt || !out) return set_err(DRC_ERR_INVALID_ARGUMENT, "q, qdot, xdot_target and out are required");
+  if (!q || !qdot || !call.xdt || !call.out)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "q, qdot, xdot_target and out are required");
   if (cf == 1 && params->mode == DRC_MODE_QPIK) return set_err(DRC_ERR_INVALID_ARGUMENT, "CLIK has Step and Cubic forms only");
-  if (params->mode != DRC_MODE_QPIK && !xt) return set_err(DRC_ERR_INVALID_ARGUMENT, "x_target required");
-  if (params->mode == DRC_MODE_QPIK_CUBIC && (!xi || !xdi)) return set_err(DRC_ERR_INVALID_ARGUMENT, "x_init/xdot_init required");
+  if (params->mode != DRC_MODE_QPIK && !call.xt) return set_err(DRC_ERR_INVALID_ARGUMENT, "x_target required");
+  if (params->mode == DRC_MODE_QPIK_CUBIC && (!call.xi || !call.xdi))
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "x_init/xdot_init required");
   drc_qpik_params pp = *params;
   for (int i = 0; i < 6; ++i) pp.kv[i] = cf == 1 ? 0.0 : params->kv[i];  // CLIK: Kp e + xdot_target (:168)
   pp.feedforward = cf == 1 ? 1.0 : 0.0;                                 // OSF: Kp e + Kv edot (:243)
@@ -1776,14 +1809,12 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
     if (rc) return set_err(DRC_ERR_HIP, std::string("dynamics launch: ") + hipGetErrorString(hipGetLastError()));
   }
   const int64_t grid = B < 8192 ? B : 8192;
-  kt.xcd_map = B >= 16384 ? 1 : 0;
-  IO io{B, 0, B, q, qdot, xt, xdt, xi, xdi, out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-        nullptr, nullptr, 0};
+  kt.xcd_map = xcd_map_for(B);
+  IO io = call;
   io.dM = dMi;
   io.dG = dG;
-  io.cf_null = nullv;
-  io.queue = cx->d_queue + StreamCtx::kQueueSlotCf * StreamCtx::kSlotInts;
-  HIP_TRY(hipMemsetAsync(io.queue, 0, 8 * sizeof(int), st));
+  io.queue = cx->d_queue + StreamCtx::kQueueSlotCf * StreamCtx::kSlotInts + StreamCtx::kSlotTask;
+  HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kXcdClasses * sizeof(int), st));
   HIP_TRY(static_cast<hipError_t>(launch_task_kernel(2, static_cast<unsigned>(grid),
                                                      static_cast<size_t>(kt.lds_doubles) * sizeof(double), st,
                                                      m->d_model, kt, io)));
@@ -2298,8 +2329,11 @@ int drc_default_qpik_params(const drc_model* m, int exact, drc_qpik_params* p) {
 int drc_qpik_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
                    const double* xt, const double* xdt, const double* xi, const double* xdi, double* out,
                    int32_t* status, int32_t* iters, void* stream) {
-  return drc_amd::launch(m, p, 0, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, stream);
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.out = out;
+  io.status = status;
+  io.iters = iters;
+  return drc_amd::launch(m, p, 0, io, stream);
 }
 
 int drc_qpik_rollout_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int steps, double dt,
@@ -2315,8 +2349,14 @@ int drc_qpik_stages_batch(const drc_model* m, const drc_qpik_params* p, int64_t 
                           const double* qdot, const double* xt, const double* xdt, const double* xi,
                           const double* xdi, double* pose, double* jac, double* man, double* dist, int32_t* pair,
                           double* xdd, void* stream) {
-  return drc_amd::launch(m, p, 1, B, q, qdot, xt, xdt, xi, xdi, nullptr, nullptr, nullptr, pose, jac, man, dist,
-                         pair, xdd, stream);
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.st_pose = pose;
+  io.st_jac = jac;
+  io.st_man = man;
+  io.st_dist = dist;
+  io.st_pair = pair;
+  io.st_xdd = xdd;
+  return drc_amd::launch(m, p, 1, io, stream);
 }
 
 // ---- obstacle slots ------------------------------------------------------------
@@ -2351,9 +2391,8 @@ int drc_qpik_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64
                              const double* qdot, const double* xt, const double* xdt, const double* xi,
                              const double* xdi, const double* obstacle_pose, int64_t obstacle_ld, double* out,
                              int32_t* status, int32_t* iters, void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
-  return drc_amd::launch(m, p, 0, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, stream, nullptr, &ob);
+  return drc_qpik_moving_obstacles_batch(m, p, B, q, qdot, xt, xdt, xi, xdi, obstacle_pose, nullptr, obstacle_ld, out,
+                                         status, iters, stream);
 }
 
 int drc_qpik_stages_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
@@ -2361,9 +2400,8 @@ int drc_qpik_stages_obstacles_batch(const drc_model* m, const drc_qpik_params* p
                                     const double* xdi, const double* obstacle_pose, int64_t obstacle_ld,
                                     double* pose, double* jac, double* man, double* dist, int32_t* pair, double* xdd,
                                     void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
-  return drc_amd::launch(m, p, 1, B, q, qdot, xt, xdt, xi, xdi, nullptr, nullptr, nullptr, pose, jac, man, dist,
-                         pair, xdd, stream, nullptr, &ob);
+  return drc_qpik_stages_moving_obstacles_batch(m, p, B, q, qdot, xt, xdt, xi, xdi, obstacle_pose, nullptr, obstacle_ld,
+                                                pose, jac, man, dist, pair, xdd, nullptr, stream);
 }
 
 int drc_qpik_rollout_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int steps, double dt,
@@ -2387,8 +2425,11 @@ int drc_qpik_moving_obstacles_batch(const drc_model* m, const drc_qpik_params* p
                                     int64_t obstacle_ld, double* out, int32_t* status, int32_t* iters, void* stream) {
   const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
   const drc_amd::Rate rt{obstacle_twist, obstacle_ld, nullptr};
-  return drc_amd::launch(m, p, 0, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, stream, nullptr, &ob, obstacle_twist ? &rt : nullptr);
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.out = out;
+  io.status = status;
+  io.iters = iters;
+  return drc_amd::launch(m, p, 0, io, stream, &ob, obstacle_twist ? &rt : nullptr);
 }
 
 int drc_qpik_stages_moving_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
@@ -2399,9 +2440,14 @@ int drc_qpik_stages_moving_obstacles_batch(const drc_model* m, const drc_qpik_pa
                                            void* stream) {
   const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
   const drc_amd::Rate rt{obstacle_twist, obstacle_ld, dist_rate};
-  if (int rc = drc_amd::launch(m, p, 1, B, q, qdot, xt, xdt, xi, xdi, nullptr, nullptr, nullptr, pose, jac, man, dist,
-                               pair, xdd, stream, nullptr, &ob, obstacle_twist ? &rt : nullptr))
-    return rc;
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.st_pose = pose;
+  io.st_jac = jac;
+  io.st_man = man;
+  io.st_dist = dist;
+  io.st_pair = pair;
+  io.st_xdd = xdd;
+  if (int rc = drc_amd::launch(m, p, 1, io, stream, &ob, obstacle_twist ? &rt : nullptr)) return rc;
   if (!obstacle_twist && dist_rate && B > 0) {  // no twist: nothing but the robot moves
     using drc_amd::set_err;
     HIP_TRY(hipSetDevice(m->device));
@@ -2528,16 +2574,29 @@ int drc_default_qpid_params(const drc_model* m, int exact, drc_qpik_params* p) {
 int drc_qpid_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
                    const double* xt, const double* xdt, const double* xi, const double* xdi, double* qddot_out,
                    double* tau_out, int32_t* status, int32_t* iters, void* stream) {
-  return drc_amd::launch_qpid(m, p, 0, B, q, qdot, xt, xdt, xi, xdi, qddot_out, tau_out, status, iters, nullptr,
-                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.out = qddot_out;
+  io.out2 = tau_out;
+  io.status = status;
+  io.iters = iters;
+  return drc_amd::launch_qpid(m, p, 0, io, stream);
 }
 
 int drc_qpid_stages_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
                           const double* qdot, const double* xt, const double* xdt, const double* xi,
                           const double* xdi, double* pose, double* jac, double* man, double* dist, int32_t* pair,
                           double* xddot_des, double* jdot, double* qpid_terms, double* graddot, void* stream) {
-  return drc_amd::launch_qpid(m, p, 1, B, q, qdot, xt, xdt, xi, xdi, nullptr, nullptr, nullptr, nullptr, pose, jac,
-                              man, dist, pair, xddot_des, jdot, qpid_terms, graddot, stream);
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.st_pose = pose;
+  io.st_jac = jac;
+  io.st_man = man;
+  io.st_dist = dist;
+  io.st_pair = pair;
+  io.st_xdd = xddot_des;
+  io.st_jdot = jdot;
+  io.st_qpid = qpid_terms;
+  io.st_gdv = graddot;
+  return drc_amd::launch_qpid(m, p, 1, io, stream);
 }
 
 int drc_qpid_stages_host(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
@@ -2736,11 +2795,21 @@ static int host_call(drc_model* m, const drc_qpik_params* p, int stages, int64_t
     uint64_t* ds = static_cast<uint64_t*>(dout[nouts + niouts]);
     if (ds && hipMemsetAsync(ds, 0, sizeof(uint64_t) * drc_amd::kStamps * B, m->hstream) != hipSuccess)
       return drc_amd::set_err(DRC_ERR_HIP, "hipMemsetAsync(stamps)");
-    if (!stages)
-      return drc_amd::launch(m, p, 0, B, d[0], d[1], d[2], d[3], d[4], d[5], od[0], oi[0], oi[1], nullptr, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, m->hstream, ds);
-    return drc_amd::launch(m, p, 1, B, d[0], d[1], d[2], d[3], d[4], d[5], nullptr, nullptr, nullptr, od[0], od[1],
-                           od[2], od[3], oi[0], od[4], m->hstream);
+    IO io = task_io(B, d[0], d[1], d[2], d[3], d[4], d[5]);
+    if (!stages) {  // outs: qdot_out; iouts: status, iters
+      io.out = od[0];
+      io.status = oi[0];
+      io.iters = oi[1];
+      io.stamps = ds;
+    } else {  // outs: pose, jac, man, dist, xdd; iouts: pair
+      io.st_pose = od[0];
+      io.st_jac = od[1];
+      io.st_man = od[2];
+      io.st_dist = od[3];
+      io.st_xdd = od[4];
+      io.st_pair = oi[0];
+    }
+    return drc_amd::launch(m, p, stages, io, m->hstream);
   };
   return round_trip(m, ha, 6, ho, no, run);
 }
@@ -2848,8 +2917,13 @@ int drc_kinematics_batch(const drc_model* m, int frame_id, int64_t B, const doub
   drc_qpik_params p;
   if (int rc = drc_default_qpik_params(m, 1, &p)) return rc;
   p.frame_id = frame_id;
-  return drc_amd::launch_closed_form(m, &p, 3, B, q, qdot, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     stream, pose, jac, xdot);
+  drc_amd::IO io = drc_amd::make_io(B);
+  io.q = q;
+  io.qdot = qdot;
+  io.st_pose = pose;
+  io.st_jac = jac;
+  io.st_xdd = xdot;
+  return drc_amd::launch_closed_form(m, &p, 3, io, stream);
 }
 
 int drc_state_host(drc_model* m, int frame_id, int64_t B, const double* q, const double* qdot, double* pose,
@@ -2883,13 +2957,19 @@ int drc_state_host(drc_model* m, int frame_id, int64_t B, const double* q, const
 int drc_clik_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
                    const double* xt, const double* xdt, const double* xi, const double* xdi, const double* null_qdot,
                    double* qdot_out, void* stream) {
-  return drc_amd::launch_closed_form(m, p, 1, B, q, qdot, xt, xdt, xi, xdi, null_qdot, qdot_out, stream);
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.cf_null = null_qdot;
+  io.out = qdot_out;
+  return drc_amd::launch_closed_form(m, p, 1, io, stream);
 }
 
 int drc_osf_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
                   const double* xt, const double* xdt, const double* xi, const double* xdi, const double* null_torque,
                   double* tau_out, void* stream) {
-  return drc_amd::launch_closed_form(m, p, 2, B, q, qdot, xt, xdt, xi, xdi, null_torque, tau_out, stream);
+  drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
+  io.cf_null = null_torque;
+  io.out = tau_out;
+  return drc_amd::launch_closed_form(m, p, 2, io, stream);
 }
 
 int drc_closed_form_host(drc_model* m, const drc_qpik_params* p, int kind, int64_t B, const double* q,
@@ -2923,9 +3003,10 @@ int drc_closed_form_host(drc_model* m, const drc_qpik_params* p, int kind, int64
       din[i] = dp;
       dp += rows[i] * B;
     }
-  int rc = drc_amd::launch_closed_form(m, p, kind, B, din[0], din[1], din[2], din[3], din[4], din[5], din[6], dp,
-                                       m->hstream);
-  if (rc) return rc;
+  drc_amd::IO io = drc_amd::task_io(B, din[0], din[1], din[2], din[3], din[4], din[5]);
+  io.cf_null = din[6];
+  io.out = dp;
+  if (int rc = drc_amd::launch_closed_form(m, p, kind, io, m->hstream)) return rc;
   HIP_TRY(hipMemcpyAsync(out, dp, n * B * 8, hipMemcpyDeviceToHost, m->hstream));
   HIP_TRY(hipStreamSynchronize(m->hstream));
   return DRC_OK;

@@ -86,6 +86,14 @@ def test_qpid_stages_match_oracle(cuda, robot):
     a = lambda v: _batch.as_device(v, cuda)
     st = _batch.qpid_stages_batch(rd.model, p, a(q), a(qd), a(xt), a(xdt))
     st = {k: v.cpu().numpy() for k, v in st.items()}
+    # pose, J, manipulability and min distance are the QPIK stage's (drc_qpik_stages_batch, which
+    # tests/test_gpu_task_fixed_stages.py holds against the oracle): the same device functions on the same state,
+    # with contraction fixed per source expression (build.sh), hence the same bits
+    ik = _batch.stages_batch(rd.model, p, a(q), a(qd), a(xt), a(xdt))
+    for k in ("pose", "jac", "man", "dist", "pair"):
+        v = ik[k].cpu().numpy()
+        print("%s %s: max |QPID stage - QPIK stage| %.3e" % (robot, k, np.abs(st[k].astype(float) - v).max()))
+        np.testing.assert_array_equal(st[k], v, err_msg=k)
     _, _, _, diags, om, spec, _ = _oracle(robot, q, qd, xt, xdt)
     nv = om.nv
     for b, dg in enumerate(diags):
