@@ -455,11 +455,9 @@ static int upload(drc_model_impl* m) {
 }
 
 // LDS plan: persistent QP region + a union of (kinematics | K^-1 | polish).
-// Lanes per QP instance: kQpGroup (kernel_common.hpp); 32 packs two instances
-// per wave (Grp<32>: group reductions, DPP / ds_bpermute broadcasts,
-// per-group instance sequence and LDS plan; parity tests green) but measured
-// slower on FR3: 13.7 M solves/s at two waves per SIMD, 13.4 M at one,
-// against 15.9 M for 64.  The compiled QP shapes: qp_compiled().
+// One plan per wave: every QP kernel runs one instance on the 64 lanes of a
+// wave (DESIGN.md "Out of scope" has the two-instances-per-wave build that was
+// tried and removed).  The compiled QP shapes: qp_compiled().
 // (poses_beside: the geometry poses outside the polytope overlay although the plan is narrow; plan_layout
 // lays the plan out again with it when the poses do not fit under the polytope)
 static int plan_layout(const DevModel& M, KParams* k, bool task_only, bool wide, bool poses_beside = false) {
@@ -542,7 +540,7 @@ static int plan_layout(const DevModel& M, KParams* k, bool task_only, bool wide,
     end = end > fac_end ? end : fac_end;
     end = end > reg_pol ? end : reg_pol;
     end = end > lds_pol ? end : lds_pol;
-    k->lds_doubles = (end + 1) & ~1;  // 16-byte aligned: the second lane group's plan follows
+    k->lds_doubles = (end + 1) & ~1;  // 16-byte aligned
     if (end * 8 > 160 * 1024) return set_err(DRC_ERR_UNSUPPORTED, "model too large for the per-wave LDS plan");
     return DRC_OK;
   }
@@ -664,7 +662,7 @@ static int plan_layout(const DevModel& M, KParams* k, bool task_only, bool wide,
     k->kCand = takeu((M.npairs + 1) / 2);
   }
   int kin_end = u;
-  // K^-1, and G K^-1 for the register ADMM (QPIK shapes); QPID runs the LDS path (K^-1 only)
+  // K^-1 (nx * nx); QPIK plans keep the nx * ng doubles past it that the removed non-Schur register ADMM used
   int kinv_end = k->oU0 + nx * nx + (k->problem == 1 ? 0 : nx * ng);
   // polish KKT: free variables + active G rows.  QPID's (<= 81) is capped at 48 —
   // typically 7 qdd + 7 tau + 7 equality rows + the few active CBF rows and free
@@ -825,7 +823,7 @@ static PlanIn plan_in(const drc_model_impl* m, int64_t B, int stages, const KPar
   in.has_mesh = dm.has_mesh != 0;
   in.slots = dm.nobst > 0;
   in.qp_compiled = kq && qp_compiled(kq->nx, kq->ng, kq->np);
-  in.qp_group = kQpGroup;
+  in.qp_group = 64;
   in.max_cand_slots = kMaxCandSlots;
   in.knobs = plan_knobs();
   return in;
@@ -996,7 +994,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     auto launch_qp = [&]() -> int {
       io.queue = qc + StreamCtx::kSlotQp;
       // compile-time QP shapes of the bundled robots; anything else runs the
-      // runtime-sized instantiation (one LDS plan per lane group)
+      // runtime-sized instantiation
       if (m->qp_dense && dm.kind == 0 && qp_compiled(kq_c.nx, kq_c.ng, kq_c.np)) {  // the dense reference build
         HIP_TRY(static_cast<hipError_t>(
             launch_qp_dense_kernel(static_cast<unsigned>(gq), lds_q, cs, m->d_model, kq_c, io)));

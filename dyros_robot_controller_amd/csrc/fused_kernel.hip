@@ -39,7 +39,6 @@ fused_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     for (int e = lane_id(); e < static_cast<int>(sizeof(KParams) / 8); e += 64) dst[e] = src[e];
     wsync();
   }
-  static_assert(QD::gs == 64, "the fused kernel runs one instance per wave");
   static_assert(sizeof...(OB) <= 2, "at most one set of obstacle poses and one of twists");
   const int64_t B = io.B;
   IO iol = io;  // the record lives in LDS: one slot, reused by every instance of the wave

@@ -249,22 +249,23 @@ __device__ void so3_exp(V3 w, double* R) {
 // Compile-time QP dimensions (nx variables, ng general rows, np = leading
 // block of P).  Dims<0,0,0> is the runtime-sized fallback; the named robots
 // get fully unrolled inner products (LDS loads issued ahead of the FMAs).
-// QP shape: compile-time sizes (0 = runtime, from KParams).  reg: the
-// register-resident Ruiz / K^-1 / ADMM path (QPIK shapes); otherwise the LDS
-// path, whose loops still unroll when the sizes are compile-time.
-// schur: the register ADMM solves K x~ = rhs through the Schur complement of
-// K's auxiliary block (every variable past np — slacks — sits in exactly one G
-// row, so that block is diagonal): S = K_cc - K_ca D^-1 K_ac is np x np.
-// gs: lanes per instance (64, or 32 = two instances per wave; the QPIK
-// shapes whose n + NG Schur lanes and polish rows fit in 32).
+// QP shape: compile-time sizes (0 = runtime, from KParams).  Three kinds are
+// instantiated: the QPIK shapes (reg, schur), the QPID shapes (schur) and the
+// runtime-sized Dims<0,0,0> (neither).
+// schur: the ADMM iterations run in registers and solve K x~ = rhs through the
+// Schur complement of K's auxiliary block (every variable past np — slacks —
+// sits in exactly one G row, so that block is diagonal): S = K_cc - K_ca D^-1
+// K_ac is np x np.  Otherwise the LDS loop on K^-1.
+// reg: the Ruiz passes run in registers too, one role per lane (qp_scale_roles,
+// nx + ng <= 64); otherwise in LDS (qp_scale).  Only with schur.
 // dense: the manipulator shapes' reference build, every G loop over the whole
 // matrix (qp_dense_kernel.hip; kQpikSparse in qp_solver.hpp).
-template <int NX, int NG, int NP, bool REG = (NX > 0), bool SCHUR = false, int GS = 64, bool DENSE = false>
+template <int NX, int NG, int NP, bool REG = (NX > 0), bool SCHUR = false, bool DENSE = false>
 struct Dims {
+  static_assert(!REG || SCHUR, "reg shapes run the Schur ADMM");
   static constexpr int nx = NX, ng = NG, np = NP;
   static constexpr bool reg = REG;
   static constexpr bool schur = SCHUR;
-  static constexpr int gs = GS;
   static constexpr bool dense = DENSE;
 };
 #define DNX (QD::nx ? QD::nx : kp.nx)
@@ -304,37 +305,6 @@ struct InstSeq {
     int v = 0;
     if (lane_id() == 0) v = atomicAdd(queue + (map ? xcd : 0), 1);
     return __builtin_amdgcn_readfirstlane(v);
-  }
-  __device__ __forceinline__ int64_t first() const { return queue ? fetch() : j0; }
-  __device__ __forceinline__ int64_t next(int64_t j) const { return queue ? fetch() : j + step; }
-  __device__ __forceinline__ int64_t at(int64_t j) const {
-    return map ? ((((j >> 4) << 3) + xcd) << 4) + (j & 15) : j;
-  }
-};
-
-// InstSeq for lane groups: each group of GS lanes is its own consumer (its
-// leader lane takes the queue position; with a fixed stride the groups of a
-// wave interleave).
-template <int GS>
-struct InstSeqG {
-  int64_t j0, step, n;
-  int xcd, map;
-  int* queue;
-  __device__ __forceinline__ InstSeqG(int64_t B, int map_, int* queue_ = nullptr) {
-    constexpr int G = 64 / GS;
-    const int g = GS == 64 ? 0 : ((threadIdx.x >> 5) & 1);
-    map = map_;
-    queue = queue_;
-    xcd = blockIdx.x & 7;
-    j0 = (map ? (blockIdx.x >> 3) : blockIdx.x) * G + g;
-    step = (map ? (gridDim.x >> 3) : gridDim.x) * G;
-    n = map ? ((B + 127) >> 7) << 4 : B;
-  }
-  __device__ __forceinline__ int64_t fetch() const {
-    int v = 0;
-    if (Grp<GS>::lane() == 0) v = atomicAdd(queue + (map ? xcd : 0), 1);
-    if constexpr (GS == 64) return __builtin_amdgcn_readfirstlane(v);
-    else return Grp<GS>::shfl(v, 0);
   }
   __device__ __forceinline__ int64_t first() const { return queue ? fetch() : j0; }
   __device__ __forceinline__ int64_t next(int64_t j) const { return queue ? fetch() : j + step; }
@@ -453,26 +423,24 @@ enum { ST_TASK0 = 0, ST_TASK1 = 1, ST_QP0 = 2, ST_ASM = 3, ST_SOLVED = 4, ST_OUT
 // Stage stamp k of instance gb (wave-uniform branch; no stamp executes in a
 // call without io.stamps).  The wait keeps the clock read from returning out
 // of order with the LDS reads that follow (cdna_hip_programming.md).
-// Written by the leader of the instance's lane group (every instance of a
-// two-instance QP wave gets its stamps); the host clears the region before the
-// launch and skips instances whose stamps are missing or out of order.
-template <int GS = 64>
+// Written by lane 0 (the & 63 is not folded by the compiler; it stays so that
+// the kernels' code is the measured one); the host clears the region before
+// the launch and skips instances whose stamps are missing or out of order.
 __device__ __forceinline__ void stage_stamp(const IO& io, int k, int64_t gb) {
   if (io.stamps) {
     const uint64_t t = __builtin_amdgcn_s_memrealtime();
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    if ((__lane_id() & (GS - 1)) == 0) io.stamps[k * io.ld + gb] = t;
+    if ((__lane_id() & 63) == 0) io.stamps[k * io.ld + gb] = t;
   }
 }
 // Where the stage of instance gb runs: workgroup index << 32 | __smid() (XCC,
 // SE, CU) << 2 | SIMD (HW_ID bits 5:4) -- drc_debug_qpik_stamps, the
 // small-batch makespan study (tools/stamp_study.py)
-template <int GS = 64>
 __device__ __forceinline__ void stage_where(const IO& io, int k, int64_t gb) {
   if (io.stamps) {
     const uint64_t w = (static_cast<uint64_t>(blockIdx.x) << 32) | (static_cast<uint64_t>(__smid()) << 2) |
                        static_cast<uint64_t>(__builtin_amdgcn_s_getreg(GETREG_IMMED(1, 4, 4)));
-    if ((__lane_id() & (GS - 1)) == 0) io.stamps[k * io.ld + gb] = w;
+    if ((__lane_id() & 63) == 0) io.stamps[k * io.ld + gb] = w;
   }
 }
 
@@ -480,11 +448,10 @@ __device__ __forceinline__ void stage_where(const IO& io, int k, int64_t gb) {
 // model table for the configuration-independent drives; a caster base's
 // depends on the steer angles q[mobi_start + 2i] and is evaluated by lane 0.
 // Wave-uniform call (contains a wave barrier).
-template <int GS = 64>
 __device__ __forceinline__ const double (*mobile_jac(const DevModel* M, const KParams& kp, double* S,
                                                      const double* q))[kMaxWheels] {
   double(*Jm)[kMaxWheels] = reinterpret_cast<double(*)[kMaxWheels]>(S + kp.kSv);
-  const int l = Grp<GS>::lane();
+  const int l = lane_id();
   if (M->drive == kDriveCaster) {
     if (l == 0) mobile_fk(M, q + M->mobi_start, Jm);
   } else if (l < 3 * kMaxWheels) {
@@ -685,12 +652,5 @@ constexpr int kEqpRegCap = 16;
 // KKTs of the manipulator QPIK shapes with at most this many rows (FR3: 96 %
 // of them) are factored whole in every lane's registers.
 constexpr int kEqpSmallCap = 4;
-
-// Lanes per QP instance (qp_kernel): 64, or 32 = two instances per wave
-// (Grp<32>; DESIGN.md: measured slower on FR3, so 64 is the default).
-#ifndef DRC_QP_GROUP
-#define DRC_QP_GROUP 64
-#endif
-constexpr int kQpGroup = DRC_QP_GROUP;
 
 }  // namespace drc_amd

@@ -22,25 +22,25 @@ int qp_waves_per_simd();
 int launch_lane_task_kernel(int nv, unsigned grid, hipStream_t st, const DevModel* m, const KParams& kp,
                             const IO& io);
 // The QPIK shapes with compile-time instantiations (register Schur ADMM), once:
-// calls f with the shape's Dims<..., gs = GS> tag, or returns
+// calls f with the shape's Dims tag, or returns
 // hipErrorInvalidValue for any other shape without calling it.  Every launcher
 // of a compiled kernel dispatches through it, and qp_compiled() asks it
-template <int GS = 64, class F>
+template <class F>
 int with_compiled_shape(int nx, int ng, int np, F&& f) {
   if (nx == 23 && ng == 16 && np == 7)  // FR3
-    f(Dims<23, 16, 7, true, true, GS>{});
+    f(Dims<23, 16, 7, true, true>{});
   else if (nx == 20 && ng == 14 && np == 6)  // UR5e
-    f(Dims<20, 14, 6, true, true, GS>{});
+    f(Dims<20, 14, 6, true, true>{});
   else if (nx == 9 && ng == 16 && np == 9)  // Husky-FR3
-    f(Dims<9, 16, 9, true, true, GS>{});
+    f(Dims<9, 16, 9, true, true>{});
   else if (nx == 11 && ng == 16 && np == 11)  // XLS-FR3
-    f(Dims<11, 16, 11, true, true, GS>{});
+    f(Dims<11, 16, 11, true, true>{});
   else
     return hipErrorInvalidValue;
   return hipSuccess;
 }
 bool qp_compiled(int nx, int ng, int np);
-// qp_kernel for kp's shape; lds = one lane group's plan
+// qp_kernel for kp's shape; lds = the QP plan
 int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io);
 // the two manipulator shapes' dense reference build (qp_dense_kernel.hip;
 // hipErrorInvalidValue for any other shape)

@@ -37,20 +37,16 @@ qp_kernel(const DevModel* __restrict__ M0, const KParams kp, const IO io) {
     for (int e = lane_id(); e < static_cast<int>(sizeof(KParams) / 8); e += 64) dst[e] = src[e];
     wsync();
   }
-  // QD::gs = 32: two instances per wave, each lane group on its own LDS
-  // plan (the launch allocates one per group) and its own instance sequence
-  using GL = Grp<QD::gs>;
-  double* const Sg = S + (GL::upper() ? kp.lds_doubles : 0);
   const int64_t B = io.B;
   // hard_mode 1: the lane stage's hard list (grid stride); 2: every instance
   // except the flagged ones (their records are still being written)
   const bool hl = io.hard_mode == 1;
-  const InstSeqG<QD::gs> seq(hl ? int64_t(*io.hard_n) : B, hl ? 0 : kp.xcd_map, hl ? nullptr : io.queue);
+  const InstSeq seq(hl ? int64_t(*io.hard_n) : B, hl ? 0 : kp.xcd_map, hl ? nullptr : io.queue);
   for (int64_t j = seq.first(); j < seq.n; j = seq.next(j)) {
     const int64_t b = hl ? int64_t(io.hard_list[j]) : seq.at(j);
     if (b >= B) continue;
     if (io.hard_mode == 2 && io.hard_flag[b]) continue;
-    qp_instance<QD>(M0, kp, kpl, io, Sg, b);
+    qp_instance<QD>(M0, kp, kpl, io, S, b);
   }
 }
 
@@ -64,12 +60,11 @@ int qp_waves_per_simd() { return DRC_QP_WAVES; }
 
 int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io) {
   const dim3 g(grid), blk(64);
-  const size_t lg = lds * (64 / kQpGroup);  // one LDS plan per lane group
   // QPIK only: the manipulator shapes' G pattern (kQpikSparse) is qp_assemble's.  The fused, rollout and reach
   // launchers take the same shapes and are QPIK entry points by construction (QPID has qpid_kernel.hip)
   if (kp.problem != 0) return hipErrorInvalidValue;
-  if (with_compiled_shape<kQpGroup>(kp.nx, kp.ng, kp.np, [&](auto qd) {
-        hipLaunchKernelGGL((qp_kernel<decltype(qd)>), g, blk, lg, st, m, kp, io);
+  if (with_compiled_shape(kp.nx, kp.ng, kp.np, [&](auto qd) {
+        hipLaunchKernelGGL((qp_kernel<decltype(qd)>), g, blk, lds, st, m, kp, io);
       }))  // any other model: runtime-sized shapes
     hipLaunchKernelGGL((qp_kernel<Dims<0, 0, 0>>), g, blk, lds, st, m, kp, io);
   return hipGetLastError();
@@ -82,12 +77,11 @@ int launch_qp_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* 
 int launch_qp_dense_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
                            const IO& io) {
   const dim3 g(grid), blk(64);
-  const size_t lg = lds * (64 / kQpGroup);
   if (kp.problem != 0) return hipErrorInvalidValue;  // QPIK only, as launch_qp_kernel
   if (kp.nx == 23 && kp.ng == 16 && kp.np == 7)  // FR3
-    hipLaunchKernelGGL((qp_kernel<Dims<23, 16, 7, true, true, kQpGroup, true>>), g, blk, lg, st, m, kp, io);
+    hipLaunchKernelGGL((qp_kernel<Dims<23, 16, 7, true, true, true>>), g, blk, lds, st, m, kp, io);
   else if (kp.nx == 20 && kp.ng == 14 && kp.np == 6)  // UR5e
-    hipLaunchKernelGGL((qp_kernel<Dims<20, 14, 6, true, true, kQpGroup, true>>), g, blk, lg, st, m, kp, io);
+    hipLaunchKernelGGL((qp_kernel<Dims<20, 14, 6, true, true, true>>), g, blk, lds, st, m, kp, io);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

@@ -1,8 +1,9 @@
 // OSQP ADMM restated for one wavefront per instance:
-// residuals, K factorisations (LDS and register forms, the Schur complement of
-// the slack block), adaptive rho, the certified polish (register / range-space
-// / LDS EQPs), primal infeasibility, and the QP kernel's phases (assembly,
-// Ruiz scaling, the ADMM loop).  Included by qp_kernel.hip and qpid_kernel.hip.
+// residuals, K factorisations (the LDS Gauss-Jordan inverse, the Schur
+// complement of the slack block), adaptive rho, the certified polish (register
+// / range-space / LDS EQPs), primal infeasibility, and the QP kernel's phases
+// (assembly, Ruiz scaling, the ADMM loop).  Included by qp_kernel.hip and
+// qpid_kernel.hip.
 #pragma once
 
 #include "kernel_common.hpp"
@@ -29,7 +30,7 @@ namespace drc_amd {
 // to a sum that fabs closes.
 #ifndef DRC_ADMM_READLANE_BCAST
 template <class QD>
-constexpr bool kQpikSparse = QD::schur && QD::gs == 64 && QD::np > 0 && QD::np < QD::nx && QD::ng == 2 * QD::np + 2 &&
+constexpr bool kQpikSparse = QD::schur && QD::np > 0 && QD::np < QD::nx && QD::ng == 2 * QD::np + 2 &&
                              QD::nx == QD::np + QD::ng && !QD::dense;
 #else
 template <class QD>
@@ -80,10 +81,9 @@ __device__ __forceinline__ double qpik_row_dot(const double* G, const double* x,
 template <class QD, bool UNSCALED = true, bool PRE = false>
 __device__ __forceinline__ void residuals(const KParams& kp, double* S, const double* x, const double* z, const double* y,
                           double eps_abs, double eps_rel, double axb_pre = 0.0, double axg_pre = 0.0) {
-  using GL = Grp<QD::gs>;
   // UNSCALED = false (the polish's certification) skips the unscaled norms
   // that only adaptive rho reads (SC_PRIS .. SC_NQ keep the ADMM values)
-  const int l = GL::lane(), nx = DNX, ng = DNG, np = DNP;
+  const int l = Grp::lane(), nx = DNX, ng = DNG, np = DNP;
   const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *ab = S + kp.oAB, *Di = S + kp.oDi, *Ei = S + kp.oEi;
   double pr = 0, prs = 0, nAx = 0, nz = 0, nAxs = 0, nzs = 0;
   double dr = 0, drs = 0, nPx = 0, nAty = 0, nq = 0, nPxs = 0, nAtys = 0, nqs = 0;
@@ -139,21 +139,21 @@ __device__ __forceinline__ void residuals(const KParams& kp, double* S, const do
     nAxs = fmax(nAxs, fabs(ax));
     nzs = fmax(nzs, fabs(z[row]));
   }
-  pr = GL::max(pr);
-  nAx = GL::max(nAx);
-  nz = GL::max(nz);
-  dr = GL::max(dr);
-  nPx = GL::max(nPx);
-  nAty = GL::max(nAty);
-  nq = GL::max(nq);
+  pr = Grp::max(pr);
+  nAx = Grp::max(nAx);
+  nz = Grp::max(nz);
+  dr = Grp::max(dr);
+  nPx = Grp::max(nPx);
+  nAty = Grp::max(nAty);
+  nq = Grp::max(nq);
   if constexpr (UNSCALED) {
-    prs = GL::max(prs);
-    nAxs = GL::max(nAxs);
-    nzs = GL::max(nzs);
-    drs = GL::max(drs);
-    nPxs = GL::max(nPxs);
-    nAtys = GL::max(nAtys);
-    nqs = GL::max(nqs);
+    prs = Grp::max(prs);
+    nAxs = Grp::max(nAxs);
+    nzs = Grp::max(nzs);
+    drs = Grp::max(drs);
+    nPxs = Grp::max(nPxs);
+    nAtys = Grp::max(nAtys);
+    nqs = Grp::max(nqs);
   }
   const double ci = S[kp.oSc + SC_CINV];
   if (l == 0) {
@@ -181,12 +181,11 @@ __device__ __forceinline__ void residuals(const KParams& kp, double* S, const do
 // qp_scale / qp_residuals do the same.
 template <class QD>
 __device__ __forceinline__ void scaling_inverses(const KParams& kp, double* S) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane(), nx = DNX, m = DM;
+  const int l = Grp::lane(), nx = DNX, m = DM;
   const double *D = S + kp.oD, *E = S + kp.oE;
   double *Di = S + kp.oDi, *Ei = S + kp.oEi;
-  for (int i = l; i < nx; i += GL::size) Di[i] = 1.0 / D[i];
-  for (int i = l; i < m; i += GL::size) Ei[i] = 1.0 / E[i];
+  for (int i = l; i < nx; i += Grp::size) Di[i] = 1.0 / D[i];
+  for (int i = l; i < m; i += Grp::size) Ei[i] = 1.0 / E[i];
   if (l == 0) S[kp.oSc + SC_CINV] = 1.0 / S[kp.oSc + SC_C];
   wsync();
 }
@@ -194,8 +193,7 @@ __device__ __forceinline__ void scaling_inverses(const KParams& kp, double* S) {
 // K = P + sigma I + A^T diag(rho) A, inverted in place (Gauss-Jordan, SPD)
 template <class QD>
 __device__ __forceinline__ void factor_kinv(const KParams& kp, double* S) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane(), nx = DNX, ng = DNG, np = DNP;
+  const int l = Grp::lane(), nx = DNX, ng = DNG, np = DNP;
   const double *P = S + kp.oP, *G = S + kp.oG, *ab = S + kp.oAB, *rho = S + kp.oRho;
   double* K = S + kp.oU0;
   if (l < nx) {
@@ -223,52 +221,6 @@ __device__ __forceinline__ void factor_kinv(const KParams& kp, double* S) {
   }
 }
 
-// Register form for compile-time shapes: lane l assembles row l of K and the
-// Gauss-Jordan sweep runs on registers, the pivot row moving by v_readlane.
-// Same operation sequence as factor_kinv's LDS sweep (bit-identical).
-template <class QD>
-__device__ __noinline__ void factor_kinv_regs(const KParams& kp, double* S) {
-  using GL = Grp<QD::gs>;
-  constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
-  const int l = GL::lane();
-  const double *P = S + kp.oP, *G = S + kp.oG, *ab = S + kp.oAB, *rho = S + kp.oRho;
-  double* K = S + kp.oU0;
-  if (l < NX) {  // row l of K = P + sigma I + A^T diag(rho) A (LDS, as factor_kinv)
-    for (int c = 0; c < NX; ++c) {
-      double s = (l < NP && c < NP) ? P[l * NP + c] : 0.0;
-      if (c == l) s += kp.s.sigma + ab[l] * ab[l] * rho[l];
-      for (int i = 0; i < NG; ++i) s += G[i * NX + l] * rho[NX + i] * G[i * NX + c];
-      K[l * NX + c] = s;
-    }
-  }
-  wsync();
-  const int lr = l < NX ? l : 0;
-  double Kr[NX];
-#pragma unroll
-  for (int c = 0; c < NX; ++c) Kr[c] = K[lr * NX + c];
-#pragma unroll
-  for (int k = 0; k < NX; ++k) {
-    if (l == k) {
-      const double p = 1.0 / Kr[k];
-      Kr[k] = 1.0;
-#pragma unroll
-      for (int j = 0; j < NX; ++j) Kr[j] *= p;
-    }
-    const double f = Kr[k];
-    if (l != k) Kr[k] = 0.0;
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      const double rkj = GL::bcast(Kr[j], k);
-      if (l != k) Kr[j] -= f * rkj;
-    }
-  }
-  if (l < NX) {
-#pragma unroll
-    for (int c = 0; c < NX; ++c) K[l * NX + c] = Kr[c];
-  }
-  wsync();
-}
-
 // ------------------------------------------------------------------------
 // Schur-complement factorisation (QD::schur).  Variables j >= np ("aux":
 // slacks) appear in the cost only linearly and each sits in exactly one G row
@@ -282,13 +234,12 @@ __device__ __noinline__ void factor_kinv_regs(const KParams& kp, double* S) {
 // ------------------------------------------------------------------------
 template <class QD>
 __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
-  using GL = Grp<QD::gs>;
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
-  const int l = GL::lane();
+  const int l = Grp::lane();
   const double *P = S + kp.oP, *G = S + kp.oG, *ab = S + kp.oAB, *rho = S + kp.oRho;
   double* Si = S + kp.oU0;             // NP x NP
-  double* GS = Si + NP * NP;           // NG x NP
-  double* dv = GS + NG * NP;           // NG
+  double* GSi = Si + NP * NP;           // NG x NP
+  double* dv = GSi + NG * NP;           // NG
   double* cf = dv + NG;                // NG
   double* wt = cf + NG;                // NG (row weights w_r)
   int* aux = reinterpret_cast<int*>(wt + NG);  // NG
@@ -320,7 +271,7 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
   wsync();
   PH_SINCE(68, ss_t0);  // row weights
   PH_STAMP(ss_t1);
-  for (int e = l; e < NP * NP; e += GL::size) {  // entry (i, c) of S, one per lane
+  for (int e = l; e < NP * NP; e += Grp::size) {  // entry (i, c) of S, one per lane
     const int i = e / NP, c = e % NP;
     double sv = P[i * NP + c];
     if (c == i) sv += sig + rho[i] * ab[i] * ab[i];
@@ -347,10 +298,9 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
   double Sr[NP];
 #pragma unroll
   for (int c = 0; c < NP; ++c) Sr[c] = Si[lr * NP + c];
-  // the pivot row reaches the lanes through LDS on 64-lane waves (the pivot
-  // lane writes it, every lane reads the same addresses: no VALU broadcasts)
+  // the pivot row reaches the lanes through LDS (the pivot lane writes it,
+  // every lane reads the same addresses: no VALU broadcasts)
   lds_double* bc = (lds_double*)(S + kp.oBc);
-  constexpr bool kLds = QD::gs == 64;
   static_for<NP>([&](auto K) {
     constexpr int k = decltype(K)::value;
     if (l == k) {
@@ -358,22 +308,18 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
       Sr[k] = 1.0;
 #pragma unroll
       for (int j = 0; j < NP; ++j) Sr[j] *= pv;
-      if constexpr (kLds) {
 #pragma unroll
-        for (int j = 0; j < NP; ++j) bc[j] = Sr[j];
-      }
+      for (int j = 0; j < NP; ++j) bc[j] = Sr[j];
     }
-    if constexpr (kLds) asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");
     const double f = Sr[k];
     if (l != k) Sr[k] = 0.0;
     static_for<NP>([&](auto J) {
       constexpr int j = decltype(J)::value;
-      double rkj;
-      if constexpr (kLds) rkj = bc[j];
-      else rkj = GL::template bcastc<k>(Sr[j]);
+      const double rkj = bc[j];
       if (l != k) Sr[j] -= f * rkj;
     });
-    if constexpr (kLds) asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");
   });
   if (l < NP) {
 #pragma unroll
@@ -382,7 +328,7 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
   wsync();
   PH_SINCE(70, ss_t2);  // Gauss-Jordan
   PH_STAMP(ss_t3);
-  for (int e = l; e < NG * NP; e += GL::size) {  // G_c S^-1
+  for (int e = l; e < NG * NP; e += Grp::size) {  // G_c S^-1
     const int r = e / NP, c = e % NP;
     double sv = 0;
     // (dense for every shape: a row r < 2 n has one nonzero term, but the lanes
@@ -390,7 +336,7 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
     // kind runs both forms; DESIGN.md "qp_kernel" has the measurement)
 #pragma unroll
     for (int k = 0; k < NP; ++k) sv += G[r * NX + k] * Si[k * NP + c];
-    GS[e] = sv;
+    GSi[e] = sv;
   }
   wsync();
   PH_SINCE(71, ss_t3);  // G_c S^-1
@@ -399,17 +345,15 @@ __device__ __noinline__ void schur_setup(const KParams& kp, double* S) {
 template <class QD>
 __device__ __forceinline__ void factor_any(const KParams& kp, double* S) {
   if constexpr (QD::schur) schur_setup<QD>(kp, S);
-  else if constexpr (QD::reg) factor_kinv_regs<QD>(kp, S);
   else factor_kinv<QD>(kp, S);
 }
 
 template <class QD>
 __device__ __forceinline__ void set_rho(const KParams& kp, double* S, double rho) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane(), nx = DNX, ng = DNG;
+  const int l = Grp::lane(), nx = DNX, ng = DNG;
   const double *lo = S + kp.oL, *up = S + kp.oU;
   double* rv = S + kp.oRho;
-  for (int row = l; row < nx + ng; row += GL::size) {
+  for (int row = l; row < nx + ng; row += Grp::size) {
     double a = lo[row], b = up[row];
     bool loose = a < -kInf * kMinScaling && b > kInf * kMinScaling;
     bool eq = !loose && b - a < kRhoTol;
@@ -422,13 +366,12 @@ __device__ __forceinline__ void set_rho(const KParams& kp, double* S, double rho
 // Primal infeasibility certificate (OSQP / Banjac et al.) on the last dy
 template <class QD>
 __device__ __forceinline__ bool primal_infeasible(const KParams& kp, double* S, double eps) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane(), nx = DNX, ng = DNG;
+  const int l = Grp::lane(), nx = DNX, ng = DNG;
   const double *lo = S + kp.oL, *up = S + kp.oU, *E = S + kp.oE, *dyv = S + kp.oDY, *G = S + kp.oG,
                *ab = S + kp.oAB, *D = S + kp.oD;
   double* dy = S + kp.oT1;
   double nrm = 0, lhs = 0;
-  for (int row = l; row < nx + ng; row += GL::size) {
+  for (int row = l; row < nx + ng; row += Grp::size) {
     double d = dyv[row], a = lo[row], b = up[row];
     bool lb_inf = a < -kInf * kMinScaling, ub_inf = b > kInf * kMinScaling;
     if (lb_inf && ub_inf) d = 0;
@@ -438,8 +381,8 @@ __device__ __forceinline__ bool primal_infeasible(const KParams& kp, double* S, 
     nrm = fmax(nrm, fabs(E[row] * d));
     lhs += d > 0 ? b * d : (d < 0 ? a * d : 0.0);
   }
-  nrm = GL::max(nrm);
-  lhs = GL::sum(lhs);
+  nrm = Grp::max(nrm);
+  lhs = Grp::sum(lhs);
   wsync();
   if (nrm <= kDivTol || !(lhs < -eps * nrm)) return false;
   double viol = 0;
@@ -452,62 +395,16 @@ __device__ __forceinline__ bool primal_infeasible(const KParams& kp, double* S, 
     }
     viol = fabs(s * S[kp.oDi + l]);
   }
-  viol = GL::max(viol);
+  viol = Grp::max(viol);
   return viol < eps * nrm;
 }
 
-// ------------------------------------------------------------------------
-// Register-resident ADMM (compile-time QP shapes).  Per iteration
-//   rhs = sigma x - q + A^T (rho z - y),  x~ = K^-1 rhs,  G x~ = (G K^-1) rhs,
-// so two broadcast passes (the G-row duals, then rhs) give x~ and the G-row
-// values together.  Lane l keeps column l of G and rows l of K^-1 and
-// G K^-1 in VGPRs; the vectors move by v_readlane (no LDS traffic inside
-// the iteration).  Same algebra as the LDS path, different summation order.
-// ------------------------------------------------------------------------
-
-// G K^-1 (NG x NX) into LDS after K^-1 (once per factorisation; out of line
-// so the ADMM loop's register file stays free)
-template <class QD>
-__device__ __noinline__ void prep_admm_mats(const KParams& kp, double* S) {
-  using GL = Grp<QD::gs>;
-  if constexpr (QD::schur) return;  // schur_setup already formed G_c S^-1
-  constexpr int NX = QD::nx, NG = QD::ng;
-  const int l = GL::lane();
-  const double* K = S + kp.oU0;
-  double* GK = S + kp.oU0 + NX * NX;
-  const double* G = S + kp.oG;
-  for (int e = l; e < NG * NX; e += GL::size) {
-    const int i = e / NX, c = e % NX;
-    double s = 0;
-    for (int k = 0; k < NX; ++k) s += G[i * NX + k] * K[k * NX + c];
-    GK[e] = s;
-  }
-  wsync();
-}
-
-// lane l: column l of G (rhs), row l of K^-1 (x~), row l of G K^-1 (G x~)
-template <class QD>
-__device__ __forceinline__ void load_admm_regs(const KParams& kp, const double* S, double (&Gc)[QD::ng],
-                                               double (&Kr)[QD::nx], double (&GKr)[QD::nx]) {
-  using GL = Grp<QD::gs>;
-  constexpr int NX = QD::nx, NG = QD::ng;
-  const int l = GL::lane();
-  const double* K = S + kp.oU0;
-  const double* GK = S + kp.oU0 + NX * NX;
-  const double* G = S + kp.oG;
-  const int lb = l < NX ? l : 0, lg = l < NG ? l : 0;
-#pragma unroll
-  for (int i = 0; i < NG; ++i) Gc[i] = G[i * NX + lb];
-#pragma unroll
-  for (int c = 0; c < NX; ++c) Kr[c] = K[lb * NX + c];
-#pragma unroll
-  for (int c = 0; c < NX; ++c) GKr[c] = GK[lg * NX + c];
-}
-
-// Termination / polish / adaptive-rho block of the register ADMM, out of
-// line (runs every check_termination iterations).  Works on the published
-// LDS iterate.  Returns 0 = continue, 1 = continue after reloading the
-// registers (K^-1 or rho changed, or the iterate was touched), 2 = stop.
+// Termination / polish / adaptive-rho block of both ADMM loops, out of line
+// (runs every check_termination / adaptive_rho_interval iterations): the one
+// place where a solve is ended.  Works on the iterate in LDS (the Schur loop
+// publishes it before the call; the runtime-sized loop keeps it there).
+// Returns true = stop, with *status set; false = continue (rho, the factor
+// and the failed-polish count in LDS may have changed).
 #ifndef DRC_POLISH_ATTR
 #define DRC_POLISH_ATTR __forceinline__
 #endif
@@ -515,10 +412,8 @@ template <class QD>
 __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict);
 
 template <class QD>
-__device__ __noinline__ int admm_check(const KParams& kp, double* S, int it, int check, int adapt, int* status) {
-  using GL = Grp<QD::gs>;
+__device__ __noinline__ bool admm_check(const KParams& kp, double* S, int it, int check, int adapt, int* status) {
   double *x = S + kp.oX, *z = S + kp.oZ, *y = S + kp.oY, *sc = S + kp.oSc;
-  int reload = 0;
   CK_T0();
   // parity mode: a certified polish is exact whatever the ADMM residual, so
   // the first kPolishMaxEarly checks try it before anything else (converged
@@ -541,14 +436,14 @@ __device__ __noinline__ int admm_check(const KParams& kp, double* S, int it, int
       if (!check) break;
       conv = sc[SC_PRI] < sc[SC_EPSP] && sc[SC_DUA] < sc[SC_EPSD];
 #ifdef DRC_QP_DEBUG
-      if (GL::lane() == 0 && it <= 200)
+      if (Grp::lane() == 0 && it <= 200)
         printf("it %d rho %.4g pri %.3e/%.3e dua %.3e/%.3e x3 %.6f\n", it, sc[SC_RHO], sc[SC_PRI], sc[SC_EPSP],
                sc[SC_DUA], sc[SC_EPSD], x[3] * S[kp.oD + 3]);
 #endif
       if (!conv) break;
       if (!kp.s.exact) {
         *status = DRC_STATUS_SOLVED;
-        return 2;
+        return true;
       }
       try_polish = !early_failed && sc[SC_PFAIL] < kPolishMaxTotal;
     }
@@ -560,15 +455,12 @@ __device__ __noinline__ int admm_check(const KParams& kp, double* S, int it, int
       if (ok_) {
         CK_N(37);
         *status = DRC_STATUS_SOLVED;
-        return 2;
+        return true;
       }
-      if (GL::lane() == 0) sc[SC_PFAIL] += 1.0;
+      if (Grp::lane() == 0) sc[SC_PFAIL] += 1.0;
       factor_any<QD>(kp, S);
       CK_T(38);  // polish used the union region
-      if (round == 0) {
-        early_failed = true;
-        reload = 1;
-      }
+      if (round == 0) early_failed = true;
     }
   }
   if (check) {
@@ -576,12 +468,11 @@ __device__ __noinline__ int admm_check(const KParams& kp, double* S, int it, int
       residuals<QD>(kp, S, x, z, y, kp.s.eps_fallback, kp.s.eps_fallback);
       if (sc[SC_PRI] < sc[SC_EPSP] && sc[SC_DUA] < sc[SC_EPSD]) {
         *status = DRC_STATUS_SOLVED;
-        return 2;
+        return true;
       }
-      reload = 1;
     } else if (primal_infeasible<QD>(kp, S, kp.s.eps_prim_inf)) {
       *status = DRC_STATUS_PRIMAL_INFEASIBLE;
-      return 2;
+      return true;
     }
   }
   if (adapt) {
@@ -594,11 +485,9 @@ __device__ __noinline__ int admm_check(const KParams& kp, double* S, int it, int
       set_rho<QD>(kp, S, rn);
       factor_any<QD>(kp, S);
       CK_T(38);
-      reload = 1;
     }
   }
-  if (reload) prep_admm_mats<QD>(kp, S);
-  return reload;
+  return false;
 }
 
 // argmax with ties toward the smaller index (row order of the oracle scans)
@@ -640,9 +529,8 @@ __device__ __forceinline__ void ldl_solve(const double* L, const double* dg, int
 template <class QD>
 __device__ __forceinline__ bool eqp_regs(const KParams& kp, double* S, int actb, int actg, double* xx, double* yy,
                                          unsigned long long freeMask, unsigned long long rowMask, int nF, int nR) {
-  using GL = Grp<QD::gs>;
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np, M = NX + NG, NK = kEqpRegCap;
-  const int l = GL::lane(), N = nF + nR;
+  const int l = Grp::lane(), N = nF + nR;
   const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL,
                *up = S + kp.oU;
   int* Fidx = reinterpret_cast<int*>(S + kp.oU0);  // 64 ints
@@ -682,7 +570,7 @@ __device__ __forceinline__ bool eqp_regs(const KParams& kp, double* S, int actb,
   }
   const bool hf = l < nF, hr = l >= nF && l < N;
   const int fi = hf ? Fidx[l] : 0, gi = hr ? Ridx[l - nF] : 0;
-  const double rF_ = GL::shfl(rF, fi), rG_ = GL::shfl(rG, gi);
+  const double rF_ = Grp::shfl(rF, fi), rG_ = Grp::shfl(rG, gi);
   const double rhs = hf ? rF_ : (hr ? rG_ : 0.0);
   // row l of K0: columns j < nF are the free variables, j >= nF the active rows
   double K0[NK], Ki[NK];
@@ -712,14 +600,12 @@ __device__ __forceinline__ bool eqp_regs(const KParams& kp, double* S, int actb,
   // Gauss-Jordan inverse of the regularised KKT.  The pivot row and the
   // vectors of the products below reach every lane through LDS (the pivot
   // lane / the owners write, every lane reads the same addresses): no VALU
-  // broadcast instructions, same values, same products (64-lane waves; a
-  // lane group of 32 keeps the register broadcasts)
+  // broadcast instructions, same values, same products
   lds_double* bc = (lds_double*)(S + kp.oBc);
-  constexpr bool kLds = QD::gs == 64;
 #pragma unroll
   for (int k = 0; k < NK; ++k) {
     if (k >= N) break;
-    const double piv = GL::bcast(Ki[k], k);
+    const double piv = Grp::bcast(Ki[k], k);
     if (piv == 0.0) return false;  // uniform
     if (l == k) {
       const double p = 1.0 / Ki[k];
@@ -729,43 +615,35 @@ __device__ __forceinline__ bool eqp_regs(const KParams& kp, double* S, int actb,
         if (j >= N) break;
         Ki[j] *= p;
       }
-      if constexpr (kLds) {
 #pragma unroll
-        for (int j = 0; j < NK; ++j) {
-          if (j >= N) break;
-          bc[j] = Ki[j];
-        }
+      for (int j = 0; j < NK; ++j) {
+        if (j >= N) break;
+        bc[j] = Ki[j];
       }
     }
-    if constexpr (kLds) asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");
     const double f = Ki[k];
     if (l != k) Ki[k] = 0.0;
 #pragma unroll
     for (int j = 0; j < NK; ++j) {
       if (j >= N) break;
-      double rkj;
-      if constexpr (kLds) rkj = bc[j];
-      else rkj = GL::bcast(Ki[j], k);
+      const double rkj = bc[j];
       if (l != k) Ki[j] -= f * rkj;
     }
-    if constexpr (kLds) asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");
   }
   auto apply = [&](const double (&A)[NK], double v) {  // row l of A times the vector held by lanes 0..N-1
-    if constexpr (kLds) {
-      if (l < N) bc[l] = v;
-      asm volatile("" ::: "memory");
-    }
+    if (l < N) bc[l] = v;
+    asm volatile("" ::: "memory");
     double s0 = 0, s1 = 0;
 #pragma unroll
     for (int j = 0; j < NK; ++j) {
       if (j >= N) break;
-      double vj;
-      if constexpr (kLds) vj = bc[j];
-      else vj = GL::bcast(v, j);
+      const double vj = bc[j];
       if (j & 1) s1 += A[j] * vj;
       else s0 += A[j] * vj;
     }
-    if constexpr (kLds) asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");
     return s0 + s1;
   };
   PH_SINCE(53, er_t1);
@@ -778,7 +656,7 @@ __device__ __forceinline__ bool eqp_regs(const KParams& kp, double* S, int actb,
   PH_SINCE(54, er_t2);
   PH_STAMP(er_t3);
   if (hf) xx[fi] = sol;
-  for (int row = l; row < M; row += GL::size) yy[row] = 0.0;
+  for (int row = l; row < M; row += Grp::size) yy[row] = 0.0;
   wsync();
   if (hr) yy[NX + gi] = sol;
   wsync();
@@ -820,14 +698,13 @@ __device__ __forceinline__ bool eqp_regs(const KParams& kp, double* S, int actb,
 // elsewhere); the bound multipliers of the fixed variables are formed by
 // polish_pass_small, with the candidate and the residuals.
 template <class QD>
-constexpr bool kEqpSmallShape = QD::nx > 0 && QD::np < QD::nx && QD::gs == 64;
+constexpr bool kEqpSmallShape = QD::nx > 0 && QD::np < QD::nx;
 
 template <class QD, int NS>
 __device__ __forceinline__ bool eqp_small(const KParams& kp, double* S, int actb, int actg, double* xx, double* yy,
                                           unsigned long long freeMask, unsigned long long rowMask, int nF, int nR) {
-  using GL = Grp<QD::gs>;
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
-  const int l = GL::lane(), N = nF + nR;
+  const int l = Grp::lane(), N = nF + nR;
   const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *lo = S + kp.oL, *up = S + kp.oU;
   double vF = 0.0, vR = 0.0;  // this lane's solution entries: free variable l, active G row l
   if (N > 0) {
@@ -873,7 +750,7 @@ __device__ __forceinline__ bool eqp_small(const KParams& kp, double* S, int actb
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       const bool fi = i < nF, ri = !fi && i < N;
-      const double a = GL::bcast(rF, idx[i]), b = GL::bcast(rG, idx[i]);
+      const double a = Grp::bcast(rF, idx[i]), b = Grp::bcast(rG, idx[i]);
       rhs[i] = fi ? a : (ri ? b : 0.0);
       reg[i] = eqp_small_reg(i, nF, N, kp.s.delta);
 #pragma unroll
@@ -923,12 +800,11 @@ template <class QD, int NS>
 __device__ __forceinline__ void polish_pass_small(const KParams& kp, double* S, int actb, int actg, const double* xx,
                                                   double* yy, double* zz, double eps, double& axb, double& axg,
                                                   double& pr1, double& dr1, double& epsp, double& epsd) {
-  using GL = Grp<QD::gs>;
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
-  const int l = GL::lane();
+  const int l = Grp::lane();
   const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU,
                *Di = S + kp.oDi, *Ei = S + kp.oEi;
-  const unsigned long long rowMask = GL::ballot(l < NG && actg != 0);
+  const unsigned long long rowMask = Grp::ballot(l < NG && actg != 0);
   double mx[7] = {0, 0, 0, 0, 0, 0, 0};  // pr, nAx, nz, dr, nPx, nAty, nq
   axb = 0.0;
   axg = 0.0;
@@ -980,7 +856,7 @@ __device__ __forceinline__ void polish_pass_small(const KParams& kp, double* S, 
     mx[1] = fmax(mx[1], fabs(axg * ei));
     mx[2] = fmax(mx[2], fabs(zg * ei));
   }
-  // seven maxima, reduced side by side (fmax is exact: same values as seven GL::max)
+  // seven maxima, reduced side by side (fmax is exact: same values as seven Grp::max)
 #pragma unroll
   for (int k = 0; k < 7; ++k) mx[k] = fmax(mx[k], dpp_d<kDppQuad1032>(mx[k]));
 #pragma unroll
@@ -1014,7 +890,7 @@ template <class QD>
 __device__ __forceinline__ bool eqp_range(const KParams& kp, double* S, int actg, double* xx, double* yy,
                                           unsigned long long rowMask, int nR) {
   constexpr int NX = QD::nx, NG = QD::ng, M = NX + NG, NK = kEqpRegCap;
-  static_assert(NX + NK <= 64 && QD::gs == 64, "x lanes and active-row lanes in one wave");
+  static_assert(NX + NK <= 64, "x lanes and active-row lanes in one wave");
   const int l = lane_id();
   const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *lo = S + kp.oL, *up = S + kp.oU;
   double* Hi = S + kp.oHi;
@@ -1184,12 +1060,11 @@ __device__ __forceinline__ bool eqp_range(const KParams& kp, double* S, int actg
 template <class QD>
 __device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int actg, double* xx, double* yy,
                                     bool& small) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane(), nx = DNX, ng = DNG, np = DNP, m = DM;
+  const int l = Grp::lane(), nx = DNX, ng = DNG, np = DNP, m = DM;
   const double *P = S + kp.oP, *G = S + kp.oG, *q = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL,
                *up = S + kp.oU;
-  unsigned long long freeMask = GL::ballot(l < nx && actb == 0);
-  unsigned long long rowMask = GL::ballot(l < ng && actg != 0);
+  unsigned long long freeMask = Grp::ballot(l < nx && actb == 0);
+  unsigned long long rowMask = Grp::ballot(l < ng && actg != 0);
   const int nF = __popcll(freeMask), nR = __popcll(rowMask), N = nF + nR;
   if (N > kp.ncap) return false;  // uniform: this polish attempt fails, ADMM continues
   PH_STAMP(eq_t0);
@@ -1205,10 +1080,7 @@ __device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int 
       return ok_;
     }
   }
-  if constexpr (QD::gs < 64) {  // two instances per wave: register EQP only (ncap <= kEqpRegCap)
-    if (N > kEqpRegCap) return false;
-  }
-  if constexpr (QD::nx > 0 && QD::nx == QD::np && QD::gs == 64) {  // whole-body shapes: range-space form
+  if constexpr (QD::nx > 0 && QD::nx == QD::np) {  // whole-body shapes: range-space form
     if (kp.oHi >= 0 && nF == QD::nx && nR <= kEqpRegCap) {
       const bool ok_ = eqp_range<QD>(kp, S, actg, xx, yy, rowMask, nR);
       PH_SINCE(40, eq_t0);
@@ -1238,7 +1110,7 @@ __device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int 
   if (l < nx) xx[l] = actb == 0 ? 0.0 : (actb < 0 ? lo[l] : up[l]) / ab[l];
   wsync();
   const double dl = kp.s.delta;
-  for (int i = l; i < N; i += GL::size) {  // K (packed rows i >= j) and rhs; lane i owns row i
+  for (int i = l; i < N; i += Grp::size) {  // K (packed rows i >= j) and rhs; lane i owns row i
     if (i < nF) {
       int fi = Fidx[i];
       for (int j = 0; j <= i; ++j) {
@@ -1271,13 +1143,13 @@ __device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int 
   }
   wsync();
   for (int j = 0; j < N; ++j) {  // left-looking LDL^T, in place
-    for (int k = l; k < j; k += GL::size) vv[k] = L[pk(j, k)] * dg[k];
+    for (int k = l; k < j; k += Grp::size) vv[k] = L[pk(j, k)] * dg[k];
     wsync();
     double part = 0;
-    for (int k = l; k < j; k += GL::size) part += L[pk(j, k)] * vv[k];
-    double dj = L[pk(j, j)] - GL::sum(part);
+    for (int k = l; k < j; k += Grp::size) part += L[pk(j, k)] * vv[k];
+    double dj = L[pk(j, j)] - Grp::sum(part);
     if (dj == 0.0) return false;  // uniform
-    for (int i = l; i < N; i += GL::size)
+    for (int i = l; i < N; i += Grp::size)
       if (i > j) {
         double t = L[pk(i, j)];
         for (int k = 0; k < j; ++k) t -= L[pk(i, k)] * vv[k];
@@ -1286,11 +1158,11 @@ __device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int 
     if (l == 0) dg[j] = dj;
     wsync();
   }
-  for (int i = l; i < N; i += GL::size) sol[i] = rhs[i];
+  for (int i = l; i < N; i += Grp::size) sol[i] = rhs[i];
   wsync();
   ldl_solve(L, dg, N, sol);
   for (int it = 0; it < kp.s.polish_refine_iter; ++it) {
-    for (int i = l; i < N; i += GL::size) {
+    for (int i = l; i < N; i += Grp::size) {
       double r = rhs[i];
       if (i < nF) {
         int fi = Fidx[i];
@@ -1308,13 +1180,13 @@ __device__ __forceinline__ bool eqp(const KParams& kp, double* S, int actb, int 
     }
     wsync();
     ldl_solve(L, dg, N, res);
-    for (int i = l; i < N; i += GL::size) sol[i] += res[i];
+    for (int i = l; i < N; i += Grp::size) sol[i] += res[i];
     wsync();
   }
-  for (int i = l; i < nF; i += GL::size) xx[Fidx[i]] = sol[i];
-  for (int row = l; row < m; row += GL::size) yy[row] = 0.0;
+  for (int i = l; i < nF; i += Grp::size) xx[Fidx[i]] = sol[i];
+  for (int row = l; row < m; row += Grp::size) yy[row] = 0.0;
   wsync();
-  for (int k = l; k < nR; k += GL::size) yy[nx + Ridx[k]] = sol[nF + k];
+  for (int k = l; k < nR; k += Grp::size) yy[nx + Ridx[k]] = sol[nF + k];
   wsync();
   if (l < nx && actb != 0) {  // bound multipliers from stationarity
     double g = q[l];
@@ -1338,8 +1210,7 @@ constexpr int kPolishFeasAttempts = 6, kPolishAsIters = 24, kPolishJacobiSweeps 
 constexpr double kPolishSlackTol = 0.3;
 template <class QD>
 __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane(), nx = DNX, ng = DNG, np = DNP, m = DM;
+  const int l = Grp::lane(), nx = DNX, ng = DNG, np = DNP, m = DM;
   const double *G = S + kp.oG, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU, *E = S + kp.oE;
   double *x = S + kp.oX, *z = S + kp.oZ, *y = S + kp.oY;
   int ob = 0, og = 0;  // OSQP's guess
@@ -1428,7 +1299,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
   // instance then ran 1 400 ADMM iterations instead of one extra attempt
   // (QPIK: the retry also differs in the infeasible phase's drop rule, below,
   // so it runs whenever the first pass fails)
-  const bool alt = strict && (kp.problem == 0 || GL::any(actb != ob || actg != og));
+  const bool alt = strict && (kp.problem == 0 || Grp::any(actb != ob || actg != og));
   double* U = S + kp.oU0;
   double* xx = U + 64;       // [nx]
   double* yy = U + 128;      // [m] (<= 128)
@@ -1459,7 +1330,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
       // oracle's qp_polish applies the same rule)
       // (the fixed values b_j / ab_j, one division per variable lane, go to xx
       // -- where the EQP puts them too -- instead of a division per term)
-      const unsigned long long fixed = GL::ballot(l < nx && actb != 0);
+      const unsigned long long fixed = Grp::ballot(l < nx && actb != 0);
       if (l < nx) xx[l] = actb == 0 ? 0.0 : (actb < 0 ? lo[l] : up[l]) / ab[l];
       wsync();
       if (l < ng && actg != 0) {
@@ -1494,8 +1365,8 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
         stepmax = fabs(xx[l] - xc[l]);
         xnorm = fabs(xc[l]);
       }
-      stepmax = GL::max(stepmax);
-      xnorm = GL::max(xnorm);
+      stepmax = Grp::max(stepmax);
+      xnorm = Grp::max(xnorm);
       if (stepmax > 1e-12 * (1 + xnorm)) {
         // ratio test along p = xx - xc over the inactive rows
         double amin = 1.0;
@@ -1527,7 +1398,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
           if (a < amin) { amin = a; blk = row; side = sd; }
         }
         int enc = blk == 0x7fffffff ? blk : blk * 4 + (side + 1);
-        GL::argmin(amin, enc);
+        Grp::argmin(amin, enc);
         const double alpha = amin < 0 ? 0.0 : amin;
         wsync();
         if (l < nx) xc[l] += alpha * (xx[l] - xc[l]);
@@ -1598,11 +1469,11 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
         double yi = E[nx + l] * yy[nx + l] * ci, viol = actg < 0 ? yi - epsd : -yi - epsd;
         if (viol > wv) { wv = viol; worst = nx + l; }
       }
-      GL::argmax(wv, worst);
+      Grp::argmax(wv, worst);
       if (worst != 0x7fffffff) ok = false;
 #ifdef DRC_QP_DEBUG
       {
-        const unsigned long long fb = GL::ballot(l < nx && actb != 0), fg = GL::ballot(l < ng && actg != 0);
+        const unsigned long long fb = Grp::ballot(l < nx && actb != 0), fg = Grp::ballot(l < ng && actg != 0);
         if (l == 0)
           printf("polish it %d feas %d pri %.2e dua %.2e worst %d (%.2e) havefeas %d bmask %llx gmask %llx\n", it,
                  (int)feasible, pr1, dr1, worst, wv, (int)have_feas, fb, fg);
@@ -1616,7 +1487,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
     if (ok) {
       if (fused_pass) wsync();  // zz of the G rows: written by their own lanes, read below by row index
       if (l < nx) x[l] = xx[l];
-      for (int row = l; row < m; row += GL::size) {
+      for (int row = l; row < m; row += Grp::size) {
         y[row] = yy[row];
         z[row] = zz[row];
       }
@@ -1657,7 +1528,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
         if (vhi > av) { av = vhi; add = row * 4 + 2; }
       }
       CK_N(45);
-      if (!GL::any(sb != 0 || sg != 0)) {
+      if (!Grp::any(sb != 0 || sg != 0)) {
         if (worst == 0x7fffffff) break;
         if (worst < nx) { if (l == worst) actb = 0; }
         else if (l == worst - nx) actg = 0;
@@ -1676,7 +1547,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
           else if (l == worst - nx) actg = 0;
         }
       } else {
-        GL::argmax(av, add);
+        Grp::argmax(av, add);
         const int row = add >> 2, sd = (add & 3) - 1;
         if (row < nx) { if (l == row) actb = sd; }
         else if (l == row - nx) actg = sd;
@@ -1697,8 +1568,7 @@ __device__ DRC_POLISH_ATTR bool polish(const KParams& kp, double* S, bool strict
 // ---- QP kernel phases ------------------------------------------------------
 template <class QD>
 __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp, double* S, const IO& io, int64_t b) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane();
+  const int l = Grp::lane();
   const int nv = kp.nv, narm = kp.narm;
   double* qv = S + kp.kq;
   double* J = S + kp.kJ;
@@ -1708,7 +1578,7 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
   PH_STAMP(as_t0);
   {  // task record written by task_kernel (one coalesced read)
     const double* rec = io.rec + b * io.rec_stride;
-    for (int e = l; e < kp.rLen; e += GL::size) {
+    for (int e = l; e < kp.rLen; e += Grp::size) {
       const double v = rec[e];
       if (e < kp.rMan) J[e] = v;
       else if (e == kp.rMan) S[kp.oSc + SC_MAN] = v;
@@ -1730,12 +1600,12 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
   const double alpha = kp.alpha_cbf, man = S[kp.oSc + SC_MAN];
   double* Jt = S + kp.kJt;  // task Jacobian over the QP's task variables: 6 x np
   if (M->kind == 0) {
-    for (int e = l; e < 6 * np; e += GL::size) Jt[e] = J[(e / np) * nv + e % np];
+    for (int e = l; e < 6 * np; e += Grp::size) Jt[e] = J[(e / np) * nv + e % np];
   } else {
     // J~ = J S  (mobile_manipulator/robot_data.cpp:407-410); S virtual block = Rz(yaw) J_mobile
     const double yaw = qv[M->virtual_start + 2], cy = cos(yaw), sy = sin(yaw);
-    const double(*Jm)[kMaxWheels] = mobile_jac<QD::gs>(M, kp, S, qv);
-    for (int e = l; e < 6 * np; e += GL::size) {
+    const double(*Jm)[kMaxWheels] = mobile_jac(M, kp, S, qv);
+    for (int e = l; e < 6 * np; e += Grp::size) {
       const int r = e / np, a = e % np;
       double v = 0;
       const int am = a - M->act_mani_start, aw = a - M->act_mobi_start;
@@ -1752,7 +1622,7 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
     }
   }
   wsync();
-  for (int e = l; e < np * np; e += GL::size) {
+  for (int e = l; e < np * np; e += Grp::size) {
     const int i = e / np, j = e % np;
     double s = 0;
     for (int r = 0; r < 6; ++r) s += Jt[r * np + i] * Jt[r * np + j];
@@ -1760,7 +1630,7 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
   }
   PH_SINCE(72, as_t1);  // J~ and P
   PH_STAMP(as_t2);
-  for (int e = l; e < ng * nx; e += GL::size) G[e] = 0.0;
+  for (int e = l; e < ng * nx; e += Grp::size) G[e] = 0.0;
   if (l < nx) {
     double qi;
     if (l < np) {
@@ -1825,8 +1695,7 @@ __device__ __forceinline__ void qp_assemble(const DevModel* M, const KParams& kp
 // moma_lp_infeasible.
 template <class QD>
 __device__ __forceinline__ bool moma_lp_infeasible(const DevModel* M, const KParams& kp, const double* S) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane();
+  const int l = Grp::lane();
   const int nx = DNX, n = kp.narm, vo = M->act_mani_start;
   const double *G = S + kp.oG, *lo = S + kp.oL + nx;
   const double *gm = G + (2 * n) * nx + vo, *gd = G + (2 * n + 1) * nx + vo;
@@ -1848,32 +1717,31 @@ __device__ __forceinline__ bool moma_lp_infeasible(const DevModel* M, const KPar
     phi += fmax(g * blo, g * bhi);
     scale += (fabs(gm[i]) + fabs(gd[i])) * fmax(fabs(blo), fabs(bhi));
   }
-  return GL::any(mu >= 0.0 && phi < -1e-6 * (1.0 + scale));
+  return Grp::any(mu >= 0.0 && phi < -1e-6 * (1.0 + scale));
 }
 
 // finiteness check + Ruiz equilibration (OSQP scaling.c); returns
 // DRC_STATUS_NONFINITE or DRC_STATUS_MAX_ITER (= not yet solved)
 template <class QD>
 __device__ __forceinline__ int qp_scale(const KParams& kp, double* S) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane();
+  const int l = Grp::lane();
   const int nx = DNX, ng = DNG, np = DNP, m = DM;
   double *P = S + kp.oP, *G = S + kp.oG, *qq = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU;
   int status = DRC_STATUS_MAX_ITER;
   {
     bool finite = true;
-    for (int e = l; e < np * np; e += GL::size) finite &= isfinite(P[e]);
-    for (int e = l; e < ng * nx; e += GL::size) finite &= isfinite(G[e]);
+    for (int e = l; e < np * np; e += Grp::size) finite &= isfinite(P[e]);
+    for (int e = l; e < ng * nx; e += Grp::size) finite &= isfinite(G[e]);
     if (l < nx) finite &= isfinite(qq[l]);
-    for (int row = l; row < m; row += GL::size) finite &= !isnan(lo[row]) && !isnan(up[row]);
-    if (!GL::all(finite)) status = DRC_STATUS_NONFINITE;
+    for (int row = l; row < m; row += Grp::size) finite &= !isnan(lo[row]) && !isnan(up[row]);
+    if (!Grp::all(finite)) status = DRC_STATUS_NONFINITE;
   }
   double *D = S + kp.oD, *E = S + kp.oE, *x = S + kp.oX, *z = S + kp.oZ, *y = S + kp.oY, *dy = S + kp.oDY;
   (void)x, (void)z, (void)y, (void)dy;  // the runtime-sized (LDS) path only
   double* sc = S + kp.oSc;
   if (status != DRC_STATUS_NONFINITE) {
     if (l < nx) D[l] = 1.0;
-    for (int row = l; row < m; row += GL::size) E[row] = 1.0;
+    for (int row = l; row < m; row += Grp::size) E[row] = 1.0;
     if (l == 0) sc[SC_C] = 1.0;
     double* Dt = S + kp.oT1;
     double* Et = S + kp.oT2;
@@ -1916,8 +1784,8 @@ __device__ __forceinline__ int qp_scale(const KParams& kp, double* S) {
           for (int i = 0; i < np; ++i) cn = fmax(cn, fabs(P[i * np + l]));
         qn = fabs(qq[l]);
       }
-      cn = GL::sum(cn) / nx;
-      qn = GL::max(qn);
+      cn = Grp::sum(cn) / nx;
+      qn = Grp::max(qn);
       qn = qn < kMinScaling ? 1.0 : (qn > kMaxScaling ? kMaxScaling : qn);
       double ct = fmax(cn, qn);
       ct = ct < kMinScaling ? 1.0 : (ct > kMaxScaling ? kMaxScaling : ct);
@@ -1926,12 +1794,12 @@ __device__ __forceinline__ int qp_scale(const KParams& kp, double* S) {
         for (int c = 0; c < np; ++c) P[l * np + c] *= ct;
       if (l < nx) qq[l] *= ct;
       if (l == 0) sc[SC_C] *= ct;
-      // fixed point (as qp_scale_regs and the oracle)
+      // fixed point: every factor of this pass exactly 1 (as qp_scale_roles and the oracle)
       const bool ones = (l >= nx || (Dt[l] == 1.0 && Et[l] == 1.0)) && (l >= ng || Et[nx + l] == 1.0);
       wsync();
-      if (ct == 1.0 && GL::all(ones)) break;
+      if (ct == 1.0 && Grp::all(ones)) break;
     }
-    for (int row = l; row < m; row += GL::size) {
+    for (int row = l; row < m; row += Grp::size) {
       lo[row] = fmax(lo[row], -kInf) * E[row];
       up[row] = fmin(up[row], kInf) * E[row];
     }
@@ -1955,158 +1823,36 @@ __device__ __forceinline__ double absmax_tree(const double (&a)[N]) {
   return t[0];
 }
 
-// Register form of qp_scale for compile-time shapes: lane l holds row l of P
-// (= column l: P is symmetric bit for bit), column l and row l of G; the
-// Ruiz factors move by v_readlane.  Same operations in the same order as
-// qp_scale (bit-identical results); P, G, q, D, E written back at the end.
-template <class QD>
-__device__ __forceinline__ int qp_scale_regs(const KParams& kp, double* S) {
-  using GL = Grp<QD::gs>;
-  constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np, M = NX + NG;
-  const int l = GL::lane();
-  double *P = S + kp.oP, *G = S + kp.oG, *qq = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU;
-  double *D = S + kp.oD, *E = S + kp.oE, *sc = S + kp.oSc;
-  {
-    bool finite = true;
-    for (int e = l; e < NP * NP; e += GL::size) finite &= isfinite(P[e]);
-    for (int e = l; e < NG * NX; e += GL::size) finite &= isfinite(G[e]);
-    if (l < NX) finite &= isfinite(qq[l]);
-    for (int row = l; row < M; row += GL::size) finite &= !isnan(lo[row]) && !isnan(up[row]);
-    if (!GL::all(finite)) return DRC_STATUS_NONFINITE;
-  }
-  const bool hx = l < NX, hg = l < NG, hp = l < NP;
-  const int lx = hx ? l : 0, lg = hg ? l : 0, lp = hp ? l : 0;
-  double Prow[NP], Gcol[NG], Grow[NX];
-#pragma unroll
-  for (int c = 0; c < NP; ++c) Prow[c] = P[lp * NP + c];
-#pragma unroll
-  for (int i = 0; i < NG; ++i) Gcol[i] = G[i * NX + lx];
-#pragma unroll
-  for (int j = 0; j < NX; ++j) Grow[j] = G[lg * NX + j];
-  double abl = ab[lx], ql = qq[lx], Dl = 1.0, El = 1.0, EGl = 1.0, cs = 1.0;
-  auto clampf = [](double v) { return v < kMinScaling ? 1.0 : (v > kMaxScaling ? kMaxScaling : v); };
-  for (int it = 0; it < kp.s.scaling; ++it) {
-    PH_ADD(49, 1);  // Ruiz passes
-    // (the inputs are finite -- checked above -- so every fmax below is exact)
-    const double sgc = absmax_tree(Gcol);
-    const double s = fmax(fabs(abl), hp ? fmax(absmax_tree(Prow), sgc) : sgc);
-    const double Dt = 1.0 / sqrt(clampf(s));
-    const double Et = 1.0 / sqrt(clampf(fabs(abl)));
-    const double sg = absmax_tree(Grow);
-    const double EtG = 1.0 / sqrt(clampf(sg));
-    // every factor of this pass exactly 1 (the fixed-point pass, usually the
-    // second): the products below would multiply by 1.0, an identity, so
-    // they are skipped -- bit for bit the same matrices, without the pass's
-    // 23 broadcasts
-    const bool unit = GL::all((!hx || (Dt == 1.0 && Et == 1.0)) && (!hg || EtG == 1.0));
-    if (!unit) {
-      // the broadcast factors are used as they arrive (not gathered into
-      // per-lane arrays: 39 doubles more would not fit the QP kernel's 168-VGPR
-      // budget and spilled); same products in the same order
-      // (64-lane waves: the factors reach the lanes through LDS -- each lane
-      // writes its own, every lane reads them all -- instead of NX + NG VALU
-      // broadcasts)
-      constexpr bool kLds = QD::gs == 64;
-      lds_double* wb = (lds_double*)(S + kp.oBc);  // NX + NG doubles (plan_layout)
-      if constexpr (kLds) {
-        if (hx) wb[l] = Dt;
-        if (hg) wb[NX + l] = EtG;
-        asm volatile("" ::: "memory");
-      }
-      static_for<NX>([&](auto C) {
-        constexpr int c = decltype(C)::value;
-        double dc;
-        if constexpr (kLds) dc = wb[c];
-        else dc = GL::template bcastc<c>(Dt);
-        if constexpr (c < NP) {
-          if (hp) Prow[c] *= Dt * dc;
-        }
-        if (hg) Grow[c] *= EtG * dc;
-      });
-      static_for<NG>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        double ei;
-        if constexpr (kLds) ei = wb[NX + i];
-        else ei = GL::template bcastc<i>(EtG);
-        if (hx) Gcol[i] *= ei * Dt;
-      });
-      if constexpr (kLds) asm volatile("" ::: "memory");
-      if (hx) {
-        abl *= Et * Dt;
-        ql *= Dt;
-        Dl *= Dt;
-        El *= Et;
-      }
-      if (hg) EGl *= EtG;
-    }
-    // cost scaling: mean column norm of P vs |q|_inf
-    double cn = 0, qn = 0;
-    if (hp) cn = absmax_tree(Prow);
-    if (hx) qn = fabs(ql);
-    cn = GL::sum(cn) / NX;
-    qn = GL::max(qn);
-    qn = clampf(qn);
-    double ct = clampf(fmax(cn, qn));
-    ct = 1.0 / ct;
-    if (hp)
-#pragma unroll
-      for (int c = 0; c < NP; ++c) Prow[c] *= ct;
-    if (hx) ql *= ct;
-    cs *= ct;
-    // fixed point: every factor of this pass was exactly 1, so the remaining
-    // passes would repeat it bit for bit (oracle: same exit)
-    if (ct == 1.0 && unit) break;
-  }
-  if (hp)
-#pragma unroll
-    for (int c = 0; c < NP; ++c) P[l * NP + c] = Prow[c];
-  if (hg)
-#pragma unroll
-    for (int j = 0; j < NX; ++j) G[l * NX + j] = Grow[j];
-  if (hx) {
-    ab[l] = abl;
-    qq[l] = ql;
-    D[l] = Dl;
-    E[l] = El;
-  }
-  if (hg) E[NX + l] = EGl;
-  if (l == 0) sc[SC_C] = cs;
-  wsync();
-  for (int row = l; row < M; row += GL::size) {
-    lo[row] = fmax(lo[row], -kInf) * E[row];
-    up[row] = fmin(up[row], kInf) * E[row];
-  }
-  wsync();
-  return DRC_STATUS_MAX_ITER;
-}
-
 // Ruiz passes with one role per lane (64-lane waves, NX + NG <= 64): lane c < NX
 // holds column c of [P; G] (P's part only for c < NP), lane NX + r holds row r
 // of G, so a lane forms one absolute maximum, one factor F (D~ on column lanes,
-// E~ on row lanes) and one set of products instead of all three.  Same
-// operands, same products in the same order as qp_scale_regs (bit-identical);
-// the column copy of G is dropped at the end, as there.
+// E~ on row lanes) and one set of products instead of all three.  Per pass and
+// entry the same products in the same order as qp_scale, so P, G, q, D, E and c
+// come out bit-identical: P_lk *= (D~_l D~_k), G_rk *= (E~_r D~_k) (each
+// factor pair multiplied first, then the entry), ab_l *= (E~_l D~_l), q_l, D_l
+// *= D~_l, E *= E~, then P, q and c *= the cost factor.  A pass whose factors
+// are all exactly 1 skips its products (multiplications by 1.0).  Only the row
+// lanes write G back; the column lanes' copy of it is dropped at the end.
 template <class QD>
 __device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* S);
 
 template <class QD>
 __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
   if constexpr (kQpikSparse<QD>) return qp_scale_roles_sparse<QD>(kp, S);
-  using GL = Grp<64>;
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np, M = NX + NG;
   constexpr int KV = NP + NG > NX ? NP + NG : NX;
   static_assert(M <= 64, "one lane per column and per G row");
-  const int l = GL::lane();
+  const int l = Grp::lane();
   double *P = S + kp.oP, *G = S + kp.oG, *qq = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU;
   double *D = S + kp.oD, *E = S + kp.oE, *sc = S + kp.oSc;
   PH_STAMP(sr_t0);
   {
     bool finite = true;
-    for (int e = l; e < NP * NP; e += GL::size) finite &= isfinite(P[e]);
-    for (int e = l; e < NG * NX; e += GL::size) finite &= isfinite(G[e]);
+    for (int e = l; e < NP * NP; e += Grp::size) finite &= isfinite(P[e]);
+    for (int e = l; e < NG * NX; e += Grp::size) finite &= isfinite(G[e]);
     if (l < NX) finite &= isfinite(qq[l]);
-    for (int row = l; row < M; row += GL::size) finite &= !isnan(lo[row]) && !isnan(up[row]);
-    if (!GL::all(finite)) return DRC_STATUS_NONFINITE;
+    for (int row = l; row < M; row += Grp::size) finite &= !isnan(lo[row]) && !isnan(up[row]);
+    if (!Grp::all(finite)) return DRC_STATUS_NONFINITE;
   }
   PH_SINCE(64, sr_t0);  // finiteness sweep
   PH_STAMP(sr_t1);
@@ -2131,7 +1877,7 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
     const double mx = absmax_tree(V);
     const double F = 1.0 / sqrt(clampf(col ? fmax(fabs(abl), mx) : mx));  // D~ (column) / E~ (row)
     const double Et = 1.0 / sqrt(clampf(fabs(abl)));                       // bound-row E~ (column lanes)
-    const bool unit = GL::all((!col || (F == 1.0 && Et == 1.0)) && (!row || F == 1.0));
+    const bool unit = Grp::all((!col || (F == 1.0 && Et == 1.0)) && (!row || F == 1.0));
     if (!unit) {
       if (l < M) wb[l] = F;  // wb[c] = D~_c, wb[NX + r] = E~_r
       asm volatile("" ::: "memory");
@@ -2167,8 +1913,8 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
       cn = absmax_tree(t);
     }
     if (col) qn = fabs(ql);
-    cn = GL::sum(cn) / NX;
-    qn = GL::max(qn);
+    cn = Grp::sum(cn) / NX;
+    qn = Grp::max(qn);
     qn = clampf(qn);
     double ct = clampf(fmax(cn, qn));
     ct = 1.0 / ct;
@@ -2196,7 +1942,7 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
   if (row) E[NX + r] = EGl;
   if (l == 0) sc[SC_C] = cs;
   wsync();
-  for (int rw = l; rw < M; rw += GL::size) {
+  for (int rw = l; rw < M; rw += Grp::size) {
     lo[rw] = fmax(lo[rw], -kInf) * E[rw];
     up[rw] = fmin(up[rw], kInf) * E[rw];
   }
@@ -2220,12 +1966,11 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
 // P, G, q, D, E, c.  G's other entries keep qp_assemble's zero fill.
 template <class QD>
 __device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* S) {
-  using GL = Grp<64>;
   using Pat = QpikPattern<QD::np>;
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np, M = NX + NG;
   constexpr int KV = NP + 4;
   static_assert(M <= 64, "one lane per column and per G row");
-  const int l = GL::lane();
+  const int l = Grp::lane();
   double *P = S + kp.oP, *G = S + kp.oG, *qq = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU;
   double *D = S + kp.oD, *E = S + kp.oE, *sc = S + kp.oSc;
   PH_STAMP(sr_t1);
@@ -2270,8 +2015,8 @@ __device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* 
 #pragma unroll
     for (int k = 0; k < KV; ++k) finite &= isfinite(V[k]);
     if (l < NX) finite &= isfinite(qq[l]);
-    for (int rw = l; rw < M; rw += GL::size) finite &= !isnan(lo[rw]) && !isnan(up[rw]);
-    if (!GL::all(finite)) return DRC_STATUS_NONFINITE;
+    for (int rw = l; rw < M; rw += Grp::size) finite &= !isnan(lo[rw]) && !isnan(up[rw]);
+    if (!Grp::all(finite)) return DRC_STATUS_NONFINITE;
   }
   PH_SINCE(64, sr_t0);  // finiteness check (on V)
   PH_STAMP(sr_t2);
@@ -2283,7 +2028,7 @@ __device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* 
     const double mx = absmax_tree(V);
     const double F = 1.0 / sqrt(clampf(col ? fmax(fabs(abl), mx) : mx));  // D~ (column) / E~ (row)
     const double Et = 1.0 / sqrt(clampf(fabs(abl)));                       // bound-row E~ (column lanes)
-    const bool unit = GL::all((!col || (F == 1.0 && Et == 1.0)) && (!row || F == 1.0));
+    const bool unit = Grp::all((!col || (F == 1.0 && Et == 1.0)) && (!row || F == 1.0));
     if (!unit) {
       if (l < M) wb[l] = F;  // wb[c] = D~_c, wb[NX + r] = E~_r
       asm volatile("" ::: "memory");
@@ -2309,8 +2054,8 @@ __device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* 
       cn = absmax_tree(t);
     }
     if (col) qn = fabs(ql);
-    cn = GL::sum(cn) / NX;
-    qn = GL::max(qn);
+    cn = Grp::sum(cn) / NX;
+    qn = Grp::max(qn);
     qn = clampf(qn);
     double ct = clampf(fmax(cn, qn));
     ct = 1.0 / ct;
@@ -2339,7 +2084,7 @@ __device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* 
   if (row) E[NX + r] = EGl;
   if (l == 0) sc[SC_C] = cs;
   wsync();
-  for (int rw = l; rw < M; rw += GL::size) {
+  for (int rw = l; rw < M; rw += Grp::size) {
     lo[rw] = fmax(lo[rw], -kInf) * E[rw];
     up[rw] = fmin(up[rw], kInf) * E[rw];
   }
@@ -2359,7 +2104,7 @@ template <class QD>
 struct SchurLanes {
   static constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
   lds_double *qq, *ab, *lo, *up, *x, *z, *y, *dy;
-  lds_cdouble *rv, *Si, *GS, *dv, *cf, *G;
+  lds_cdouble *rv, *Si, *GSi, *dv, *cf, *G;
   int l, rr, lc, ia, ig, iv;
   bool hc, hr, ha, hv;
   __device__ __forceinline__ SchurLanes(const KParams& kpl, double* S0) {
@@ -2367,13 +2112,13 @@ struct SchurLanes {
     lds_ckparams* kq = opaque_lds((lds_ckparams*)&kpl);
     lds_double* S = opaque_lds((lds_double*)S0);
     lds_ckparams& kp = *kq;
-    l = Grp<QD::gs>::lane();
+    l = Grp::lane();
     qq = S + kp.oQ; ab = S + kp.oAB; lo = S + kp.oL; up = S + kp.oU;
     x = S + kp.oX; z = S + kp.oZ; y = S + kp.oY; dy = S + kp.oDY;
     rv = S + kp.oRho;
     Si = S + kp.oU0;
-    GS = Si + NP * NP;
-    dv = GS + NG * NP;
+    GSi = Si + NP * NP;
+    dv = GSi + NG * NP;
     cf = dv + NG;
     G = S + kp.oG;
     lds_cint* aux = (lds_cint*)(cf + 2 * NG);
@@ -2408,7 +2153,7 @@ struct SchurLanes {
       }
     } else {
 #pragma unroll
-      for (int c = 0; c < NP; ++c) R[c] = GS[rr * NP + c];
+      for (int c = 0; c < NP; ++c) R[c] = GSi[rr * NP + c];
 #pragma unroll
       for (int i = 0; i < kCol; ++i) R[NP + i] = 0.0;
     }
@@ -2434,13 +2179,12 @@ struct SchurLanes {
 //   rows: x~_a = t_a - coef_r v_r,  (G x~)_r = v_r + g_r x~_a
 template <class QD>
 __device__ __forceinline__ void admm_iters_schur(const KParams& kpl, double* S, int steps) {
-  using GL = Grp<QD::gs>;
   const KParams& kp = kpl;
   const double sig = kp.s.sigma, al = kp.s.alpha;
   PHG_DECL
   constexpr int NX = QD::nx, NG = QD::ng, NP = QD::np;
   (void)NX;
-  static_assert(NP + NG <= QD::gs, "one lane per core variable and per G row");
+  static_assert(NP + NG <= 64, "one lane per core variable and per G row");
   constexpr bool kSparse = kQpikSparse<QD>;
   using Pat = QpikPattern<NP>;
   double R[NP + SchurLanes<QD>::kCol];
@@ -2520,7 +2264,7 @@ __device__ __forceinline__ void admm_iters_schur(const KParams& kpl, double* S, 
 #else
       static_for<NG>([&](auto I) {
         constexpr int i = decltype(I)::value;
-        const double ui = GL::template bcastc<NP + i>(u);
+        const double ui = Grp::bcastc<NP + i>(u);
         if constexpr (i & 1) r1 += R[NP + i] * ui;
         else r0 += R[NP + i] * ui;
       });
@@ -2528,7 +2272,7 @@ __device__ __forceinline__ void admm_iters_schur(const KParams& kpl, double* S, 
       double s0 = 0, s1 = 0;
       static_for<NP>([&](auto C) {
         constexpr int c = decltype(C)::value;
-        const double rpc = GL::template bcastc<c>(rp);
+        const double rpc = Grp::bcastc<c>(rp);
         if constexpr (c & 1) s1 += R[c] * rpc;
         else s0 += R[c] * rpc;
       });
@@ -2584,8 +2328,7 @@ __device__ __noinline__ void admm_iters_schur_call(const KParams& kpl, double* S
 // rho, K^-1 and the ADMM iterations (+ polish); returns the status
 template <class QD>
 __device__ __forceinline__ int qp_admm(const KParams& kp, const KParams& kpl, double* S, int* iters_out) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane();
+  const int l = Grp::lane();
   const int nx = DNX, ng = DNG, m = DM;
   double *G = S + kp.oG, *qq = S + kp.oQ, *ab = S + kp.oAB, *lo = S + kp.oL, *up = S + kp.oU;
   double *x = S + kp.oX, *z = S + kp.oZ, *y = S + kp.oY, *dy = S + kp.oDY;
@@ -2601,7 +2344,7 @@ __device__ __forceinline__ int qp_admm(const KParams& kp, const KParams& kpl, do
   factor_any<QD>(kpl, S);
   PHG(24);
   if (l < nx) x[l] = 0.0;
-  for (int row = l; row < m; row += GL::size) z[row] = y[row] = 0.0;
+  for (int row = l; row < m; row += Grp::size) z[row] = y[row] = 0.0;
   wsync();
   // ---------------- OSQP: ADMM ----------------------------------------
   const double* K = S + kp.oU0;
@@ -2634,102 +2377,17 @@ __device__ __forceinline__ int qp_admm(const KParams& kp, const KParams& kpl, do
       if (adapt) to_adapt = adapt_every;
       if (!(check || adapt)) continue;  // last iteration: published for the output
       PH_STAMP(tc0);
-      const int act = __builtin_amdgcn_readfirstlane(admm_check<QD>(kpl, S, it, check, adapt, &status));
+      const bool stop = __builtin_amdgcn_readfirstlane(admm_check<QD>(kpl, S, it, check, adapt, &status));
       PH_ONLY(const unsigned long long dchk = __builtin_amdgcn_s_memtime() - tc0; PH_ADD(27, dchk));
-      if (act == 2) {
+      if (stop) {
         stopped = true;
         break;
       }
     }
     if (!stopped) it = (max_iter > 0 ? max_iter : 0) + 1;  // as a counted loop 1..max_iter leaves it
-  } else if constexpr (QD::reg) {
-    constexpr int NX = QD::nx, NG = QD::ng;
-    double Gc[NG], Kr[NX], GKr[NX];
-    prep_admm_mats<QD>(kpl, S);
-    load_admm_regs<QD>(kp, S, Gc, Kr, GKr);
-    PHG(25);
-    const bool hb = l < NX, hg = l < NG;
-    const int lb_ = hb ? l : 0, lg_ = hg ? NX + l : 0;
-    const double ab_l = ab[lb_], q_l = qq[lb_], lo_b = lo[lb_], up_b = up[lb_], lo_g = lo[lg_], up_g = up[lg_];
-    double rb = rv[lb_], rg = rv[lg_];
-    double xl = 0, zb = 0, yb = 0, zg = 0, yg = 0, dyb = 0, dyg = 0;
-    for (it = 1; it <= kp.s.max_iter; ++it) {
-      const double wg = hg ? rg * zg - yg : 0.0;
-      double r0 = hb ? sig * xl - q_l + ab_l * (rb * zb - yb) : 0.0, r1 = 0;
-#pragma unroll
-      for (int i = 0; i < NG; ++i) {
-        const double wi = GL::bcast(wg, i);
-        if (i & 1) r1 += Gc[i] * wi;
-        else r0 += Gc[i] * wi;
-      }
-      const double rhs = hb ? r0 + r1 : 0.0;
-      double x0 = 0, x1 = 0, a0 = 0, a1 = 0;
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        const double rc = GL::bcast(rhs, c);
-        if (c & 1) {
-          x1 += Kr[c] * rc;
-          a1 += GKr[c] * rc;
-        } else {
-          x0 += Kr[c] * rc;
-          a0 += GKr[c] * rc;
-        }
-      }
-      const double xtil = x0 + x1, ag = a0 + a1;
-      if (hb) {  // z~ = A x~ ; relaxation ; projection ; dual update
-        const double zr = al * ab_l * xtil + (1 - al) * zb;
-        double zn = zr + yb / rb;
-        zn = fmin(fmax(zn, lo_b), up_b);
-        dyb = rb * (zr - zn);
-        yb += dyb;
-        zb = zn;
-        xl = al * xtil + (1 - al) * xl;
-      }
-      if (hg) {
-        const double zr = al * ag + (1 - al) * zg;
-        double zn = zr + yg / rg;
-        zn = fmin(fmax(zn, lo_g), up_g);
-        dyg = rg * (zr - zn);
-        yg += dyg;
-        zg = zn;
-      }
-      const bool check = kp.s.check_termination > 0 && it % kp.s.check_termination == 0;
-      const bool adapt = kp.s.adaptive_rho && kp.s.adaptive_rho_interval > 0 && it % kp.s.adaptive_rho_interval == 0;
-      if (!(check || adapt) && it < kp.s.max_iter) continue;
-      // publish the iterate for the (LDS) residual / polish / rho code
-      if (hb) {
-        x[l] = xl;
-        z[l] = zb;
-        y[l] = yb;
-        dy[l] = dyb;
-      }
-      if (hg) {
-        z[NX + l] = zg;
-        y[NX + l] = yg;
-        dy[NX + l] = dyg;
-      }
-      wsync();
-      if (!(check || adapt)) continue;  // last iteration: published for the output
-      PH_STAMP(tc0);
-      const int act = admm_check<QD>(kpl, S, it, check, adapt, &status);
-      PH_ONLY(const unsigned long long dchk = __builtin_amdgcn_s_memtime() - tc0; PH_ADD(27, dchk); PH_ADD(26, 0ull - dchk));  // checks out of the loop's slot
-      if (act == 2) break;
-      // Always re-read the register state from LDS (published above, or
-      // updated by the check): nothing large stays live across the call, so
-      // the out-of-line block costs no spill traffic.
-      load_admm_regs<QD>(kp, S, Gc, Kr, GKr);
-      rb = rv[lb_];
-      rg = rv[lg_];
-      xl = x[lb_];
-      zb = z[lb_];
-      yb = y[lb_];
-      zg = z[lg_];
-      yg = y[lg_];
-    }
-    PHG(26);
   } else {
     for (it = 1; it <= kp.s.max_iter; ++it) {
-      for (int row = l; row < m; row += GL::size) w[row] = rv[row] * z[row] - y[row];
+      for (int row = l; row < m; row += Grp::size) w[row] = rv[row] * z[row] - y[row];
       wsync();
       if (l < nx) {
         double r0 = sig * x[l] - qq[l] + ab[l] * w[l], r1 = 0.0;
@@ -2785,54 +2443,7 @@ __device__ __forceinline__ int qp_admm(const KParams& kp, const KParams& kpl, do
       wsync();
       const bool check = kp.s.check_termination > 0 && it % kp.s.check_termination == 0;
       const bool adapt = kp.s.adaptive_rho && kp.s.adaptive_rho_interval > 0 && it % kp.s.adaptive_rho_interval == 0;
-      if (check || adapt) residuals<QD>(kp, S, x, z, y, kp.s.eps_abs, kp.s.eps_rel);
-      if (check) {
-        const bool conv = sc[SC_PRI] < sc[SC_EPSP] && sc[SC_DUA] < sc[SC_EPSD];
-        // parity mode: a certified polish is exact whatever the ADMM
-        // residual, so also try it every 4th check (slow-ADMM vertices)
-        if (kp.s.exact && !conv && sc[SC_PFAIL] < kPolishMaxEarly) {
-          if (polish<QD>(kp, S, true)) {
-            status = DRC_STATUS_SOLVED;
-            break;
-          }
-          if (l == 0) sc[SC_PFAIL] += 1.0;
-          factor_kinv<QD>(kp, S);  // polish used the union region
-          residuals<QD>(kp, S, x, z, y, kp.s.eps_abs, kp.s.eps_rel);
-        }
-        if (conv) {
-          if (!kp.s.exact) {
-            status = DRC_STATUS_SOLVED;
-            break;
-          }
-          if (sc[SC_PFAIL] < kPolishMaxTotal) {
-            if (polish<QD>(kp, S, true)) {
-              status = DRC_STATUS_SOLVED;
-              break;
-            }
-            if (l == 0) sc[SC_PFAIL] += 1.0;
-            factor_kinv<QD>(kp, S);  // polish used the union region
-          }
-          residuals<QD>(kp, S, x, z, y, kp.s.eps_fallback, kp.s.eps_fallback);
-          if (sc[SC_PRI] < sc[SC_EPSP] && sc[SC_DUA] < sc[SC_EPSD]) {
-            status = DRC_STATUS_SOLVED;
-            break;
-          }
-        } else if (primal_infeasible<QD>(kp, S, kp.s.eps_prim_inf)) {
-          status = DRC_STATUS_PRIMAL_INFEASIBLE;
-          break;
-        }
-      }
-      if (adapt) {
-        const double pr = sc[SC_PRIS] / (fmax(sc[SC_NAX], sc[SC_NZ]) + kDivTol);
-        const double dr = sc[SC_DUAS] / (fmax(fmax(sc[SC_NQ], sc[SC_NATY]), sc[SC_NPX]) + kDivTol);
-        const double rho = sc[SC_RHO];
-        double rn = rho * sqrt(pr / (dr + kDivTol));
-        rn = fmin(fmax(rn, kRhoMin), kRhoMax);
-        if (rn > rho * kp.s.adaptive_rho_tolerance || rn < rho / kp.s.adaptive_rho_tolerance) {
-          set_rho<QD>(kp, S, rn);
-          factor_kinv<QD>(kp, S);
-        }
-      }
+      if ((check || adapt) && admm_check<QD>(kpl, S, it, check, adapt, &status)) break;
     }
   }
   *iters_out = it > kp.s.max_iter ? kp.s.max_iter : it;
@@ -2840,27 +2451,25 @@ __device__ __forceinline__ int qp_admm(const KParams& kp, const KParams& kpl, do
   return status;
 }
 
-// One instance b of the QP stage on this lane group (S: its LDS plan kp; kpl:
+// One instance b of the QP stage on this wave (S: its LDS plan kp; kpl:
 // an LDS copy of kp for the out-of-line ADMM blocks): assembly from the task
 // record, Ruiz scaling, ADMM + certified polish, outputs (zero on failure,
 // QP_IK.cpp:56-61).  Used by qp_kernel and the fused task + QP kernel.
 template <class QD>
 __device__ __forceinline__ void qp_instance(const DevModel* __restrict__ M0, const KParams& kp, const KParams& kpl,
                                             const IO& io, double* S, int64_t b) {
-  using GL = Grp<QD::gs>;
-  const int l = GL::lane();
+  const int l = Grp::lane();
   PH_DECL
   const int64_t gb = io.b0 + b, LD = io.ld;  // position in the caller's [field][B] arrays
   const DevModel* M = opaque_model(M0);
-  stage_stamp<QD::gs>(io, ST_QP0, gb);
-  stage_where<QD::gs>(io, ST_WQP, gb);
+  stage_stamp(io, ST_QP0, gb);
+  stage_where(io, ST_WQP, gb);
   qp_assemble<QD>(M, kp, S, io, b);
-  stage_stamp<QD::gs>(io, ST_ASM, gb);
+  stage_stamp(io, ST_ASM, gb);
   PH(0);
   const bool lp_inf = M->kind == 1 && kp.s.exact && moma_lp_infeasible<QD>(M, kp, S);
   int status, iters = 0;
-  if constexpr (QD::reg && QD::gs == 64 && QD::nx + QD::ng <= 64) status = qp_scale_roles<QD>(kpl, S);
-  else if constexpr (QD::reg) status = qp_scale_regs<QD>(kpl, S);
+  if constexpr (QD::reg) status = qp_scale_roles<QD>(kpl, S);
   else status = qp_scale<QD>(kp, S);
   scaling_inverses<QD>(kp, S);
   PH(1);
@@ -2869,7 +2478,7 @@ __device__ __forceinline__ void qp_instance(const DevModel* __restrict__ M0, con
     else status = qp_admm<QD>(kp, kpl, S, &iters);
   }
   PH(3);
-  stage_stamp<QD::gs>(io, ST_SOLVED, gb);
+  stage_stamp(io, ST_SOLVED, gb);
   // ---------------- outputs (zero on failure, QP_IK.cpp:56-61) ------------
   const double *D = S + kp.oD, *x = S + kp.oX;
   if (l < kp.na) io.out[(int64_t)l * LD + gb] = status == DRC_STATUS_SOLVED ? D[l] * x[l] : 0.0;
@@ -2878,7 +2487,7 @@ __device__ __forceinline__ void qp_instance(const DevModel* __restrict__ M0, con
     if (io.iters) io.iters[gb] = iters;
   }
   wsync();
-  stage_stamp<QD::gs>(io, ST_OUT, gb);
+  stage_stamp(io, ST_OUT, gb);
   PH(5);
   PH_FLUSH(16);
 }

@@ -79,7 +79,6 @@ reach_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
     for (int e = lane_id(); e < static_cast<int>(sizeof(KParams) / 8); e += 64) dst[e] = src[e];
     wsync();
   }
-  static_assert(QD::gs == 64, "the reach kernel runs one instance per wave");
   const int l = lane_id();
   const int64_t B = io.B, LD = io.ld;
   const int nv = kt.nv, na = kq.na;

@@ -44,7 +44,6 @@ reach_seeds_kernel(const DevModel* __restrict__ M0, const KParams kt, const KPar
     for (int e = lane_id(); e < static_cast<int>(sizeof(KParams) / 8); e += 64) dst[e] = src[e];
     wsync();
   }
-  static_assert(QD::gs == 64, "the reach seeds kernel runs one instance per wave");
   static_assert(sizeof...(OB) <= 1, "at most one set of obstacle poses");
   const ReachArgs& re = rs.re;
   const int l = lane_id();

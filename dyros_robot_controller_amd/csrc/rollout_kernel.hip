@@ -63,7 +63,6 @@ rollout_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams 
     for (int e = lane_id(); e < static_cast<int>(sizeof(KParams) / 8); e += 64) dst[e] = src[e];
     wsync();
   }
-  static_assert(QD::gs == 64, "the rollout kernel runs one instance per wave");
   const int l = lane_id();
   const int64_t B = io.B, LD = io.ld;
   const int nv = kt.nv, na = kq.na;

@@ -15,8 +15,10 @@ These cases exercise every boundary of that computation against the oracle
     (10 / 7: steps that fall on one iteration and on different ones);
   * exact mode with a short check interval (3).
 
-Device against the oracle on identical settings (FR3 and XLS-FR3, stress-tier
-inputs): iteration counts and statuses identical and q-dot within the
+Device against the oracle on identical settings (FR3 and XLS-FR3 on the Schur
+loop, Caster-FR3 on the runtime-sized LDS loop, which tests the intervals at
+every iteration; stress-tier inputs): iteration counts and statuses identical
+and q-dot within the
 reference census bound (1e-7 relative up to 150 iterations, x10 per 250
 beyond; 1e-6 in exact mode, the parity contract's QP bound) on every instance
 except where both sides ran >= 500 ADMM iterations (the reference-settings
@@ -52,11 +54,19 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("robot", ["fr3", "xls_fr3"])
-@pytest.mark.parametrize("mode,over", CASES, ids=[f"{m}-{'-'.join(f'{k}{v}' for k, v in o.items())}" for m, o in CASES])
+# Caster-FR3 runs the runtime-sized QP kernel (no compiled shape), so its loop
+# bounds and checks face the oracle too.  It leaves out {"adaptive_rho": 0}
+# alone: there the oracle itself runs >= LONG_RUN iterations on 230 of the 256
+# instances, so the test's floor on compared instances (B // 4) cannot hold.
+_ids = [f"{m}-{'-'.join(f'{k}{v}' for k, v in o.items())}" for m, o in CASES]
+ROBOT_CASES = [pytest.param(r, m, o, id=f"{i}-{r}") for r in ("fr3", "xls_fr3", "caster_fr3")
+               for (m, o), i in zip(CASES, _ids) if not (r == "caster_fr3" and o == {"adaptive_rho": 0})]
+
+
+@pytest.mark.parametrize("robot,mode,over", ROBOT_CASES)
 def test_admm_loop_bounds_match_oracle(cuda, robot, mode, over):
     import torch
-    moma = robot == "xls_fr3"
+    moma = robot in ("xls_fr3", "caster_fr3")
     rd = make_moma(robot, cuda) if moma else make_manipulator(robot, cuda)
     ctrl = (mobile_manipulator if moma else manipulator).RobotController(0.001, rd, solver_mode=mode)
     for k, v in over.items():
