@@ -1,12 +1,19 @@
 // DyrosMath::PinvCOD (math_type_define.h:563-570) as a serial device routine,
 // shared by the manipulability stage (6x6 JJ^T, task_kernel.hip) and the
 // dynamics kernel (M, S^T M S; dynamics.hip) for the rare inputs whose full rank
-// the fast paths cannot certify.
+// the fast paths cannot certify, and by CLIK for J itself (pinv_cod_rect).
+// Plain host / device code without wave intrinsics: tools/pinv_cod_host_test.hip
+// runs both routines on the CPU against a 50-digit reference
+// (tests/test_pinv_cod_host.py).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "model.hpp"
+
+#ifndef DRC_HD
+#define DRC_HD __host__ __device__
+#endif
 
 namespace drc_amd {
 
@@ -16,7 +23,7 @@ constexpr double kPinvCodThreshold = 1e-6;  // COD_THRESHOLD (math_type_define.h
 // A[(i*n+j)*st]; X likewise; w: 3n^2+3n doubles): column-pivoted Householder QR, rank |R_ii| > 1e-6 max|R_ii|,
 // X = P W^T (W W^T)^-1 Q_r^T with W = R[:r, :] — the Moore-Penrose inverse of the
 // QR-truncated matrix, which is what Eigen's cod.pseudoInverse() returns.
-__device__ inline void pinv_cod_serial(const double* A, int n, int st, double* X, double* w) {
+DRC_HD inline void pinv_cod_serial(const double* A, int n, int st, double* X, double* w) {
   double* R = w;                 // n x n, Householder vectors below the diagonal
   double* G = w + n * n;         // r x r, then its Cholesky factor
   double* Y = w + 2 * n * n;     // n x r
@@ -133,7 +140,7 @@ __device__ inline void pinv_cod_serial(const double* A, int n, int st, double* X
 // n <= kMaxJoints) into X (n x m, row-major): column-pivoted Householder QR
 // (k < min(m, n)), rank |R_ii| > 1e-6 max|R_ii|, X = P W^T (W W^T)^-1 Q_r^T.
 // Serial (one lane); w: m*n + m*m + n*m + 3m + 2n doubles in LDS.
-__device__ inline void pinv_cod_rect(const double* A, int m, int n, double* X, double* w) {
+DRC_HD inline void pinv_cod_rect(const double* A, int m, int n, double* X, double* w) {
   double* R = w;               // m x n
   double* G = R + m * n;       // r x r (r <= m)
   double* Y = G + m * m;       // n x r

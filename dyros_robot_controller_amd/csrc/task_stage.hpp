@@ -783,7 +783,9 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     if (!(piv_min > 0) || !(fa * fi < 1e10)) {  // uniform
       const double dt = det_lu6_wave(A6);
       pinv_cod6_wave(A6, Ai, S + kp.kScr);
-      if (l == 0) S[kp.oSc + SC_MAN] = sqrt(dt);
+      // at a singularity det(JJ^T) is rounding noise of either sign: a negative
+      // one is zero, not NaN (a NaN input stays NaN); DESIGN.md "Manipulability at a singularity"
+      if (l == 0) S[kp.oSc + SC_MAN] = dt < 0 ? 0.0 : sqrt(dt);
     } else if (l == 0) {
       S[kp.oSc + SC_MAN] = sqrt(det);
     }

@@ -376,7 +376,10 @@ static void manip(const OracleModel* m, const Kin* k, const double* J, int c0, i
     for (int i = 0; i < 6; ++i) for (int c = 0; c < nc; ++c) Jr[i * nc + c] = J[i * nv + c0 + c];
     for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) { double s = 0; for (int c = 0; c < nc; ++c) s += Jr[i * nc + c] * Jr[j * nc + c]; A[i * 6 + j] = s; }
     double det = det_lu(A, 6);
-    *man = sqrt(det);
+    /* at a singularity det(JJ^T) is rounding noise of either sign; the reference's
+     * sqrt (robot_data.cpp:526) yields NaN for a negative one, this restatement
+     * zero (a NaN input stays NaN) */
+    *man = sqrt(det < 0 ? 0.0 : det);
     pinv_cod_sym(A, 6, Ai);
     /* W = Jr^T Ai  (nc x 6) */
     for (int c = 0; c < nc; ++c) for (int j = 0; j < 6; ++j) { double s = 0; for (int i = 0; i < 6; ++i) s += Jr[i * nc + c] * Ai[i * 6 + j]; W[c * 6 + j] = s; }

@@ -4,7 +4,9 @@ two_link(): planar 2R arm (joints about y, links along x) whose mass matrix,
 gravity and Coriolis terms have the textbook closed forms (Spong, Robot
 Modeling and Control, §7.4).  rank_deficient(): a 3R chain whose last link has
 no <inertial>, so M(q) has a zero row/column and PinvCOD must return the
-rank-2 pseudo-inverse (robot_data.cpp:118)."""
+rank-2 pseudo-inverse (robot_data.cpp:118).  swing_arm(): a 3R chain whose
+M(q) is well conditioned except where its long link lies on joint 1's axis,
+where it loses a mode (below)."""
 import os
 
 import numpy as np
@@ -70,6 +72,39 @@ def rank_deficient(dirpath):
 </robot>
 """
     path = os.path.join(dirpath, "rank_deficient.urdf")
+    with open(path, "w") as f:
+        f.write(urdf)
+    return path
+
+
+SWING = dict(m=5.0, L=0.8, rotor=2e-7)
+
+
+def swing_arm(dirpath):
+    """3R chain: joint 1 about z; joint 2 about y at the same point, carrying a
+    long slender link (length L along its x) with a heavy mass m at the tip;
+    joint 3 about that link's own x at the tip, carrying a compact body.  The
+    tip mass swings on and off joint 1's axis with q[1]: at q[1] = +-pi/2 the
+    link lies on the axis, joints 1 and 3 turn the same bodies about the same
+    line, and what is left of M's smallest mode is the base rotor's inertia,
+    6e-8 of the m L^2 = 3.2 that joint 2 always carries.  There PinvCOD drops
+    the mode; a few degrees away M is certified full rank (condition ~1e3)."""
+    p = SWING
+    urdf = f"""<?xml version="1.0"?>
+<robot name="swing_arm">
+  <link name="base"/>
+  <link name="a">{_inertial(0.3, (0.0, 0.0, 0.0), 1e-3, 1e-3, p['rotor'])}</link>
+  <link name="b">{_inertial(p['m'], (p['L'], 0.0, 0.0), 2e-3, 1e-8, 2e-3)}</link>
+  <link name="c">{_inertial(0.4, (0.0, 0.0, 0.0), 3e-3, 4e-3, 3e-3)}</link>
+  <joint name="j1" type="revolute"><parent link="base"/><child link="a"/>
+    <origin xyz="0 0 0.1" rpy="0 0 0"/><axis xyz="0 0 1"/><limit lower="-3" upper="3" velocity="2" effort="10"/></joint>
+  <joint name="j2" type="revolute"><parent link="a"/><child link="b"/>
+    <origin xyz="0 0 0" rpy="0 0 0"/><axis xyz="0 1 0"/><limit lower="-3" upper="3" velocity="2" effort="10"/></joint>
+  <joint name="j3" type="revolute"><parent link="b"/><child link="c"/>
+    <origin xyz="{p['L']!r} 0 0" rpy="0 0 0"/><axis xyz="1 0 0"/><limit lower="-3" upper="3" velocity="2" effort="10"/></joint>
+</robot>
+"""
+    path = os.path.join(dirpath, "swing_arm.urdf")
     with open(path, "w") as f:
         f.write(urdf)
     return path

@@ -8,12 +8,19 @@ Tolerance: 1e-8 relative to max(1, |out|_inf) on instances where the 6x6
 PinvCOD keeps every mode; where the oracle's COD truncates (a mode within
 1e-6 of the cut — the two sides may decide differently at the boundary) the
 instance is only required to agree to 1e-4 relative and such instances stay
-<= 5 %.  The oracle's M^-1, g come from the numpy restatement (pyref)."""
+<= 5 %.  The exemption is attributable: every instance above 1e-8 must have
+its deciding pivot ratio (the |R_kk| / |R_00| nearest the cut, from the
+pivoted QR of the matrix the reference decomposes: J for CLIK, J M^-1 J^T for
+OSF; tests/_singular.py) inside [1e-7, 1e-5].  An instance above 1e-8 outside
+that band is a bug to find, not a tolerance to widen; inputs chosen away from
+the cut are in tests/test_gpu_singular.py, with no exemption.  The oracle's
+M^-1, g come from the numpy restatement (pyref)."""
 import numpy as np
 import pytest
 
 import oracle as O
 import pyref as R
+import _singular as SG
 from _common import LINK, make_manipulator, step_inputs
 from dyros_robot_controller_amd import manipulator
 
@@ -22,6 +29,14 @@ pytestmark = pytest.mark.gpu
 
 def _rel(a, b):
     return np.abs(a - b).max(axis=0) / np.maximum(1.0, np.abs(b).max(axis=0))
+
+
+def _assert_close(rel, rho, what=""):
+    """rel: per-instance relative error; rho: per-instance deciding pivot ratio."""
+    off = rel > 1e-8
+    print(what, "instances above 1e-8: %d of %d, deciding ratios %s" % (off.sum(), len(rel), np.sort(rho[off])))
+    assert np.mean(off) <= 0.05 and np.all(rel <= 1e-4), (what, np.sort(rel)[-5:])
+    assert np.all((rho[off] >= 1e-7) & (rho[off] <= 1e-5)), (what, np.nonzero(off)[0], rel[off], rho[off])
 
 
 @pytest.mark.parametrize("robot", ["fr3", "ur5e"])
@@ -39,9 +54,9 @@ def test_clik_matches_oracle(cuda, robot):
     ref = np.stack([O.clik_one(om, par, q[:, b], qd[:, b], xt[:, b], xdt[:, b], null_qdot=nu[:, b])
                     for b in range(B)], axis=1)
     ref0 = np.stack([O.clik_one(om, par, q[:, b], qd[:, b], xt[:, b], xdt[:, b]) for b in range(B)], axis=1)
+    rho = np.array([SG.deciding_ratio(SG.pivot_ratios(SG.jacobian(om, q[:, b]))) for b in range(B)])
     for o, r in ((out, ref), (out0, ref0)):
-        rel = _rel(o, r)
-        assert np.mean(rel > 1e-8) <= 0.05 and np.all(rel <= 1e-4), np.sort(rel)[-5:]
+        _assert_close(_rel(o, r), rho, "CLIKStep")
     # CLIKCubic
     xi, xdi = xt.copy(), np.zeros((6, B))
     xi[9:] += 0.03
@@ -49,8 +64,7 @@ def test_clik_matches_oracle(cuda, robot):
     par.mode, par.t, par.t0, par.duration = 2, 0.3, 0.0, 1.0
     rc = np.stack([O.clik_one(om, par, q[:, b], qd[:, b], xt[:, b], xdt[:, b], xi[:, b], xdi[:, b])
                    for b in range(B)], axis=1)
-    rel = _rel(oc, rc)
-    assert np.mean(rel > 1e-8) <= 0.05 and np.all(rel <= 1e-4), np.sort(rel)[-5:]
+    _assert_close(_rel(oc, rc), rho, "CLIKCubic")
 
 
 @pytest.mark.parametrize("robot", ["fr3", "ur5e"])
@@ -64,6 +78,7 @@ def test_osf_matches_oracle(cuda, robot):
     pm, om, spec = O.load(robot)
     dyn = [R.dynamics(pm, q[:, b], qd[:, b]) for b in range(B)]
     par = O.default_params(0)
+    rho = np.array([SG.deciding_ratio(SG.pivot_ratios(SG.osf_matrix(om, q[:, b], dyn[b]["Minv"]))) for b in range(B)])
     cases = [(0, ctrl.OSF_batch(q, qd, xdd, LINK[robot], null_torque=nu), None, xdd, nu),
              (1, ctrl.OSF_step_batch(q, qd, xt, xdt, LINK[robot]), xt, xdt, None)]
     for mode, out, x_t, xd_t, nv_ in cases:
@@ -72,8 +87,7 @@ def test_osf_matches_oracle(cuda, robot):
         ref = np.stack([O.osf_one(om, par, q[:, b], qd[:, b], dyn[b]["Minv"], dyn[b]["g"],
                                   None if x_t is None else x_t[:, b], xd_t[:, b],
                                   null_torque=None if nv_ is None else nv_[:, b]) for b in range(B)], axis=1)
-        rel = _rel(out, ref)
-        assert np.mean(rel > 1e-8) <= 0.05 and np.all(rel <= 1e-4), (mode, np.sort(rel)[-5:])
+        _assert_close(_rel(out, ref), rho, "OSF mode %d" % mode)
 
 
 def test_single_instance_reference_signatures(cuda):

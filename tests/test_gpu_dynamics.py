@@ -10,7 +10,8 @@ import pytest
 import oracle as O
 import pyref as R
 from pyref_model import load_urdf
-from _dyn_models import two_link, two_link_closed_form, rank_deficient
+import _singular as SG
+from _dyn_models import two_link, two_link_closed_form, rank_deficient, swing_arm
 from dyros_robot_controller_amd import manipulator, _batch, workload
 from _common import make_manipulator, make_moma
 
@@ -101,6 +102,69 @@ def test_rank_deficient_pinv_cod_fallback(cuda, tmp_path):
         ref = R.dynamics(pm, q[:, b], qd[:, b])
         np.testing.assert_allclose(dev["Minv"][:, :, b], ref["Minv"], atol=1e-9 * np.abs(ref["Minv"]).max())
         assert np.abs(dev["Minv"][2, :, b]).max() < 1e-12
+
+
+def _mixed(classes, B, rng):
+    """B indices into a classified pool, K and T alternating with a random
+    phase per 16-robot block, so that every block of dyn_kernel holds both."""
+    k, t = (list(np.nonzero(classes == c)[0]) for c in (SG.K, SG.T))
+    idx = []
+    for blk in range(0, B, 16):
+        ph = int(rng.integers(0, 2))
+        for i in range(min(16, B - blk)):
+            idx.append((k if (i + ph) % 2 == 0 else t).pop())
+    return np.array(idx)
+
+
+def test_mixed_certified_and_queued_instances(cuda, tmp_path):
+    """The uncertified-instance queue with certified and uncertified robots in
+    the same 16-robot block.  Model: _dyn_models.swing_arm, whose M loses a
+    mode where the long link lies on joint 1's axis.  (The largest column norm
+    of a serial chain's M cannot vary much with q[1]: joint 2 always carries
+    the tip mass, M_11 = m L^2; what varies here is the smallest mode.)
+    Inputs: q uniform, and for the T half q[1] within 3e-4 rad of +-pi/2;
+    classes from pyref's M (tests/_singular.py), none ambiguous.  B = 203:
+    101 in class K (certified: estimate < 2.5e9), 102 in class T (pivot ratio
+    <= 3e-7: queued and truncated to rank 2), alternating within every block.
+    M^-1: _check's bound for K, 1e-9 relative for T; M, g, nle, c as in _check.
+    Measured on an MI355X, M^-1 relative to max|M^-1| against pyref: K 9.2e-14,
+    T 7.4e-14.
+
+    The actuated form (S^T M S) has no such test: of 512 workload states of
+    Husky-FR3 (stress tiers included; pyref) 491 are in class K and 21 are
+    ambiguous by the estimate alone (largest 3.5e9), none in F or T: the
+    smallest pivot ratio is 2.7e-5 and max column norm x |(S^T M S)^-1|_F,
+    which the kernel's certificate compares with 1e6, stays below 3.7e4.  Its
+    queue has no input on a whole-body robot of this repository."""
+    path = swing_arm(str(tmp_path))
+    pm = load_urdf(path)
+    rd = manipulator.RobotData(path, "", device=cuda)
+    rng = np.random.default_rng(14)
+    B, N = 203, 320
+    q, qd = rng.uniform(-3, 3, (3, N)), rng.uniform(-1.5, 1.5, (3, N))
+    near = np.arange(N) % 2 == 1
+    q[1, near] = rng.choice([-1.0, 1.0], near.sum()) * np.pi / 2 + rng.uniform(-3e-4, 3e-4, near.sum())
+    cls = np.array([SG.classify(R.mass_matrix(pm, q[:, b])) for b in range(N)])
+    idx = _mixed(cls, B, rng)
+    q, qd, cls = np.ascontiguousarray(q[:, idx]), np.ascontiguousarray(qd[:, idx]), cls[idx]
+    got = SG.counts(cls)
+    assert got[SG.K] >= 0.25 * B and got[SG.T] >= 0.25 * B and got[SG.K] + got[SG.T] == B, got
+    for blk in range(0, B, 16):
+        assert {SG.K, SG.T} <= set(cls[blk:blk + 16]), blk
+    dev = _run(rd, q, qd)
+    worst = {SG.K: 0.0, SG.T: 0.0}
+    for b in range(B):
+        ref = R.dynamics(pm, q[:, b], qd[:, b])
+        sX = np.abs(ref["Minv"]).max()
+        worst[cls[b]] = max(worst[cls[b]], np.abs(dev["Minv"][:, :, b] - ref["Minv"]).max() / sX)
+        if cls[b] == SG.K:
+            _check(dev, ref, b)
+        else:
+            assert np.linalg.matrix_rank(ref["Minv"], tol=1e-9 * sX) == 2
+            ref_k = dict(ref, Minv=dev["Minv"][:, :, b])   # M, g, nle, c by _check; Minv below
+            _check(dev, ref_k, b)
+            np.testing.assert_allclose(dev["Minv"][:, :, b], ref["Minv"], atol=1e-9 * sX, err_msg="Minv b=%d" % b)
+    print("swing_arm Minv worst relative error:", {c: "%.2e" % v for c, v in worst.items()}, got)
 
 
 def test_host_entry_and_getters(cuda):
