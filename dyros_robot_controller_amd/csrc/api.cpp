@@ -21,6 +21,7 @@
 #include "../../include/drc_amd_debug.h"
 #include "call_plan.hpp"
 #include "dynamics.hpp"
+#include "host_staging.hpp"
 #include "kernel_common.hpp"
 #include "launch.hpp"
 #include "mesh.hpp"
@@ -130,9 +131,9 @@ struct drc_model_impl {
   std::mutex host_mu;
   void* stage = nullptr;
   int64_t stage_bytes = 0;
-  // pinned host mirror of the staging buffer: the synchronous entries pack
-  // their inputs into it and copy them over in one transfer, and bring the
-  // outputs back in one (drc_qpik_host, drc_state_host: B = 1 control cycles)
+  // pinned host mirror of the staging buffer: every synchronous *_host entry
+  // packs its inputs into it and copies them over in one transfer, and brings
+  // the outputs back in one (HostStage; both grow together, ensure_staging)
   double* pinned = nullptr;
   int64_t pinned_bytes = 0;
   hipStream_t hstream = nullptr;
@@ -157,6 +158,11 @@ static int set_err(int code, const std::string& msg) {
     hipError_t e_ = (expr);                                                             \
     if (e_ != hipSuccess) return set_err(DRC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+// Widths of a model's vectors: the actuated joints (arm + wheels of a
+// whole-body robot; q-dot*, qddot and tau of the QP entries) and the arm
+static int actuated_width(const DevModel& d) { return d.kind == 1 ? d.n_arm + d.n_wheel : d.nv; }
+static int arm_width(const DevModel& d) { return d.kind == 1 ? d.n_arm : d.nv; }
 
 static void free_ctx(StreamCtx* c) {
   // the event outlives a destroyed stream: waiting on it orders the frees
@@ -2153,8 +2159,8 @@ int drc_model_info(const drc_model* m, int* dof, int* act, int* mani, int* mobi,
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
   const drc_amd::DevModel& d = m->hm.dev;
   if (dof) *dof = d.nv;
-  if (act) *act = d.kind == 1 ? d.n_arm + d.n_wheel : d.nv;
-  if (mani) *mani = d.kind == 1 ? d.n_arm : d.nv;
+  if (act) *act = drc_amd::actuated_width(d);
+  if (mani) *mani = drc_amd::arm_width(d);
   if (mobi) *mobi = d.kind == 1 ? d.n_wheel : 0;
   if (ngeom) *ngeom = d.ngeom;
   if (npairs) *npairs = d.npairs;
@@ -2597,66 +2603,10 @@ int drc_qpid_stages_batch(const drc_model* m, const drc_qpik_params* p, int64_t 
   return drc_amd::launch_qpid(m, p, 1, io, stream);
 }
 
-int drc_qpid_stages_host(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
-                         const double* xt, const double* xdt, const double* xi, const double* xdi, double* pose,
-                         double* jac, double* man, double* dist, int32_t* pair, double* xddot_des, double* jdot,
-                         double* qpid_terms, double* graddot) {
-  using drc_amd::set_err;
-  if (!m || !p) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
-  if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  const drc_amd::DevModel& d = m->hm.dev;
-  const int64_t n = d.nv, na = d.kind == 1 ? d.n_arm : n;
-  std::lock_guard<std::mutex> lk(m->host_mu);
-  HIP_TRY(hipSetDevice(m->device));
-  const double* src[6] = {q, qdot, xt, xdt, xi, xdi};
-  const int64_t rin[6] = {n, n, 12, 6, 12, 6};
-  double* outs[8] = {pose, jac, man, dist, xddot_des, jdot, qpid_terms, graddot};
-  const int64_t rout[8] = {12, 6 * n, 1 + na, 1 + n, 6, 6 * n, 8, na + n};
-  int64_t words = (B + 1) / 2;
-  for (int i = 0; i < 6; ++i) words += src[i] ? rin[i] * B : 0;
-  for (int i = 0; i < 8; ++i) words += outs[i] ? rout[i] * B : 0;
-  if (m->stage_bytes < words * 8) {
-    if (m->stage) (void)hipFree(m->stage);
-    m->stage = nullptr;
-    m->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&m->stage, words * 8));
-    m->stage_bytes = words * 8;
-  }
-  if (!m->hstream) HIP_TRY(hipStreamCreateWithFlags(&m->hstream, hipStreamNonBlocking));
-  double* dp = reinterpret_cast<double*>(m->stage);
-  const double* din[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 6; ++i)
-    if (src[i]) {
-      HIP_TRY(hipMemcpyAsync(dp, src[i], rin[i] * B * 8, hipMemcpyHostToDevice, m->hstream));
-      din[i] = dp;
-      dp += rin[i] * B;
-    }
-  double* dout[8] = {nullptr};
-  for (int i = 0; i < 8; ++i)
-    if (outs[i]) {
-      dout[i] = dp;
-      dp += rout[i] * B;
-    }
-  int32_t* dpair = pair ? reinterpret_cast<int32_t*>(dp) : nullptr;
-  int rc = drc_qpid_stages_batch(m, p, B, din[0], din[1], din[2], din[3], din[4], din[5], dout[0], dout[1], dout[2],
-                                 dout[3], dpair, dout[4], dout[5], dout[6], dout[7], m->hstream);
-  if (rc) return rc;
-  for (int i = 0; i < 8; ++i)
-    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], dout[i], rout[i] * B * 8, hipMemcpyDeviceToHost, m->hstream));
-  if (pair) HIP_TRY(hipMemcpyAsync(pair, dpair, B * 4, hipMemcpyDeviceToHost, m->hstream));
-  HIP_TRY(hipStreamSynchronize(m->hstream));
-  return DRC_OK;
-}
-
 }  // extern "C"
 
 // ---- host-buffer entry points (synchronous; staged through device memory) --
 namespace drc_amd {
-struct HostIO {
-  const double* src[6];  // q, qdot, xt, xdt, xi, xdi
-  int64_t rows[6];
-};
-
 // Device staging buffer and its pinned host mirror, both >= `words` doubles
 // (the caller holds m->host_mu).
 static int ensure_staging(drc_model* m, int64_t words) {
@@ -2683,21 +2633,6 @@ static int ensure_staging(drc_model* m, int64_t words) {
   return DRC_OK;
 }
 
-// A synchronous host-buffer call in one round trip: the inputs are packed
-// into the pinned mirror and sent in one transfer, `run` enqueues the
-// launches on m->hstream with device pointers into the staging buffer, and
-// the outputs (laid out contiguously after the inputs) come back in one
-// transfer.  in/out: host arrays and their sizes in 8-byte words (NULL arrays
-// are skipped; their device pointer is NULL too).
-struct HostArr {
-  const void* host;
-  int64_t words;
-};
-struct HostOut {
-  void* host;
-  int64_t words;      // staging space (whole 8-byte words)
-  int64_t bytes = -1;  // bytes copied back (default: words * 8)
-};
 static inline int64_t now_ns() {
   return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch())
       .count();
@@ -2724,110 +2659,121 @@ static int wait_done(drc_model* m) {
   return DRC_OK;
 }
 
-template <class Run>
-static int round_trip(drc_model* m, const HostArr* in, int nin, const HostOut* out, int nout, Run run) {
-  const int64_t t0 = m->tl_on ? now_ns() : 0;
-  int64_t wi = 0, wo = 0;
-  for (int i = 0; i < nin; ++i) wi += in[i].host ? in[i].words : 0;
-  for (int i = 0; i < nout; ++i) wo += out[i].host ? out[i].words : 0;
-  if (int rc = ensure_staging(m, wi + wo)) return rc;
-  double* dev = reinterpret_cast<double*>(m->stage);
-  const void* din[16] = {nullptr};
-  void* dout[16] = {nullptr};
-  int64_t o = 0;
-  for (int i = 0; i < nin; ++i)
-    if (in[i].host) {
-      std::memcpy(m->pinned + o, in[i].host, in[i].words * 8);
-      din[i] = dev + o;
-      o += in[i].words;
-    }
-  for (int i = 0; i < nout; ++i)
-    if (out[i].host) {
-      dout[i] = dev + o;
-      o += out[i].words;
-    }
-  const int64_t t1 = m->tl_on ? now_ns() : 0;
-  if (wi && hipMemcpyAsync(dev, m->pinned, wi * 8, hipMemcpyHostToDevice, m->hstream) != hipSuccess)
-    return drc_amd::set_err(DRC_ERR_HIP, "hipMemcpyAsync H2D");
-  if (int rc = run(din, dout)) return rc;
-  if (wo && hipMemcpyAsync(m->pinned + wi, dev + wi, wo * 8, hipMemcpyDeviceToHost, m->hstream) != hipSuccess)
-    return drc_amd::set_err(DRC_ERR_HIP, "hipMemcpyAsync D2H");
-  const int64_t t2 = m->tl_on ? now_ns() : 0;
-  if (int rc = wait_done(m)) return rc;
-  const int64_t t3 = m->tl_on ? now_ns() : 0;
-  o = wi;
-  for (int i = 0; i < nout; ++i)
-    if (out[i].host) {
-      std::memcpy(out[i].host, m->pinned + o, out[i].bytes >= 0 ? out[i].bytes : out[i].words * 8);
-      o += out[i].words;
-    }
-  if (m->tl_on) {
-    const int64_t t4 = now_ns();
-    for (int64_t v : {t0, t1, t2, t3, t4}) m->tl.push_back(v);
+// A synchronous host-buffer call in one round trip.  The entry registers each
+// of its host arrays once, with its element count and where the array's device
+// pointer goes (a NULL array gets a NULL device pointer and no space): in()
+// arrays are packed into the pinned mirror and sent in one transfer, out()
+// arrays lie after the inputs (host_staging.hpp) and come back in one
+// transfer.  run() sets the device pointers, sends the inputs, calls
+// `launches` (which enqueues on m->hstream), fetches the outputs, waits and
+// copies them to the caller.  The staging buffers are the model's: the object
+// holds m->host_mu from its construction to the entry's return.
+class HostStage {
+ public:
+  explicit HostStage(drc_model* m) : m_(m), lock_(m->host_mu) {}
+  template <class T>
+  void in(const T* host, int64_t count, const T** dev) {
+    add(host, nullptr, count, sizeof(T), dev,
+        [](void* to, void* p) { *static_cast<const T**>(to) = static_cast<const T*>(p); });
   }
-  return DRC_OK;
+  template <class T>
+  void out(T* host, int64_t count, T** dev) {
+    add(nullptr, host, count, sizeof(T), dev, [](void* to, void* p) { *static_cast<T**>(to) = static_cast<T*>(p); });
+  }
+  template <class Launches>
+  int run(Launches launches) {
+    drc_model* const m = m_;
+    if (full_) return set_err(DRC_ERR_INVALID_ARGUMENT, "too many host arrays in one call");
+    if (hipSetDevice(m->device) != hipSuccess) return set_err(DRC_ERR_HIP, "hipSetDevice");
+    const int64_t t0 = m->tl_on ? now_ns() : 0;
+    const int64_t wi = lay_.in_words, wo = lay_.out_words;
+    if (int rc = ensure_staging(m, wi + wo)) return rc;
+    double* dev = reinterpret_cast<double*>(m->stage);
+    for (int i = 0; i < lay_.n; ++i) {
+      arr_[i].set(arr_[i].dev, dev + lay_.offset(i));
+      if (arr_[i].src) std::memcpy(m->pinned + lay_.offset(i), arr_[i].src, lay_.r[i].bytes);
+    }
+    const int64_t t1 = m->tl_on ? now_ns() : 0;
+    if (wi && hipMemcpyAsync(dev, m->pinned, wi * 8, hipMemcpyHostToDevice, m->hstream) != hipSuccess)
+      return set_err(DRC_ERR_HIP, "hipMemcpyAsync H2D");
+    if (int rc = launches()) return rc;
+    if (wo && hipMemcpyAsync(m->pinned + wi, dev + wi, wo * 8, hipMemcpyDeviceToHost, m->hstream) != hipSuccess)
+      return set_err(DRC_ERR_HIP, "hipMemcpyAsync D2H");
+    const int64_t t2 = m->tl_on ? now_ns() : 0;
+    if (int rc = wait_done(m)) return rc;
+    const int64_t t3 = m->tl_on ? now_ns() : 0;
+    for (int i = 0; i < lay_.n; ++i)
+      if (arr_[i].dst) std::memcpy(arr_[i].dst, m->pinned + lay_.offset(i), lay_.r[i].bytes);
+    if (m->tl_on) {
+      const int64_t t4 = now_ns();
+      for (int64_t v : {t0, t1, t2, t3, t4}) m->tl.push_back(v);
+    }
+    return DRC_OK;
+  }
+
+ private:
+  struct Arr {
+    const void* src;  // the caller's input array, or
+    void* dst;        // the caller's output array
+    void* dev;        // the entry's device pointer of this array, set through
+    void (*set)(void* to, void* p);
+  };
+  void add(const void* src, void* dst, int64_t count, int elem_bytes, void* dev, void (*set)(void*, void*)) {
+    set(dev, nullptr);
+    const int i = lay_.add(src || dst, dst != nullptr, count, elem_bytes);
+    if (i == StagingLayout::kFull) full_ = true;
+    if (i >= 0) arr_[i] = {src, dst, dev, set};
+  }
+  drc_model* m_;
+  std::lock_guard<std::mutex> lock_;
+  StagingLayout lay_;
+  Arr arr_[StagingLayout::kMaxArrays];
+  bool full_ = false;
+};
+
+// The six task inputs of a controller entry, into the call record
+static void stage_task_inputs(HostStage& st, IO& io, int64_t nv, const double* q, const double* qdot,
+                              const double* xt, const double* xdt, const double* xi, const double* xdi) {
+  st.in(q, nv * io.B, &io.q);
+  st.in(qdot, nv * io.B, &io.qdot);
+  st.in(xt, 12 * io.B, &io.xt);
+  st.in(xdt, 6 * io.B, &io.xdt);
+  st.in(xi, 12 * io.B, &io.xi);
+  st.in(xdi, 6 * io.B, &io.xdi);
 }
 
-static int host_call(drc_model* m, const drc_qpik_params* p, int stages, int64_t B, const HostIO& in,
-                     double** outs, const int64_t* out_rows, int nouts, int32_t** iouts, int niouts,
-                     uint64_t* stamps = nullptr /* host [kStamps][B]: the kernels' stage stamps */) {
-  if (!m || !p) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
-  if (B <= 0) return B == 0 ? DRC_OK : drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  std::lock_guard<std::mutex> g(m->host_mu);
-  if (hipSetDevice(m->device) != hipSuccess) return drc_amd::set_err(DRC_ERR_HIP, "hipSetDevice");
-  HostArr ha[6];
-  for (int i = 0; i < 6; ++i) ha[i] = {in.src[i], in.rows[i] * B};
-  // outputs: the double arrays, the int32 arrays (one word per two), the stamps
-  HostOut ho[8 + 2 + 1];
-  int no = 0;
-  for (int i = 0; i < nouts; ++i) ho[no++] = {outs[i], out_rows[i] * B};
-  for (int i = 0; i < niouts; ++i) ho[no++] = {iouts[i], (B + 1) / 2, 4 * B};
-  ho[no++] = {stamps, stamps ? drc_amd::kStamps * B : 0};
-  auto run = [&](const void** din, void** dout) -> int {
-    const double* d[6];
-    for (int i = 0; i < 6; ++i) d[i] = static_cast<const double*>(din[i]);
-    double* od[8] = {nullptr};
-    for (int i = 0; i < nouts; ++i) od[i] = static_cast<double*>(dout[i]);
-    int32_t* oi[2] = {nullptr, nullptr};
-    for (int i = 0; i < niouts; ++i) oi[i] = static_cast<int32_t*>(dout[nouts + i]);
-    uint64_t* ds = static_cast<uint64_t*>(dout[nouts + niouts]);
-    if (ds && hipMemsetAsync(ds, 0, sizeof(uint64_t) * drc_amd::kStamps * B, m->hstream) != hipSuccess)
-      return drc_amd::set_err(DRC_ERR_HIP, "hipMemsetAsync(stamps)");
-    IO io = task_io(B, d[0], d[1], d[2], d[3], d[4], d[5]);
-    if (!stages) {  // outs: qdot_out; iouts: status, iters
-      io.out = od[0];
-      io.status = oi[0];
-      io.iters = oi[1];
-      io.stamps = ds;
-    } else {  // outs: pose, jac, man, dist, xdd; iouts: pair
-      io.st_pose = od[0];
-      io.st_jac = od[1];
-      io.st_man = od[2];
-      io.st_dist = od[3];
-      io.st_xdd = od[4];
-      io.st_pair = oi[0];
-    }
-    return drc_amd::launch(m, p, stages, io, m->hstream);
-  };
-  return round_trip(m, ha, 6, ho, no, run);
+// drc_qpik_host; with `stamps` (host [kStamps][B]) its two variants that also
+// return the kernels' stage stamps
+static int qpik_host(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
+                     const double* xt, const double* xdt, const double* xi, const double* xdi, double* out,
+                     int32_t* status, int32_t* iters, uint64_t* stamps) {
+  if (!m || !p) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  HostStage st(m);
+  IO io = make_io(B);
+  stage_task_inputs(st, io, m->hm.dev.nv, q, qdot, xt, xdt, xi, xdi);
+  st.out(out, actuated_width(m->hm.dev) * B, &io.out);
+  st.out(status, B, &io.status);
+  st.out(iters, B, &io.iters);
+  st.out(stamps, kStamps * B, &io.stamps);
+  return st.run([&]() -> int {
+    if (io.stamps && hipMemsetAsync(io.stamps, 0, sizeof(uint64_t) * kStamps * B, m->hstream) != hipSuccess)
+      return set_err(DRC_ERR_HIP, "hipMemsetAsync(stamps)");
+    return launch(m, p, 0, io, m->hstream);
+  });
 }
 }  // namespace drc_amd
 
 extern "C" {
-using drc_amd::HostIO;
-using drc_amd::host_call;
+using drc_amd::HostStage;
+using drc_amd::IO;
 
 int drc_qpik_host(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
                   const double* xt, const double* xdt, const double* xi, const double* xdi, double* out,
                   int32_t* status, int32_t* iters) {
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
   if (!out || !status) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "qdot_out and status are required");
-  const int64_t n = m->hm.dev.nv, a = m->hm.dev.kind == 1 ? m->hm.dev.n_arm + m->hm.dev.n_wheel : n;
-  HostIO in{{q, qdot, xt, xdt, xi, xdi}, {n, n, 12, 6, 12, 6}};
-  double* outs[1] = {out};
-  const int64_t rows[1] = {a};
-  int32_t* iouts[2] = {status, iters};
-  return host_call(m, p, 0, B, in, outs, rows, 1, iouts, 2);
+  return drc_amd::qpik_host(m, p, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, nullptr);
 }
 
 int drc_qpik_host_timed(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
@@ -2837,14 +2783,9 @@ int drc_qpik_host_timed(drc_model* m, const drc_qpik_params* p, int64_t B, const
   if (!out || !status || !ts) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "qdot_out, status and time_status are required");
   std::memset(ts, 0, sizeof(*ts));
   if (B <= 0) return B == 0 ? DRC_OK : drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  const int64_t n = m->hm.dev.nv, a = m->hm.dev.kind == 1 ? m->hm.dev.n_arm + m->hm.dev.n_wheel : n;
-  HostIO in{{q, qdot, xt, xdt, xi, xdi}, {n, n, 12, 6, 12, 6}};
-  double* outs[1] = {out};
-  const int64_t rows[1] = {a};
-  int32_t* iouts[2] = {status, iters};
   std::vector<uint64_t> st(static_cast<size_t>(drc_amd::kStamps * B));
   const auto t0 = std::chrono::steady_clock::now();
-  const int rc = host_call(m, p, 0, B, in, outs, rows, 1, iouts, 2, st.data());
+  const int rc = drc_amd::qpik_host(m, p, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, st.data());
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (rc) return rc;
   // stamps are s_memrealtime ticks (100 MHz); per-instance stage durations, averaged
@@ -2887,24 +2828,27 @@ int drc_debug_qpik_stamps(drc_model* m, const drc_qpik_params* p, int64_t B, con
                           int32_t* status, int32_t* iters, uint64_t* stamps) {
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
   if (!out || !status || !stamps) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "qdot_out, status and stamps are required");
-  const int64_t n = m->hm.dev.nv, a = m->hm.dev.kind == 1 ? m->hm.dev.n_arm + m->hm.dev.n_wheel : n;
-  HostIO in{{q, qdot, xt, xdt, xi, xdi}, {n, n, 12, 6, 12, 6}};
-  double* outs[1] = {out};
-  const int64_t rows[1] = {a};
-  int32_t* iouts[2] = {status, iters};
-  return host_call(m, p, 0, B, in, outs, rows, 1, iouts, 2, stamps);
+  return drc_amd::qpik_host(m, p, B, q, qdot, xt, xdt, xi, xdi, out, status, iters, stamps);
 }
 
 int drc_qpik_stages_host(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
                          const double* xt, const double* xdt, const double* xi, const double* xdi, double* pose,
                          double* jac, double* man, double* dist, int32_t* pair, double* xdd) {
-  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
-  const int64_t n = m->hm.dev.nv, na = m->hm.dev.kind == 1 ? m->hm.dev.n_arm : n;
-  HostIO in{{q, qdot, xt, xdt, xi, xdi}, {n, n, 12, 6, 12, 6}};
-  double* outs[5] = {pose, jac, man, dist, xdd};
-  const int64_t rows[5] = {12, 6 * n, 1 + na, 1 + n, 6};
-  int32_t* iouts[1] = {pair};
-  return host_call(m, p, 1, B, in, outs, rows, 5, iouts, 1);
+  using drc_amd::set_err;
+  if (!m) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  if (!p) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  const int64_t n = m->hm.dev.nv, na = drc_amd::arm_width(m->hm.dev);
+  HostStage st(m);
+  IO io = drc_amd::make_io(B);
+  drc_amd::stage_task_inputs(st, io, n, q, qdot, xt, xdt, xi, xdi);
+  st.out(pose, 12 * B, &io.st_pose);
+  st.out(jac, 6 * n * B, &io.st_jac);
+  st.out(man, (1 + na) * B, &io.st_man);
+  st.out(dist, (1 + n) * B, &io.st_dist);
+  st.out(xdd, 6 * B, &io.st_xdd);
+  st.out(pair, B, &io.st_pair);
+  return st.run([&] { return drc_amd::launch(m, p, 1, io, m->hstream); });
 }
 
 
@@ -2932,23 +2876,26 @@ int drc_state_host(drc_model* m, int frame_id, int64_t B, const double* q, const
   if (!q) return set_err(DRC_ERR_INVALID_ARGUMENT, "q is required");
   if ((xdot || nle || c) && !qdot) return set_err(DRC_ERR_INVALID_ARGUMENT, "qdot is required for xdot / nle / c");
   const int64_t n = m->hm.dev.nv;
-  std::lock_guard<std::mutex> lk(m->host_mu);
-  HIP_TRY(hipSetDevice(m->device));
-  const drc_amd::HostArr in[2] = {{q, n * B}, {qdot, n * B}};
-  const drc_amd::HostOut out[8] = {{pose, 12 * B}, {jac, 6 * n * B}, {xdot, 6 * B}, {M, n * n * B},
-                                   {M_inv, n * n * B}, {g, n * B}, {nle, n * B}, {c, n * B}};
-  auto run = [&](const void** din, void** dout) -> int {
-    const double* dq = static_cast<const double*>(din[0]);
-    const double* dqd = static_cast<const double*>(din[1]);
-    double* o[8];
-    for (int i = 0; i < 8; ++i) o[i] = static_cast<double*>(dout[i]);
+  HostStage st(m);
+  const double *dq, *dqd;
+  double *dpose, *djac, *dxdot, *dM, *dMinv, *dg, *dnle, *dc;
+  st.in(q, n * B, &dq);
+  st.in(qdot, n * B, &dqd);
+  st.out(pose, 12 * B, &dpose);
+  st.out(jac, 6 * n * B, &djac);
+  st.out(xdot, 6 * B, &dxdot);
+  st.out(M, n * n * B, &dM);
+  st.out(M_inv, n * n * B, &dMinv);
+  st.out(g, n * B, &dg);
+  st.out(nle, n * B, &dnle);
+  st.out(c, n * B, &dc);
+  return st.run([&]() -> int {
     if (pose || jac || xdot)
-      if (int rc = drc_kinematics_batch(m, frame_id, B, dq, dqd, o[0], o[1], o[2], m->hstream)) return rc;
+      if (int rc = drc_kinematics_batch(m, frame_id, B, dq, dqd, dpose, djac, dxdot, m->hstream)) return rc;
     if (M || M_inv || g || nle || c)
-      if (int rc = drc_dynamics_batch(m, 0, B, dq, dqd, o[3], o[4], o[5], o[6], o[7], m->hstream)) return rc;
+      if (int rc = drc_dynamics_batch(m, 0, B, dq, dqd, dM, dMinv, dg, dnle, dc, m->hstream)) return rc;
     return DRC_OK;
-  };
-  return drc_amd::round_trip(m, in, 2, out, 8, run);
+  });
 }
 
 // ---- closed-form controllers ------------------------------
@@ -2979,35 +2926,12 @@ int drc_closed_form_host(drc_model* m, const drc_qpik_params* p, int kind, int64
   if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   if (!out) return set_err(DRC_ERR_INVALID_ARGUMENT, "out is required");
   const int64_t n = m->hm.dev.nv;
-  std::lock_guard<std::mutex> lk(m->host_mu);
-  HIP_TRY(hipSetDevice(m->device));
-  const double* src[7] = {q, qdot, xt, xdt, xi, xdi, nullv};
-  const int64_t rows[7] = {n, n, 12, 6, 12, 6, n};
-  int64_t words = n * B;
-  for (int i = 0; i < 7; ++i) words += src[i] ? rows[i] * B : 0;
-  if (m->stage_bytes < words * 8) {
-    if (m->stage) (void)hipFree(m->stage);
-    m->stage = nullptr;
-    m->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&m->stage, words * 8));
-    m->stage_bytes = words * 8;
-  }
-  if (!m->hstream) HIP_TRY(hipStreamCreateWithFlags(&m->hstream, hipStreamNonBlocking));
-  double* dp = reinterpret_cast<double*>(m->stage);
-  const double* din[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 7; ++i)
-    if (src[i]) {
-      HIP_TRY(hipMemcpyAsync(dp, src[i], rows[i] * B * 8, hipMemcpyHostToDevice, m->hstream));
-      din[i] = dp;
-      dp += rows[i] * B;
-    }
-  drc_amd::IO io = drc_amd::task_io(B, din[0], din[1], din[2], din[3], din[4], din[5]);
-  io.cf_null = din[6];
-  io.out = dp;
-  if (int rc = drc_amd::launch_closed_form(m, p, kind, io, m->hstream)) return rc;
-  HIP_TRY(hipMemcpyAsync(out, dp, n * B * 8, hipMemcpyDeviceToHost, m->hstream));
-  HIP_TRY(hipStreamSynchronize(m->hstream));
-  return DRC_OK;
+  HostStage st(m);
+  IO io = drc_amd::make_io(B);
+  drc_amd::stage_task_inputs(st, io, n, q, qdot, xt, xdt, xi, xdi);
+  st.in(nullv, n * B, &io.cf_null);
+  st.out(out, n * B, &io.out);
+  return st.run([&] { return drc_amd::launch_closed_form(m, p, kind, io, m->hstream); });
 }
 
 int drc_qpid_host(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
@@ -3017,42 +2941,38 @@ int drc_qpid_host(drc_model* m, const drc_qpik_params* p, int64_t B, const doubl
   if (!m || !p) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   if (!qdd || !tau || !status) return set_err(DRC_ERR_INVALID_ARGUMENT, "qddot_out, tau_out and status are required");
-  const drc_amd::DevModel& d = m->hm.dev;
-  const int64_t n = d.nv, na = d.kind == 1 ? d.n_arm + d.n_wheel : n;
-  std::lock_guard<std::mutex> lk(m->host_mu);
-  HIP_TRY(hipSetDevice(m->device));
-  const double* src[6] = {q, qdot, xt, xdt, xi, xdi};
-  const int64_t rows[6] = {n, n, 12, 6, 12, 6};
-  int64_t words = 2 * na * B + B;  // outputs + status/iters
-  for (int i = 0; i < 6; ++i) words += src[i] ? rows[i] * B : 0;
-  if (m->stage_bytes < words * 8) {
-    if (m->stage) (void)hipFree(m->stage);
-    m->stage = nullptr;
-    m->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&m->stage, words * 8));
-    m->stage_bytes = words * 8;
-  }
-  if (!m->hstream) HIP_TRY(hipStreamCreateWithFlags(&m->hstream, hipStreamNonBlocking));
-  double* dp = reinterpret_cast<double*>(m->stage);
-  const double* din[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 6; ++i)
-    if (src[i]) {
-      HIP_TRY(hipMemcpyAsync(dp, src[i], rows[i] * B * 8, hipMemcpyHostToDevice, m->hstream));
-      din[i] = dp;
-      dp += rows[i] * B;
-    }
-  double* dqdd = dp;
-  double* dtau = dp + na * B;
-  int32_t* dst = reinterpret_cast<int32_t*>(dp + 2 * na * B);
-  int32_t* dit = iters ? dst + B : nullptr;
-  int rc = drc_qpid_batch(m, p, B, din[0], din[1], din[2], din[3], din[4], din[5], dqdd, dtau, dst, dit, m->hstream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(qdd, dqdd, na * B * 8, hipMemcpyDeviceToHost, m->hstream));
-  HIP_TRY(hipMemcpyAsync(tau, dtau, na * B * 8, hipMemcpyDeviceToHost, m->hstream));
-  HIP_TRY(hipMemcpyAsync(status, dst, B * 4, hipMemcpyDeviceToHost, m->hstream));
-  if (iters) HIP_TRY(hipMemcpyAsync(iters, dit, B * 4, hipMemcpyDeviceToHost, m->hstream));
-  HIP_TRY(hipStreamSynchronize(m->hstream));
-  return DRC_OK;
+  const int64_t na = drc_amd::actuated_width(m->hm.dev);
+  HostStage st(m);
+  IO io = drc_amd::make_io(B);
+  drc_amd::stage_task_inputs(st, io, m->hm.dev.nv, q, qdot, xt, xdt, xi, xdi);
+  st.out(qdd, na * B, &io.out);
+  st.out(tau, na * B, &io.out2);
+  st.out(status, B, &io.status);
+  st.out(iters, B, &io.iters);
+  return st.run([&] { return drc_amd::launch_qpid(m, p, 0, io, m->hstream); });
+}
+
+int drc_qpid_stages_host(drc_model* m, const drc_qpik_params* p, int64_t B, const double* q, const double* qdot,
+                         const double* xt, const double* xdt, const double* xi, const double* xdi, double* pose,
+                         double* jac, double* man, double* dist, int32_t* pair, double* xddot_des, double* jdot,
+                         double* qpid_terms, double* graddot) {
+  using drc_amd::set_err;
+  if (!m || !p) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  const int64_t n = m->hm.dev.nv, na = drc_amd::arm_width(m->hm.dev);
+  HostStage st(m);
+  IO io = drc_amd::make_io(B);
+  drc_amd::stage_task_inputs(st, io, n, q, qdot, xt, xdt, xi, xdi);
+  st.out(pose, 12 * B, &io.st_pose);
+  st.out(jac, 6 * n * B, &io.st_jac);
+  st.out(man, (1 + na) * B, &io.st_man);
+  st.out(dist, (1 + n) * B, &io.st_dist);
+  st.out(pair, B, &io.st_pair);
+  st.out(xddot_des, 6 * B, &io.st_xdd);
+  st.out(jdot, 6 * n * B, &io.st_jdot);
+  st.out(qpid_terms, 8 * B, &io.st_qpid);
+  st.out(graddot, (na + n) * B, &io.st_gdv);
+  return st.run([&] { return drc_amd::launch_qpid(m, p, 1, io, m->hstream); });
 }
 
 // ---- joint-space dynamics ------------------------------
@@ -3095,47 +3015,22 @@ int drc_dynamics_batch(drc_model* m, int actuated, int64_t B, const double* q, c
 int drc_dynamics_host(drc_model* m, int actuated, int64_t B, const double* q, const double* qdot, double* M,
                       double* M_inv, double* g, double* nle, double* c) {
   using drc_amd::set_err;
-  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
-  if (B <= 0) return B == 0 ? DRC_OK : drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  if (!q) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "q is required");
-  const drc_amd::DevModel& d = m->hm.dev;
-  const int64_t n = d.nv, no = actuated ? d.n_arm + d.n_wheel : n;
-  std::lock_guard<std::mutex> lk(m->host_mu);
-  HIP_TRY(hipSetDevice(m->device));
-  double* outs[5] = {M, M_inv, g, nle, c};
-  const int64_t rows[5] = {no * no, no * no, no, no, no};
-  int64_t words = (qdot ? 2 : 1) * n * B;
-  for (int i = 0; i < 5; ++i) words += outs[i] ? rows[i] * B : 0;
-  if (m->stage_bytes < words * 8) {
-    if (m->stage) (void)hipFree(m->stage);
-    m->stage = nullptr;
-    m->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&m->stage, words * 8));
-    m->stage_bytes = words * 8;
-  }
-  if (!m->hstream) HIP_TRY(hipStreamCreateWithFlags(&m->hstream, hipStreamNonBlocking));
-  double* dp = reinterpret_cast<double*>(m->stage);
-  double* dq = dp;
-  dp += n * B;
-  HIP_TRY(hipMemcpyAsync(dq, q, n * B * 8, hipMemcpyHostToDevice, m->hstream));
-  double* dqd = nullptr;
-  if (qdot) {
-    dqd = dp;
-    dp += n * B;
-    HIP_TRY(hipMemcpyAsync(dqd, qdot, n * B * 8, hipMemcpyHostToDevice, m->hstream));
-  }
-  double* dout[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 5; ++i)
-    if (outs[i]) {
-      dout[i] = dp;
-      dp += rows[i] * B;
-    }
-  int rc = drc_dynamics_batch(m, actuated, B, dq, dqd, dout[0], dout[1], dout[2], dout[3], dout[4], m->hstream);
-  if (rc) return rc;
-  for (int i = 0; i < 5; ++i)
-    if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], dout[i], rows[i] * B * 8, hipMemcpyDeviceToHost, m->hstream));
-  HIP_TRY(hipStreamSynchronize(m->hstream));
-  return DRC_OK;
+  if (!m) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (!q) return set_err(DRC_ERR_INVALID_ARGUMENT, "q is required");
+  const int64_t n = m->hm.dev.nv, no = actuated ? drc_amd::actuated_width(m->hm.dev) : n;
+  HostStage st(m);
+  const double *dq, *dqd;
+  double *dM, *dMinv, *dg, *dnle, *dc;
+  st.in(q, n * B, &dq);
+  st.in(qdot, n * B, &dqd);
+  st.out(M, no * no * B, &dM);
+  st.out(M_inv, no * no * B, &dMinv);
+  st.out(g, no * B, &dg);
+  st.out(nle, no * B, &dnle);
+  st.out(c, no * B, &dc);
+  // (a missing qdot, or `actuated` on a manipulator: the batch entry's errors)
+  return st.run([&] { return drc_dynamics_batch(m, actuated, B, dq, dqd, dM, dMinv, dg, dnle, dc, m->hstream); });
 }
 
 // ---- joint torque step ---------------------------------
@@ -3173,35 +3068,18 @@ int drc_joint_torque_step_host(drc_model* m, int64_t B, const double* q, const d
   if (m->hm.dev.nobst > 0) return set_err(DRC_ERR_UNSUPPORTED, drc_amd::kSlotsUnsupportedMsg);
   if (B <= 0) return B == 0 ? DRC_OK : set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
   if (!q || !tau) return set_err(DRC_ERR_INVALID_ARGUMENT, "q and tau are required");
-  const drc_amd::DevModel& d = m->hm.dev;
-  const int64_t n = d.nv, nb = d.kind == 1 ? d.n_arm : d.nv;
-  std::lock_guard<std::mutex> lk(m->host_mu);
-  HIP_TRY(hipSetDevice(m->device));
-  const double* src[5] = {q, qdot, q_target, qdot_target, qddot_target};
-  const int64_t rows[5] = {n, n, nb, nb, nb};
-  int64_t words = nb * B;
-  for (int i = 0; i < 5; ++i) words += src[i] ? rows[i] * B : 0;
-  if (m->stage_bytes < words * 8) {
-    if (m->stage) (void)hipFree(m->stage);
-    m->stage = nullptr;
-    m->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&m->stage, words * 8));
-    m->stage_bytes = words * 8;
-  }
-  if (!m->hstream) HIP_TRY(hipStreamCreateWithFlags(&m->hstream, hipStreamNonBlocking));
-  double* dp = reinterpret_cast<double*>(m->stage);
-  const double* din[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int i = 0; i < 5; ++i)
-    if (src[i]) {
-      HIP_TRY(hipMemcpyAsync(dp, src[i], rows[i] * B * 8, hipMemcpyHostToDevice, m->hstream));
-      din[i] = dp;
-      dp += rows[i] * B;
-    }
-  int rc = drc_joint_torque_step_batch(m, B, din[0], din[1], din[2], din[3], din[4], dt, kp, kv, dp, m->hstream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(tau, dp, nb * B * 8, hipMemcpyDeviceToHost, m->hstream));
-  HIP_TRY(hipStreamSynchronize(m->hstream));
-  return DRC_OK;
+  const int64_t n = m->hm.dev.nv, nb = drc_amd::arm_width(m->hm.dev);
+  HostStage st(m);
+  const double *dq, *dqd, *dqt, *dqdt, *dqddt;
+  double* dtau;
+  st.in(q, n * B, &dq);
+  st.in(qdot, n * B, &dqd);
+  st.in(q_target, nb * B, &dqt);
+  st.in(qdot_target, nb * B, &dqdt);
+  st.in(qddot_target, nb * B, &dqddt);
+  st.out(tau, nb * B, &dtau);
+  return st.run(
+      [&] { return drc_joint_torque_step_batch(m, B, dq, dqd, dqt, dqdt, dqddt, dt, kp, kv, dtau, m->hstream); });
 }
 
 }  // extern "C"

@@ -193,6 +193,40 @@ def test_host_timeline_and_waves(cuda):
     assert wt.value in (2, 3) and wq.value == 3
 
 
+def test_host_timeline_covers_every_host_entry(cuda):
+    """drc_debug_host_timeline "and the other *_host calls": one call of
+    drc_qpid_host, drc_qpid_stages_host, drc_closed_form_host,
+    drc_dynamics_host and drc_joint_torque_step_host each appends exactly one
+    row of five non-decreasing stamps."""
+    rd = make_manipulator("fr3", cuda)
+    B, n = 2, rd.model.dof
+    q, qd, xt, xdt = step_inputs(rd, "fr3", 37, B, cuda)
+    pid = manipulator.QPIKParamsBuilder(rd.model, exact=True, qpid=True).params(LINK["fr3"], _capi.MODE_QPID_STEP)
+    pik = manipulator.QPIKParamsBuilder(rd.model, exact=True).params(LINK["fr3"], _capi.MODE_QPIK_STEP)
+    f = lambda rows: np.zeros((rows, B))
+    s, pair = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    task = (dp(q), dp(qd), dp(xt), dp(xdt), None, None)
+    lib, h = _capi.lib(), rd.model.handle
+    calls = (
+        lambda: lib.drc_qpid_host(h, C.byref(pid), B, *task, dp(f(n)), dp(f(n)), ip(s), None),
+        lambda: lib.drc_qpid_stages_host(h, C.byref(pid), B, *task, dp(f(12)), dp(f(6 * n)), dp(f(1 + n)),
+                                         dp(f(1 + n)), ip(pair), dp(f(6)), dp(f(6 * n)), dp(f(8)), dp(f(2 * n))),
+        lambda: lib.drc_closed_form_host(h, C.byref(pik), 1, B, *task, None, dp(f(n))),
+        lambda: lib.drc_dynamics_host(h, 0, B, dp(q), dp(qd), dp(f(n * n)), dp(f(n * n)), dp(f(n)), dp(f(n)),
+                                      dp(f(n))),
+        lambda: lib.drc_joint_torque_step_host(h, B, dp(q), dp(qd), dp(q), dp(qd), None, 0.001, None, None,
+                                               dp(f(n))))
+    tl = np.zeros((4, 5), np.int64)
+    cnt = C.c_int64()
+    for call in calls:
+        _capi.check(lib.drc_debug_host_timeline(h, 1, None, 0, None))
+        _capi.check(call())
+        tl[:] = 0
+        _capi.check(lib.drc_debug_host_timeline(h, 0, tl.ctypes.data_as(C.POINTER(C.c_int64)), 4, C.byref(cnt)))
+        assert cnt.value == 1
+        assert np.all(np.diff(tl[0]) >= 0) and tl[0, 0] > 0 and np.all(tl[1:] == 0)
+
+
 def test_qpik_stamps_diagnostic(cuda):
     """drc_debug_qpik_stamps: the same outputs as drc_qpik_host, plus per
     instance six ordered clock stamps (task start / end, QP start / assembled /
