@@ -460,233 +460,6 @@ static int upload(drc_model_impl* m) {
   return DRC_OK;
 }
 
-// LDS plan: persistent QP region + a union of (kinematics | K^-1 | polish).
-// One plan per wave: every QP kernel runs one instance on the 64 lanes of a
-// wave (DESIGN.md "Out of scope" has the two-instances-per-wave build that was
-// tried and removed).  The compiled QP shapes: qp_compiled().
-// (poses_beside: the geometry poses outside the polytope overlay although the plan is narrow; plan_layout
-// lays the plan out again with it when the poses do not fit under the polytope)
-static int plan_layout(const DevModel& M, KParams* k, bool task_only, bool wide, bool poses_beside = false) {
-  int off = 0;
-  auto take = [&](int n) {
-    int o = off;
-    off += (n + 1) & ~1;  // keep 16-byte alignment
-    return o;
-  };
-  const int nx = k->nx, ng = k->ng, np = k->np, m = k->m, nv = M.nv;
-  if (task_only) {  // task_kernel: scalars + kinematics only (oRed: the winner's two witness points)
-    k->oRed = take(wide ? 64 : 8);
-    k->oSc = take(32);
-  } else {
-  k->oP = take(np * np);
-  k->oG = take(ng * nx);
-  k->oQ = take(nx);
-  k->oAB = take(nx);
-  k->oL = take(m);
-  k->oU = take(m);
-  k->oD = take(nx);
-  k->oE = take(m);
-  k->oDi = take(nx);
-  k->oEi = take(m);
-  k->oRho = take(m);
-  k->oX = take(nx);
-  k->oZ = take(m);
-  k->oY = take(m);
-  k->oDY = take(m);
-  k->oXT = take(nx);
-  k->oZT = take(m);
-  k->oT1 = take(m > nx ? m : nx);
-  k->oT2 = take(m > nx ? m : nx);
-  k->oRed = take(64);
-  k->oSc = take(32);
-  k->oBc = take(nx + ng > 32 ? nx + ng : 32);  // Ruiz factors (nx + ng), ADMM passes (ng + np), EQP (<= kEqpRegCap)
-  }
-  k->oHi = -1;
-  if (!task_only && k->problem == 0 && M.kind == 1 && qp_compiled(nx, ng, np)) k->oHi = take(nx * nx);
-  k->oU0 = off;
-  if (!task_only && k->problem == 0) {
-    // QPIK QP kernel: the union holds only what it uses -- the task record
-    // view (q, J, xdd, grad m, grad d, the mobile Jacobian, the task
-    // Jacobian), the factor (Schur blocks for the compiled shapes, K^-1
-    // otherwise) and the polish (index lists, x / y candidates; the LDS
-    // EQP only where a KKT can exceed the register EQP's kEqpRegCap).
-    // FR3: ~10 KB per wave instead of ~20.
-    int u = k->oU0;
-    auto takeu = [&](int n) {
-      int o = u;
-      u += (n + 1) & ~1;
-      return o;
-    };
-    k->kq = takeu(nv);
-    k->kJ = takeu(6 * nv);
-    k->kxdd = takeu(6);
-    k->kmg = takeu(k->narm);
-    k->kdg = takeu(nv);
-    k->kSv = takeu(3 * kMaxWheels);
-    k->kJt = takeu(6 * np);
-    const int kin_end = u;
-    const int fac_end = k->oU0 + (qp_compiled(nx, ng, np) ? np * np + ng * np + 4 * ng : nx * nx + nx * ng);
-    // manipulator QPs: the register EQP's size; a larger reduced KKT fails
-    // that polish attempt and ADMM continues (the oracle applies the same
-    // cap).  Whole-body QPs have no variable bounds, so every variable is free
-    // in the reduced KKT (N = nx + active rows): capped at 16 their polish
-    // fails whenever 6 (XLS-FR3) / 8 (Husky-FR3) rows are active and the
-    // instance runs to the tight ADMM fallback (up to ~3 000 iterations);
-    // they get the LDS EQP for N > 16
-    const int N = M.kind == 1 ? nx + ng : (nx + ng < kEqpRegCap ? nx + ng : kEqpRegCap);
-    k->ncap = N;
-    k->nbuf = (N + 7) & ~7;
-    const int reg_pol = k->oU0 + 128 + m;  // Fidx/Ridx | xx | yy
-    // (compiled whole-body shapes solve every polish KKT in range-space form,
-    // eqp_range: its H^-1 g_a buffer instead of the LDS LDL^T's)
-    const int lds_pol = k->oHi >= 0 ? k->oU0 + 256 + kEqpRegCap * nx
-                        : (qp_compiled(nx, ng, np) && N <= kEqpRegCap) ? 0
-                        : k->oU0 + 64 + 64 + 128 + k->nbuf * 5 + N * (N + 1) / 2;
-    int end = kin_end;
-    end = end > fac_end ? end : fac_end;
-    end = end > reg_pol ? end : reg_pol;
-    end = end > lds_pol ? end : lds_pol;
-    k->lds_doubles = (end + 1) & ~1;  // 16-byte aligned
-    if (end * 8 > 160 * 1024) return set_err(DRC_ERR_UNSUPPORTED, "model too large for the per-wave LDS plan");
-    return DRC_OK;
-  }
-  // kinematics view of the union
-  int u = k->oU0;
-  auto takeu = [&](int n) {
-    int o = u;
-    u += (n + 1) & ~1;
-    return o;
-  };
-  k->kT = takeu((nv + 1) * 12);
-  k->kZ = takeu((nv + 1) * 3);
-  k->kTe = takeu(12);
-  k->kJ = takeu(6 * nv);
-  const int ng_ = M.ngeom > nv ? M.ngeom : nv;  // (nv: the FK's local transforms, loc, use the poses' space first)
-  const bool epa = task_only && !k->cf;
-  // The geometry poses are read by the broad phase and the candidate GJKs;
-  // after those only EPA and the winner's refinement want the poses of one
-  // pair: EPA forms its pair's again in kPp and puts the winner's back in
-  // place when it is done.  So with EPA the poses go into the overlay below,
-  // under polytope fields that are written only once EPA runs.
-  const bool tg_over = epa && !wide && !poses_beside;
-  if (!tg_over) k->kTg = takeu(ng_ * 12);
-  k->kq = takeu(nv);
-  k->kqd = takeu(nv);
-  k->kPd = takeu(M.npairs);
-  k->kPf = takeu((M.npairs + 7) / 8);  // one byte per pair
-  k->kxdd = takeu(6);
-  k->kmg = takeu(k->narm);
-  k->kdg = takeu(nv);
-  k->kSv = takeu(3 * kMaxWheels);
-  // the pose pair of the pair EPA expands (2 x 12).  The QPIK task
-  // stage never stages the mobile Jacobian (QPID's extras and the QP kernels do),
-  // so there the pair takes kSv's place
-  static_assert(3 * kMaxWheels >= 24, "kSv holds the pose pair");
-  k->kPp = epa && k->problem == 1 ? takeu(24) : k->kSv;
-  // QPID's task extras read Ai and W after the collision stage
-  if (!epa || k->problem == 1) {
-    k->kAi = takeu(36);
-    k->kW = takeu(k->narm * 6);
-  }
-  if (k->problem == 1) {  // QPID stage data (task kernel) and dynamics (QP kernel)
-    k->kJd = takeu(6 * nv);
-    k->kDa = takeu(6 * k->narm);
-    k->kVf = takeu(nv);
-    k->kX6 = takeu(72 + 6 * k->narm + 2 * k->narm * k->narm);
-    k->kGdv = takeu(k->narm + nv);
-    k->kBias = takeu(8);
-    k->kMq = takeu(k->na * k->na);
-    k->kGq = takeu(k->na);
-  }
-  if (k->cf && k->cf != 3) {  // W, W2 (6 x nv), M^-1, nu, g, task vectors, then the serial COD work (+ its nv x 6 result)
-    const int ws = 6 * nv + 36 + 6 * nv + 18 + 2 * nv + 6 * nv;
-    k->kCf = takeu(2 * 6 * nv + nv * nv + 3 * nv + 48 + (ws > 160 ? ws : 160));
-  }
-  // Regions dead once the collision stage starts (manipulability work, the
-  // QP kernel's task Jacobian), then the EPA polytope laid over them: they
-  // share LDS, which keeps the QPIK task kernel within 20 KB per wave
-  // (8 waves per CU).  The GJK candidate list lives in the polytope's space
-  // too (it is consumed before EPA starts).
-  const int scr0 = u;
-  if (epa && k->problem != 1) {
-    k->kAi = takeu(36);
-    k->kW = takeu(k->narm * 6);
-  }
-  k->kA6 = takeu(36);
-  k->kPart = takeu(k->narm * k->narm);
-  k->kJt = takeu(6 * np);
-  k->kScr = takeu(160);  // serial 6x6 COD work (pinv_cod_serial: 3n^2 + 3n)
-  k->kOvl = 0;
-  if (epa) {
-    k->kEpa = scr0;
-    // (wide: the polytope's footprint before its index fields were narrowed, so
-    // that the wide plan has the former size and residency: A/B runs)
-    const int ep = scr0 + (wide ? 1178 : ((static_cast<int>((sizeof(EpaPoly) + 7) / 8) + 1) & ~1));
-    u = u > ep ? u : ep;
-    // int list of the GJK candidates, in the polytope's face planes (fn, fd):
-    // the candidate GJKs write the EPA seed stash (epa_stash: vertex slots
-    // kEpaStashV0.., out[], nv) while later candidates are still being read,
-    // so the list must not overlap those; the face planes are only written
-    // once EPA starts, after the last candidate is consumed
-    static_assert(sizeof(EpaPoly) <= 1178 * 8, "the wide plan's polytope footprint");
-    static_assert(offsetof(EpaPoly, fn) % 8 == 0 && offsetof(EpaPoly, fd) == offsetof(EpaPoly, fn) + sizeof(EpaPoly::fn),
-                  "face planes: one contiguous double-aligned region");
-    static_assert(sizeof(EpaPoly::fn) + sizeof(EpaPoly::fd) >= kMaxPairs * sizeof(int),
-                  "the face planes hold a candidate list of kMaxPairs ints");
-    static_assert(offsetof(EpaPoly, fn) >= sizeof(EpaPoly::vw) + sizeof(EpaPoly::va) &&
-                      offsetof(EpaPoly, out) >= offsetof(EpaPoly, fd) + sizeof(EpaPoly::fd) &&
-                      offsetof(EpaPoly, nv) > offsetof(EpaPoly, out),
-                  "stash (vw / va slots, out[], nv) outside the candidate list");
-    k->kCand = scr0 + static_cast<int>(offsetof(EpaPoly, fn) / 8);
-    k->kOvl = scr0;
-    if (tg_over) {
-      // The poses, then the candidate list, from the face planes on.  While the
-      // candidate GJKs read the poses, the stage writes the list (before),
-      // the stash and pd / pf (live region): poses and list may share bytes
-      // only with fields EPA writes later, [fn, out); and the poses start past
-      // the manipulability scratch (kAi .. kScr, written after the poses).
-      static_assert(offsetof(EpaPoly, out) % 8 == 0 && offsetof(EpaPoly, out) > offsetof(EpaPoly, alive) &&
-                        offsetof(EpaPoly, alive) > offsetof(EpaPoly, adj) && offsetof(EpaPoly, hl) > offsetof(EpaPoly, fd) &&
-                        offsetof(EpaPoly, fv) > offsetof(EpaPoly, fd) && offsetof(EpaPoly, freel) > offsetof(EpaPoly, fd) &&
-                        offsetof(EpaPoly, vout) > offsetof(EpaPoly, fd) && offsetof(EpaPoly, vin) > offsetof(EpaPoly, fd) &&
-                        offsetof(EpaPoly, adj) == offsetof(EpaPoly, fd) + sizeof(EpaPoly::fd),
-                    "fn .. alive: the fields EPA writes after the last candidate, then out[] and the counters");
-      const int scr_end = k->kScr + 160;
-      k->kTg = k->kCand > scr_end ? k->kCand : scr_end;
-      k->kCand = k->kTg + ng_ * 12;
-      // the fused kernels' record must leave the poses alone (an instance that
-      // ran no EPA refines its winner on them after the record is written);
-      // the list is dead by then
-      k->kOvl = k->kCand;
-    }
-    const int ce = k->kCand + (M.npairs + 1) / 2;
-    if (tg_over && ce > scr0 + static_cast<int>(offsetof(EpaPoly, out) / 8))  // a model with many geometries
-      return plan_layout(M, k, task_only, wide, true);
-    u = u > ce ? u : ce;
-  } else {
-    k->kEpa = 0;
-    k->kCand = takeu((M.npairs + 1) / 2);
-  }
-  int kin_end = u;
-  // K^-1 (nx * nx); QPIK plans keep the nx * ng doubles past it that the removed non-Schur register ADMM used
-  int kinv_end = k->oU0 + nx * nx + (k->problem == 1 ? 0 : nx * ng);
-  // polish KKT: free variables + active G rows.  QPID's (<= 81) is capped at 48 —
-  // typically 7 qdd + 7 tau + 7 equality rows + the few active CBF rows and free
-  // slacks — which halves the per-wave LDS; a larger guess fails that polish try
-  const int N = k->problem == 1 ? 48 : nx + ng;
-  k->ncap = N;
-  k->nbuf = N > 64 ? 128 : 64;
-  int pol_end = k->oU0 + 64 + 64 + 128 + k->nbuf * 5 + N * (N + 1) / 2;
-  int end = kin_end;
-  if (!task_only) {
-    end = end > kinv_end ? end : kinv_end;
-    end = end > pol_end ? end : pol_end;
-  }
-  k->lds_doubles = end;
-  if (end * 8 > 160 * 1024) return set_err(DRC_ERR_UNSUPPORTED, "model too large for the per-wave LDS plan");
-  return DRC_OK;
-}
-
 static int make_kparams(const drc_model_impl* mm, const drc_qpik_params* p, int stages, KParams* k,
                         int problem = 0, int cf = 0) {
   const DevModel& M = mm->hm.dev;
@@ -723,41 +496,12 @@ static int make_kparams(const drc_model_impl* mm, const drc_qpik_params* p, int 
   k->stages = stages;
   k->s = p->solver;
   k->eqp_small = mm->eqp_small_cap < 0 || mm->eqp_small_cap > kEqpSmallCap ? kEqpSmallCap : mm->eqp_small_cap;
-  k->nv = M.nv;
-  if (M.kind == 0) {
-    k->narm = M.nv;
-    k->c0 = 0;
-    k->np = M.nv;
-    k->nx = 3 * M.nv + 2;  // QP_IK.cpp:24-28
-    k->na = M.nv;
-  } else {
-    k->narm = M.n_arm;
-    k->c0 = M.mani_start;
-    k->np = M.n_arm + M.n_wheel;
-    k->nx = k->np;  // MoMa QP_IK.cpp:20
-    k->na = k->np;
-  }
-  k->ng = 2 * k->narm + 2;
-  if (problem == 1) {  // QPID: QP_ID.cpp:11-63 / MoMa QP_ID.cpp:11-33
-    k->nx = M.kind == 0 ? 6 * M.nv + 2 : 2 * k->na;
-    k->ng = 4 * k->narm + 2 + k->na;
-  }
-  k->m = k->nx + k->ng;
-  k->rJac = 0;
-  k->rMan = 6 * M.nv;
-  k->rDist = k->rMan + 1 + k->narm;
-  k->rXdd = k->rDist + 1 + M.nv;
-  k->rQ = k->rXdd + 6;
-  k->rQd = k->rQ + M.nv;
-  k->rBias = k->rQd + M.nv;
-  k->rMgd = k->rBias + 6;
-  k->rDgd = k->rMgd + 1;
-  k->rLen = problem == 1 ? k->rDgd + 1 : k->rQd;
-  k->xcd_map = 0;
-  if (k->nx > 64 || k->ng > 64 || k->narm > 8 || k->m > 128)
-    return set_err(DRC_ERR_UNSUPPORTED, "QP larger than one wavefront's row mapping");
+  if (plan_dims(M, k)) return set_err(DRC_ERR_UNSUPPORTED, "QP larger than one wavefront's row mapping");
   if (k->s.max_iter < 1 || k->s.check_termination < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "bad solver settings");
-  return plan_layout(M, k, stages != 0, mm->task_plan_wide);
+  // the LDS plan (lds_plan.hpp): the task kernel's, or the QP kernel's
+  if (stages ? plan_task(M, k, mm->task_plan_wide) : plan_qp(M, k, qp_compiled(k->nx, k->ng, k->np)))
+    return set_err(DRC_ERR_UNSUPPORTED, "model too large for the per-wave LDS plan");
+  return DRC_OK;
 }
 
 // The record of a call: kernel_common.hpp's IO, filled by field name.  The

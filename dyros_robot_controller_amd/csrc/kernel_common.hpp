@@ -32,42 +32,11 @@
 #include "pinv_cod.hpp"
 #include "qpik_device.hpp"
 #include "instrument.hpp"
+#include "lds_plan.hpp"
 
 namespace drc_amd {
 
-// Kernel parameters, passed by value.  LDS offsets (in doubles) are laid out
-// by the host from the model dimensions (see plan_layout()).
-struct KParams {
-  double kp[6], kv[6], ff, alpha_cbf, w_reg, slack_w, man_min, dist_min;
-  double t, t0, duration;
-  double frame_place[12];
-  int frame_joint, mode, stages;
-  int nv, nx, ng, np, na, m, narm, c0;
-  int xcd_map;                         // XCD-aware instance order (grid % 8 == 0)
-  int rJac, rMan, rDist, rXdd, rQ, rLen;  // per-instance task record (doubles)
-  int problem;                         // 0 QPIK, 1 QPID (torque-level QP)
-  int rQd, rBias, rMgd, rDgd;          // QPID extras of the task record
-  int nbuf;                            // polish work-vector stride (>= ncap)
-  int ncap;                            // largest polish KKT the LDS plan holds (nx + ng, or 48 for QPID)
-  int eqp_small;                       // polish: reduced KKTs of up to this many rows take the small EQP (<= kEqpSmallCap; 0 = never)
-  drc_solver_settings s;
-  // persistent QP region
-  int oP, oG, oQ, oAB, oL, oU, oD, oE, oRho, oX, oZ, oY, oDY, oXT, oZT, oT1, oT2, oRed, oSc;
-  int oDi, oEi;  // D^-1 and E^-1 beside the scaling (OSQP scaling.c keeps Dinv / Einv)
-  int oBc;  // max(32, nx + ng) doubles: vectors broadcast through LDS (ADMM passes, polish KKT sweeps)
-  // union region (kinematics | K^-1 | polish)
-  int oU0;
-  int oHi;  // whole-body polish: cached rows of (P + delta I)^-1 (persistent, nx * nx), -1 if unused
-  int kT, kZ, kTe, kJ, kTg, kq, kqd, kA6, kAi, kW, kPart, kPd, kPf, kCand, kxdd, kmg, kdg, kJt, kSv, kScr, kEpa;
-  int kPp;   // pose pair (2 x 12) of the pair EPA expands (task_stage.hpp)
-  int kOvl;  // first offset of the task plan's overlay that nothing reads once the task record is written
-  int kJd, kDa, kVf, kX6, kBias, kMq, kGq;  // QPID: Jdot, arm-only Jdot, S eta, 6x6 scratch, bias | M, g
-  int kGdv;                                 // QPID stage: grad_dot vectors
-  int cf;                                   // closed-form controller: 1 CLIK, 2 OSF (task_kernel<2>)
-  int kCf;                                  // its LDS work area
-  int lds_doubles;
-};
-
+// Kernel parameters (KParams, passed by value) with the LDS plan: lds_plan.hpp
 
 // diagnostic phase stamps: instrument.hpp (compile to nothing unless -DDRC_PHASE_TIMING)
 
@@ -322,26 +291,7 @@ struct InstSeq {
 // LDS (address space 3) views: an opaque copy of an LDS address must keep its
 // address space, or every access through it becomes a flat access (vector
 // memory path and its waits) instead of a ds_read / ds_write
-// The fused kernel's LDS: the task plan (kt) and the QP plan (kq) overlay each
-// other from offset 0, and the task record sits where neither stage touches it
-// while the other reads it: in the task plan's overlay region (from kOvl: EPA
-// polytope, GJK candidates, manipulability scratch -- dead once the record is
-// written, task_stage.hpp "task data out") when that region lies past the QP
-// plan and holds the record, else past both plans.  Whole-body plans then need
-// no extra space for the record: 8 instead of 7 fused waves per CU (r06).
-// Offsets in doubles; same function on the host (launch size) and the device.
-__host__ __device__ __forceinline__ int fused_rec_offset(const KParams& kt, const KParams& kq) {
-  const int rec = (kt.rLen + 1) & ~1;
-  const int plans = kt.lds_doubles > kq.lds_doubles ? kt.lds_doubles : kq.lds_doubles;
-  const int inside = kt.kOvl > kq.lds_doubles ? kt.kOvl : kq.lds_doubles;
-  return kt.kEpa > 0 && inside + rec <= kt.lds_doubles ? inside : plans;
-}
-__host__ __device__ __forceinline__ int fused_lds_doubles(const KParams& kt, const KParams& kq) {
-  const int plans = kt.lds_doubles > kq.lds_doubles ? kt.lds_doubles : kq.lds_doubles;
-  const int end = fused_rec_offset(kt, kq) + ((kt.rLen + 1) & ~1);
-  return end > plans ? end : plans;
-}
-
+// (where the fused kernels' record lies in LDS: lds_plan.hpp fused_rec_offset)
 typedef __attribute__((address_space(3))) double lds_double;
 typedef __attribute__((address_space(3))) const double lds_cdouble;
 typedef __attribute__((address_space(3))) const int lds_cint;
@@ -645,9 +595,7 @@ __device__ __forceinline__ void pinv_cod6_wave(const double* A, double* X, doubl
 }
 
 
-// Register EQP of the polish (eqp_regs): reduced KKTs of up to this many rows
-// are solved lane-per-row in registers; the LDS plan sizes follow it.
-constexpr int kEqpRegCap = 16;
+// (the register EQP's cap kEqpRegCap: lds_plan.hpp, whose plan sizes follow it)
 // Small EQP of the polish (eqp_small): the largest compiled tier.  Reduced
 // KKTs of the manipulator QPIK shapes with at most this many rows (FR3: 96 %
 // of them) are factored whole in every lane's registers.

@@ -16,7 +16,7 @@ namespace drc_amd {
 // pattern of qpik_pattern.hpp, and schur_setup, the Schur ADMM's G-column
 // pass, qp_scale_roles and the polish's Jacobi guess visit its nonzero entries
 // only.  These shapes reach the QP code only as QPIK on a fixed-base model
-// (make_kparams: kind 0 <=> np < nx, nx = np + ng, ng = 2 np + 2; QPID has its
+// (lds_plan.hpp plan_dims: kind 0 <=> np < nx, nx = np + ng, ng = 2 np + 2; QPID has its
 // own kernel and shapes).  Dims<..., dense = true> keeps the dense loops: the
 // reference build the sparse one is compared with bit for bit
 // (drc_debug_qp_dense, tests/test_gpu_qp_sparse.py).
@@ -1871,7 +1871,7 @@ __device__ __forceinline__ int qp_scale_roles(const KParams& kp, double* S) {
   PH_SINCE(65, sr_t1);  // V load
   PH_STAMP(sr_t2);
   auto clampf = [](double v) { return v < kMinScaling ? 1.0 : (v > kMaxScaling ? kMaxScaling : v); };
-  lds_double* wb = (lds_double*)(S + kp.oBc);  // NX + NG doubles (plan_layout)
+  lds_double* wb = (lds_double*)(S + kp.oBc);  // NX + NG doubles (lds_plan.hpp)
   for (int it = 0; it < kp.s.scaling; ++it) {
     PH_ADD(49, 1);  // Ruiz passes
     const double mx = absmax_tree(V);
@@ -2022,7 +2022,7 @@ __device__ __forceinline__ int qp_scale_roles_sparse(const KParams& kp, double* 
   PH_STAMP(sr_t2);
   double abl = ab[lc], ql = qq[lc], Dl = 1.0, El = 1.0, EGl = 1.0, cs = 1.0;
   auto clampf = [](double v) { return v < kMinScaling ? 1.0 : (v > kMaxScaling ? kMaxScaling : v); };
-  lds_double* wb = (lds_double*)(S + kp.oBc);  // NX + NG doubles (plan_layout)
+  lds_double* wb = (lds_double*)(S + kp.oBc);  // NX + NG doubles (lds_plan.hpp)
   for (int it = 0; it < kp.s.scaling; ++it) {
     PH_ADD(49, 1);  // Ruiz passes
     const double mx = absmax_tree(V);

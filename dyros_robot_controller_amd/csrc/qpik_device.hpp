@@ -12,6 +12,7 @@
 
 #include <cstdint>
 
+#include "epa_poly.hpp"
 #include "model.hpp"
 
 namespace drc_amd {
@@ -659,29 +660,7 @@ __device__ inline __noinline__ GjkDist gjk_wave(const SH A, const SH B, double c
 // runs a step on the whole wave (epa_grow_wave: component by ballots, horizon
 // compaction, cycle order by pointer jumping, one new face per lane);
 // epa_grow_canon is the lane-serial form (host harness, single-lane use).
-// caps: hpp-fcl's GJKSolver defaults (epa_max_vertex_num 64,
-// epa_max_face_num 128, epa_max_iterations 255), mirrored by the oracle
-constexpr int kEpaMaxV = 64, kEpaMaxF = 128;
-static_assert(kEpaMaxF == 128, "face bit masks are two 64-bit words");
-static_assert(kEpaMaxF <= 256 && kEpaMaxV <= 127, "EpaPoly's 8-bit face and horizon fields");
-struct EpaPoly {
-  double vw[kEpaMaxV][3], va[kEpaMaxV][3];
-  double fn[kEpaMaxF][3], fd[kEpaMaxF];
-  // narrow index types (faces < 128, edges < 3, vertices and horizon positions
-  // < 64): the polytope is most of the task kernel's per-wave LDS
-  // From fn to alive: written only once EPA runs, after the last GJK candidate
-  // is consumed.  The task plan lays the candidate list and the geometry poses
-  // over these fields (api.cpp plan_layout); what the candidate GJKs write
-  // (epa_stash: vertex slots, out[], nv) lies outside them.
-  int16_t adj[kEpaMaxF][3];  // neighbour across edge e: face | (its edge << 8)
-  int16_t hl[kEpaMaxV];      // a step's horizon edges: face | (edge << 8)
-  uint8_t fv[kEpaMaxF][3];
-  uint8_t freel[kEpaMaxF];  // recycled slots, last freed first
-  int8_t vout[kEpaMaxV], vin[kEpaMaxV];  // horizon edge leaving / entering each vertex (-1: none)
-  int8_t alive[kEpaMaxF];
-  double out[6];
-  int nv, nf, fail, stop, nfree;
-};
+// The polytope itself, EpaPoly with its caps kEpaMaxV / kEpaMaxF: epa_poly.hpp
 DRC_HD __forceinline__ V3 epa_vw(const EpaPoly* E, int i) { return v3(E->vw[i][0], E->vw[i][1], E->vw[i][2]); }
 DRC_HD __forceinline__ V3 epa_va(const EpaPoly* E, int i) { return v3(E->va[i][0], E->va[i][1], E->va[i][2]); }
 DRC_HD __forceinline__ void epa_addv(EpaPoly* E, V3 w, V3 a) {

@@ -45,14 +45,7 @@ __host__ __device__ __forceinline__ double rollout_time(double t, int k, double 
   return t + d;
 }
 
-// LDS of the state update: q_k [nv], eta_k [na], J_mobile [3][kMaxWheels].
-// It lies at the start of the plan, not past it: once the QP has stored its
-// outputs nothing in the plan is live (the next task stage rewrites it from
-// the state arrays), so the kernel needs no more LDS than the fused kernel
-// and keeps its waves per CU (fused_rec_offset's comment).
-__host__ __device__ __forceinline__ int rollout_state_doubles(const KParams& kt, const KParams& kq) {
-  return ((kt.nv + 1) & ~1) + ((kq.na + 1) & ~1) + 3 * kMaxWheels;
-}
+// (LDS of the state update, at the start of the plan: lds_plan.hpp rollout_state_doubles)
 
 // Orders this wave's global stores before its later loads of the same
 // addresses: the stores have completed when the wait returns, and a CU's

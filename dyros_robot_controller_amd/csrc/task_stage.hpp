@@ -997,7 +997,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   // lane expands the polytope, the whole wave scans for the closest face.
   // (Only pairs whose GJK intersected are searched: none, no search.)
   if (__any(pen)) {
-    // The task plan may lay the polytope over Tg (api.cpp plan_layout): from
+    // The task plan may lay the polytope over Tg (lds_plan.hpp plan_kinematics): from
     // here on the poses in Tg are gone.  EPA works on the poses of its pair,
     // formed again in Pp; after the search the winner's two poses go back to
     // their places in Tg, where the refinement (and dist_rate) read them as

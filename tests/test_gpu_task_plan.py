@@ -1,5 +1,5 @@
-"""The task plan with the geometry poses under the EPA polytope (api.cpp
-plan_layout) against the wide plan that keeps them beside it
+"""The task plan with the geometry poses under the EPA polytope (lds_plan.hpp
+plan_kinematics) against the wide plan that keeps them beside it
 (drc_debug_task_plan_wide), on the same build and the same inputs.
 
 The device code is the same for both layouts; only where data lie in LDS
