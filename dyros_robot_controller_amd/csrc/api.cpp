@@ -29,15 +29,26 @@
 #include "reach_path.hpp"
 #include "reach_seeds.hpp"
 #include "rollout_update.hpp"
+#include "scratch_layout.hpp"
 
 // ==========================================================================
 // host side: the C-ABI (include/drc_amd.h)
 // ==========================================================================
 namespace drc_amd {
 
-// Per-stream scratch of a model: the task-record pool, the work-queue
-// counters and the COD list.  Calls on one stream are ordered by that stream,
-// so they may share it; calls on two streams get disjoint contexts (the
+// A block of device scratch: grown to what a call needs, never shrunk (grow)
+struct Block {
+  void* p = nullptr;
+  int64_t bytes = 0;
+};
+
+// Per-stream scratch of a model: the work-queue counters and four blocks,
+// each carved by the layouts of scratch_layout.hpp (DESIGN.md "Stream
+// scratch").  There are several because calls nest: a stepwise closed-loop
+// call holds `roll` while each of its steps uses `pool`, and a stepwise seeds
+// call holds `seeds` around a reach that uses `roll`.  Calls on one stream
+// are ordered by that stream, so they may share it; calls on two streams get
+// disjoint contexts (the
 // C-ABI's "reentrant per stream", include/drc_amd.h).  At most kMaxStreamCtx
 // contexts are kept: a new stream beyond that evicts the least recently used
 // one (once the last call that used it has finished: `done`, an event recorded
@@ -48,8 +59,7 @@ struct StreamCtx {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;  // recorded on `stream` after every call's launches
   uint64_t last_use = 0;
-  void* pool = nullptr;  // task records / QPID dynamics / OSF M^-1, g
-  int64_t pool_bytes = 0;
+  Block pool;  // task records, hard and order lists / QPID records and dynamics / OSF M^-1, g
   // work-queue counters, one slot of kSlotInts per launch sequence: slots
   // 0..15 the QPIK sub-batches, 16 QPID, 17 the closed-form controllers.  In a
   // slot: the task (or fused) kernel's queue and the QP kernel's, one counter
@@ -62,12 +72,9 @@ struct StreamCtx {
                 "the users of a queue slot do not overlap and fit it");
   static constexpr int kQueueSlotQpid = 16, kQueueSlotCf = 17, kQueueInts = 18 * kSlotInts;
   int* d_queue = nullptr;
-  int* dyn_list = nullptr;  // instances whose M_inv needs the serial COD
-  int64_t dyn_list_cap = 0;
-  void* roll = nullptr;  // rollout / reach / reach path scratch: one step's eta, stage outputs, status, counters
-  int64_t roll_bytes = 0;
-  void* seeds = nullptr;  // drc_qpik_reach_seeds_batch: per-instance results, expanded targets, group words
-  int64_t seeds_bytes = 0;
+  Block dyn_list;  // instances whose M_inv needs the serial COD
+  Block roll;      // rollout / reach / reach path scratch: one step's eta, stage outputs, status, counters
+  Block seeds;     // drc_qpik_reach_seeds_batch: per-instance results, expanded targets, group words
 };
 constexpr size_t kMaxStreamCtx = 8;
 
@@ -170,42 +177,12 @@ static void free_ctx(StreamCtx* c) {
   if (c->done) (void)hipEventSynchronize(c->done), (void)hipEventDestroy(c->done);
   c->done = nullptr;
   if (c->d_queue) (void)hipFree(c->d_queue);
-  if (c->pool) (void)hipFree(c->pool);
-  if (c->dyn_list) (void)hipFree(c->dyn_list);
-  if (c->roll) (void)hipFree(c->roll);
-  c->roll = nullptr;
-  c->roll_bytes = 0;
-  if (c->seeds) (void)hipFree(c->seeds);
-  c->seeds = nullptr;
-  c->seeds_bytes = 0;
   c->d_queue = nullptr;
-  c->pool = nullptr;
-  c->dyn_list = nullptr;
-}
-
-// Records a stream context's `done` event on every exit of a launch path
-// once the context is in use, so eviction (free_ctx) never frees scratch that
-// kernels of this call still use.  Every launch path enqueues on the caller's
-// stream only, except the QPIK path's concurrent sub-batches: a call that
-// fails after forking may have left kernels on the model's internal fork /
-// side streams that `done` on the caller's stream does not follow, so that
-// path (forks set) waits for those streams -- the model's own, never the
-// device: other streams and models in the process are not stalled, and a
-// failure before anything was forked costs no synchronisation at all.
-struct DoneGuard {
-  StreamCtx* const& cx;
-  hipStream_t st;
-  const Lanes* forks = nullptr;  // set once a sub-batch may run on a fork stream
-  bool ok = false;
-  ~DoneGuard() {
-    if (!cx || !cx->done) return;
-    if (!ok && forks) {
-      for (hipStream_t s : forks->lanes) (void)hipStreamSynchronize(s);
-      for (hipStream_t s : forks->sides) (void)hipStreamSynchronize(s);
-    }
-    (void)hipEventRecord(cx->done, st);
+  for (Block* b : {&c->pool, &c->dyn_list, &c->roll, &c->seeds}) {
+    if (b->p) (void)hipFree(b->p);
+    *b = Block();
   }
-};
+}
 
 // A tuning knob from the environment: its integer value when set and
 // parsable, clamped to >= lo; otherwise the default.
@@ -246,15 +223,69 @@ static int stream_ctx(drc_model_impl* m, hipStream_t st, StreamCtx** out) {
   m->ctxs.push_back(std::move(c));
   return DRC_OK;
 }
-static int ensure_pool(StreamCtx* c, int64_t bytes) {
-  if (c->pool_bytes >= bytes) return DRC_OK;
-  if (c->pool) HIP_TRY(hipFree(c->pool));  // synchronises: no launch still reads it
-  c->pool = nullptr;
-  c->pool_bytes = 0;
-  HIP_TRY(hipMalloc(&c->pool, bytes));
-  c->pool_bytes = bytes;
+// Grows a block to exactly `bytes` (no head-room: tests/test_gpu_streams.py
+// bounds what a model holds); the caller holds m->mu
+static int grow(Block* b, int64_t bytes) {
+  if (b->bytes >= bytes) return DRC_OK;
+  if (b->p) HIP_TRY(hipFree(b->p));  // synchronises: no launch still uses it
+  *b = Block();
+  HIP_TRY(hipMalloc(&b->p, bytes));
+  b->bytes = bytes;
   return DRC_OK;
 }
+
+// The start and the end of every launch path: selects the model's device,
+// takes the caller stream's context, grows and carves the blocks the path
+// names, and records the context's `done` event on every exit once the context
+// is in use, so eviction (free_ctx) never frees scratch that kernels of this
+// call still use.  Every launch path enqueues on the caller's stream only,
+// except the QPIK path's concurrent sub-batches: a call that fails after
+// forking may have left kernels on the model's internal fork / side streams
+// that `done` on the caller's stream does not follow, so that path (forks set)
+// waits for those streams -- the model's own, never the device: other streams
+// and models in the process are not stalled, and a failure before anything was
+// forked costs no synchronisation at all.
+// (the caller holds m->launch_mu, from before the Launch is made until after
+// it is gone: `done` is recorded on a context that nobody can have evicted)
+struct Launch {
+  drc_model_impl* m;
+  hipStream_t st;
+  StreamCtx* cx = nullptr;
+  const Lanes* forks = nullptr;  // set once a sub-batch may run on a fork stream
+  bool ok = false;
+  Launch(drc_model_impl* model, void* stream) : m(model), st(reinterpret_cast<hipStream_t>(stream)) {}
+  Launch(const Launch&) = delete;
+  ~Launch() {
+    if (!cx || !cx->done) return;
+    if (!ok && forks) {
+      for (hipStream_t s : forks->lanes) (void)hipStreamSynchronize(s);
+      for (hipStream_t s : forks->sides) (void)hipStreamSynchronize(s);
+    }
+    (void)hipEventRecord(cx->done, st);
+  }
+  int context() {
+    std::lock_guard<std::mutex> g(m->mu);
+    return stream_ctx(m, st, &cx);
+  }
+  int begin() {
+    HIP_TRY(hipSetDevice(m->device));
+    return context();
+  }
+  // One block of the context by its layout (scratch_layout.hpp): measured
+  // without a base, grown to the layout's bytes, carved
+  template <class F, class L>
+  int carve(Block StreamCtx::*block, F layout, L* out) {
+    std::lock_guard<std::mutex> g(m->mu);
+    Block* b = &(cx->*block);
+    if (int r = grow(b, layout(nullptr).bytes)) return r;
+    *out = layout(b->p);
+    return DRC_OK;
+  }
+  int done() {
+    ok = true;
+    return DRC_OK;
+  }
+};
 static void free_lanes(Lanes* c) {
   for (hipStream_t ls : c->lanes) (void)hipStreamSynchronize(ls);
   for (hipStream_t ls : c->sides) (void)hipStreamSynchronize(ls);
@@ -607,35 +638,23 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     rc = make_kparams(m, params, 0, &kq);
     if (rc) return rc;
   }
-  HIP_TRY(hipSetDevice(m->device));
-  // product path: per-instance task records (rLen doubles padded to whole
-  // 128-B lines) in a model-owned pool; the stage API writes [field][B]
-  const int64_t stride = (kt.rLen + 15) & ~int64_t(15);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  double* rec = nullptr;
-  int* hard = nullptr;           // lane-stage hard list, B ints
-  uint8_t* hard_flag = nullptr;  // and its per-instance flags
-  StreamCtx* cx = nullptr;
-  DoneGuard done_guard{cx, st};
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
+  // product path: per-instance task records in the stream's pool; the stage
+  // API writes [field][B]
+  const int64_t stride = record_stride(kt.rLen);
   const DevModel& dm = m->hm.dev;
   const PlanIn pin = plan_in(m, B, stages, stages ? nullptr : &kq);
   const CallPlan plan = plan_call(pin);
   const bool lane = plan.lane, fuse = plan.fuse, auto_order = plan.auto_order;
   const int ls = m->lane_stage, S = plan.S;
-  int32_t* order_buf = nullptr;
-  {
-    std::lock_guard<std::mutex> g(m->mu);
-    if (int r = stream_ctx(m, st, &cx)) return r;
-    if (!stages || lane) {
-      const int64_t rec_bytes = stages ? 0 : stride * B * 8;
-      const int64_t ord_off = (rec_bytes + B * 4 + B + 7) & ~int64_t(7);
-      if (int r = ensure_pool(cx, ord_off + (auto_order ? B * 9 : 0))) return r;
-      if (!stages) rec = reinterpret_cast<double*>(cx->pool);
-      hard = reinterpret_cast<int*>(static_cast<char*>(cx->pool) + rec_bytes);
-      hard_flag = reinterpret_cast<uint8_t*>(static_cast<char*>(cx->pool) + rec_bytes + B * 4);
-      if (auto_order) order_buf = reinterpret_cast<int32_t*>(static_cast<char*>(cx->pool) + ord_off);
-    }
-  }
+  QpikPool pool{};
+  if (!stages || lane)
+    if (int r = L.carve(&StreamCtx::pool, [&](void* p) { return qpik_pool(p, stride, B, stages != 0, auto_order); },
+                        &pool))
+      return r;
   const bool timed = m->timing && !stages;
   std::vector<hipEvent_t> tev;
   // (timing events come from the model's pool: creating five to fourteen
@@ -684,7 +703,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     if (int r = mkev(&e_end)) return r;
     HIP_TRY(hipEventRecord(e_start, st));
   }
-  done_guard.forks = &m->ln;  // (launch_mu held: the stream lists do not change under it)
+  L.forks = &m->ln;  // (launch_mu held: the stream lists do not change under it)
   if (S > 1) HIP_TRY(hipEventRecord(m->ln.fork, st));
   for (int c = 0; c < S; ++c) {
     const SubBatch sb = plan_sub_batch(pin, plan, c);
@@ -701,7 +720,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     IO io = call;
     io.B = Bc;
     io.b0 = b0;
-    io.rec = rec ? rec + b0 * stride : nullptr;
+    io.rec = pool.rec ? pool.rec + b0 * stride : nullptr;
     io.rec_stride = stride;
     if (stages) io.stamps = nullptr;
     io.order = plan.use_caller_order ? m->d_order : nullptr;
@@ -754,12 +773,10 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
       HIP_TRY(static_cast<hipError_t>(launch_qp_kernel(static_cast<unsigned>(gq), lds_q, cs, m->d_model, kq_c, io)));
       return DRC_OK;
     };
-    if (order_buf) {  // this sub-batch's order (hot count in the zeroed queue slot; hot list / flags after it)
-      int32_t* hl = order_buf + B + b0;
-      uint8_t* hf = reinterpret_cast<uint8_t*>(order_buf + 2 * B) + b0;
-      HIP_TRY(static_cast<hipError_t>(
-          launch_order_kernel(Bc, cs, m->d_model, io, qc + StreamCtx::kSlotHot, hl, hf, order_buf)));
-      io.order = order_buf;
+    if (pool.order) {  // this sub-batch's order (hot count in the zeroed queue slot; hot list / flags after it)
+      HIP_TRY(static_cast<hipError_t>(launch_order_kernel(Bc, cs, m->d_model, io, qc + StreamCtx::kSlotHot,
+                                                          pool.hot + b0, pool.hot_flag + b0, pool.order)));
+      io.order = pool.order;
     }
     if (fuse) {  // one fused task + QP kernel, the record in LDS
       const int64_t gf = sb.grid_fused;
@@ -780,9 +797,9 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     } else {
       // lane stage for every instance; the wave-per-instance task kernel only
       // for the instances it hands back (hard list)
-      io.hard_list = hard + b0;
+      io.hard_list = pool.hard + b0;
       io.hard_n = qc + StreamCtx::kSlotHard;
-      io.hard_flag = stages ? nullptr : hard_flag + b0;
+      io.hard_flag = stages ? nullptr : pool.hard_flag + b0;
       const unsigned gl = static_cast<unsigned>((Bc + 63) / 64);  // one lane per instance
       HIP_TRY(static_cast<hipError_t>(launch_lane_task_kernel(dm.nv, gl, cs, m->d_model, kt_c, io)));
       if (timed) HIP_TRY(hipEventRecord(e1, cs));
@@ -818,8 +835,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     std::lock_guard<std::mutex> g(m->mu);
     m->events.push_back({ev, S});
   }
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int stages, const IO& call, void* stream,
@@ -876,29 +892,6 @@ static int make_kparams_pair(const drc_model_impl* m, const drc_qpik_params* par
   if (int rc = make_kparams(m, params, 1, kt)) return rc;
   return make_kparams(m, params, 0, kq);
 }
-
-// Grows a stream context's scratch block (cx->roll, cx->seeds) to `bytes`; the
-// caller holds m->mu
-static int grow_scratch(void** p, int64_t* have, int64_t bytes) {
-  if (*have >= bytes) return DRC_OK;
-  if (*p) HIP_TRY(hipFree(*p));  // synchronises: no launch still uses it
-  *p = nullptr;
-  *have = 0;
-  HIP_TRY(hipMalloc(p, bytes));
-  *have = bytes;
-  return DRC_OK;
-}
-// Carves arrays off a scratch block one after the other: the doubles first,
-// then the int32 arrays, so every array is aligned to its element
-struct Carver {
-  char* p;
-  template <class T>
-  T* take(int64_t n) {
-    T* r = reinterpret_cast<T*>(p);
-    p += n * int64_t(sizeof(T));
-    return r;
-  }
-};
 
 // What a persistent closed-loop launch needs first: the grid, the placement
 // and the zeroed work queue of io, the caller's IO of the whole batch (q, qdot,
@@ -961,8 +954,10 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   KParams kt, kq;
   if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (B == 0) return DRC_OK;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
   // The persistent kernel up to the batch size where it was measured to beat
@@ -975,17 +970,10 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   const int64_t rollout_max = env_int("DRC_ROLLOUT_MAX", dm.kind == 0 ? 4096 : 65536, 0);
   // (models with obstacle slots: the stepwise path; no persistent build takes poses)
   const bool persistent = persistent_path(plan_in(m, B, 0, &kq), rollout_max, true, false);
-  StreamCtx* cx = nullptr;
-  DoneGuard done_guard{cx, st};
-  double* eta = qdot_traj;  // without qdot_traj: one step's eta in stream scratch
-  {
-    std::lock_guard<std::mutex> g(m->mu);
-    if (int r = stream_ctx(m, st, &cx)) return r;
-    if (!qdot_traj) {
-      if (int r = grow_scratch(&cx->roll, &cx->roll_bytes, int64_t(na) * B * 8)) return r;
-      eta = static_cast<double*>(cx->roll);
-    }
-  }
+  RolloutScratch sc;
+  if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return rollout_scratch(p, na, B, qdot_traj != nullptr); }, &sc))
+    return r;
+  double* eta = qdot_traj ? qdot_traj : sc.eta;  // without qdot_traj: one step's eta in stream scratch
   const int64_t out_step = qdot_traj ? int64_t(na) * B : 0;
   if (persistent) {
     IO io = in;
@@ -996,8 +984,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_kernel(grid, st, m->d_model, kt, kq, io, steps, per_step, dt, qf, vf,
                                                           q_traj, pose_traj, dist_traj, out_step, dm.has_mesh != 0)));
-    done_guard.ok = true;
-    return DRC_OK;
+    return L.done();
   }
   for (int k = 0; k < steps; ++k) {
     drc_qpik_params pk = *params;
@@ -1033,8 +1020,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     HIP_TRY(static_cast<hipError_t>(launch_rollout_integrate_kernel(
         B, st, m->d_model, dt, qk, eta_k, qf, vf, q_traj ? q_traj + int64_t(k) * nv * B : nullptr)));
   }
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 static const char kSlotsReachMsg[] =
@@ -1072,8 +1058,10 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   KParams kt, kq;
   if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (B == 0) return DRC_OK;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
   double tau[2];
@@ -1088,53 +1076,37 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   // takes obstacle poses
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
   const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, false);
-  StreamCtx* cx = nullptr;
-  DoneGuard done_guard{cx, st};
-  // one step's scratch: eta [na][B], then (stepwise) pose [12][B] and dist
-  // [1+nv][B], then status [B] and iters [B]
-  const int64_t n_dbl = int64_t(na) * B + (persistent ? 0 : int64_t(12 + 1 + nv) * B);
-  {
-    std::lock_guard<std::mutex> g(m->mu);
-    if (int r = stream_ctx(m, st, &cx)) return r;
-    if (int r = grow_scratch(&cx->roll, &cx->roll_bytes, n_dbl * 8 + 2 * B * 4)) return r;
-  }
-  Carver sc{static_cast<char*>(cx->roll)};
-  double* eta = sc.take<double>(int64_t(na) * B);
-  double* s_pose = sc.take<double>(persistent ? 0 : 12 * B);
-  double* s_dist = sc.take<double>(persistent ? 0 : int64_t(1 + nv) * B);
-  int32_t* s_status = sc.take<int32_t>(B);
-  int32_t* s_iters = sc.take<int32_t>(B);
+  ReachScratch sc;  // one step's eta, stage outputs, status and iters
+  if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return reach_scratch(p, na, nv, B, persistent); }, &sc)) return r;
   const ReachArgs re{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
                      err_final, dist_final};
   if (persistent) {
     IO io = task_io(B, q0, qdot0, xt, xdt, nullptr, nullptr);
-    io.out = eta;
-    io.status = s_status;
-    io.iters = s_iters;
+    io.out = sc.eta;
+    io.status = sc.status;
+    io.iters = sc.iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(grid, st, m->d_model, kt, kq, io, re)));
-    done_guard.ok = true;
-    return DRC_OK;
+    return L.done();
   }
   if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, re)) return r;
   IO qp = task_io(B, qf, vf, xt, xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
   IO sg = qp;
-  sg.st_pose = s_pose;
-  sg.st_dist = s_dist;
-  qp.out = eta;
-  qp.status = s_status;
-  qp.iters = s_iters;
+  sg.st_pose = sc.pose;
+  sg.st_dist = sc.dist;
+  qp.out = sc.eta;
+  qp.status = sc.status;
+  qp.iters = sc.iters;
   for (int k = 0; k <= max_steps; ++k) {
     const int last = k == max_steps;
     if (int rc = launch_locked(m, params, 1, sg, stream, ob)) return rc;
     if (!last)
       if (int rc = launch_locked(m, params, 0, qp, stream, ob)) return rc;
-    HIP_TRY(static_cast<hipError_t>(launch_reach_update_kernel(B, st, m->d_model, k, last, re, xt, s_pose, s_dist, eta,
-                                                               s_status, s_iters)));
+    HIP_TRY(static_cast<hipError_t>(launch_reach_update_kernel(B, st, m->d_model, k, last, re, xt, sc.pose, sc.dist,
+                                                               sc.eta, sc.status, sc.iters)));
   }
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int max_steps, double dt,
@@ -1191,8 +1163,10 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   KParams kt, kq;
   if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (B == 0) return DRC_OK;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
   const bool slots = dm.nobst > 0;
@@ -1206,67 +1180,48 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   // against 1 786 ms; profiles/reach_path_bench.json, DESIGN.md "Reach paths")
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
   const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, true);
-  StreamCtx* cx = nullptr;
-  DoneGuard done_guard{cx, st};
-  // scratch: one step's eta [na][B], then (stepwise) pose [12][B], dist
-  // [1+nv][B] and the current targets [12][B], [6][B]; then status [B], iters
-  // [B] and (stepwise) the segment counters [B]
-  const int64_t n_dbl = int64_t(na) * B + (persistent ? 0 : int64_t(12 + 1 + nv + 12 + 6) * B);
-  {
-    std::lock_guard<std::mutex> g(m->mu);
-    if (int r = stream_ctx(m, st, &cx)) return r;
-    if (int r = grow_scratch(&cx->roll, &cx->roll_bytes, n_dbl * 8 + 3 * B * 4)) return r;
-  }
-  Carver sc{static_cast<char*>(cx->roll)};
-  double* eta = sc.take<double>(int64_t(na) * B);
-  double* s_pose = sc.take<double>(persistent ? 0 : 12 * B);
-  double* s_dist = sc.take<double>(persistent ? 0 : int64_t(1 + nv) * B);
-  double* s_xt = sc.take<double>(persistent ? 0 : 12 * B);
-  double* s_xdt = sc.take<double>(persistent ? 0 : 6 * B);
-  int32_t* s_status = sc.take<int32_t>(B);
-  int32_t* s_iters = sc.take<int32_t>(B);
-  int32_t* s_seg = sc.take<int32_t>(B);
+  ReachPathScratch sc;  // reach's, the current targets and the segment counters
+  if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return reach_path_scratch(p, na, nv, B, persistent); }, &sc))
+    return r;
   const ReachPathArgs rp{{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
                           err_final, dist_final},
-                         W, x_path, xdot_path, waypoints_reached, dist_min, steps_at, s_xt, s_xdt, s_seg};
+                         W, x_path, xdot_path, waypoints_reached, dist_min, steps_at, sc.xt, sc.xdt, sc.seg};
   if (persistent) {
     IO io = task_io(B, q0, qdot0, x_path, xdot_path, nullptr, nullptr);
-    io.out = eta;
-    io.status = s_status;
-    io.iters = s_iters;
+    io.out = sc.eta;
+    io.status = sc.status;
+    io.iters = sc.iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(static_cast<hipError_t>(slots ? launch_reach_path_obstacle_kernel(grid, st, m->d_model, kt, kq, io, rp, *ob)
                                           : launch_reach_path_kernel(grid, st, m->d_model, kt, kq, io, rp)));
-    done_guard.ok = true;
-    return DRC_OK;
+    return L.done();
   }
   // reach()'s start, at waypoint 0 with no step taken
   if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, rp.re)) return r;
-  HIP_TRY(hipMemcpyAsync(s_xt, x_path, size_t(12) * B * 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s_xdt, xdot_path, size_t(6) * B * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(sc.xt, x_path, size_t(12) * B * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(sc.xdt, xdot_path, size_t(6) * B * 8, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemsetAsync(waypoints_reached, 0, size_t(B) * 4, st));
   HIP_TRY(hipMemsetAsync(steps_used, 0, size_t(B) * 4, st));
-  HIP_TRY(hipMemsetAsync(s_seg, 0, size_t(B) * 4, st));
+  HIP_TRY(hipMemsetAsync(sc.seg, 0, size_t(B) * 4, st));
   if (steps_at) HIP_TRY(hipMemsetAsync(steps_at, 0xff, size_t(W) * B * 4, st));  // -1: never reached
   const int64_t rounds = int64_t(W) * (int64_t(max_steps) + 1);
-  IO qp = task_io(B, qf, vf, s_xt, s_xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
+  IO qp = task_io(B, qf, vf, sc.xt, sc.xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
   IO sg = qp;
-  sg.st_pose = s_pose;
-  sg.st_dist = s_dist;
-  qp.out = eta;
-  qp.status = s_status;
-  qp.iters = s_iters;
+  sg.st_pose = sc.pose;
+  sg.st_dist = sc.dist;
+  qp.out = sc.eta;
+  qp.status = sc.status;
+  qp.iters = sc.iters;
   for (int64_t r = 0; r <= rounds; ++r) {
     const int last = r == rounds;
     if (int rc = launch_locked(m, params, 1, sg, stream, ob)) return rc;
     if (!last)
       if (int rc = launch_locked(m, params, 0, qp, stream, ob)) return rc;
-    HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, s_pose, s_dist,
-                                                                    eta, s_status, s_iters)));
+    HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, sc.pose,
+                                                                    sc.dist, sc.eta, sc.status, sc.iters)));
   }
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 static const char kSlotsReachSeedsMsg[] =
@@ -1318,8 +1273,10 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   KParams kt, kq;
   if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
   if (T == 0) return DRC_OK;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
   const bool slots = dm.nobst > 0;
@@ -1329,70 +1286,44 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
   const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, true);
   const bool ob_expand = ob && ob->ld != 0;
-  StreamCtx* cx = nullptr;
-  DoneGuard done_guard{cx, st};
-  // scratch: the expanded targets [12][B], [6][B], the instances' finals
-  // [nv][B] twice, err [2][B], dist [1+nv][B], the per-target poses expanded
-  // [nobst][12][B], (persistent) one step's eta [na][B]; then result, steps,
-  // status_last, iters_total [B], (persistent) one step's status and iters [B]
-  // and the groups' words [T]
-  const int64_t n_pose = ob_expand ? int64_t(dm.nobst) * 12 * B : 0;
-  const int64_t n_dbl = int64_t(12 + 6 + 2 * nv + 2 + 1 + nv + (persistent ? na : 0)) * B + n_pose;
-  {
-    std::lock_guard<std::mutex> g(m->mu);
-    if (int r = stream_ctx(m, st, &cx)) return r;
-    if (int r = grow_scratch(&cx->seeds, &cx->seeds_bytes, n_dbl * 8 + 6 * B * 4 + T * 4)) return r;
-  }
-  Carver sc{static_cast<char*>(cx->seeds)};
-  double* s_xt = sc.take<double>(12 * B);
-  double* s_xdt = sc.take<double>(6 * B);
-  double* s_qf = sc.take<double>(int64_t(nv) * B);
-  double* s_vf = sc.take<double>(int64_t(nv) * B);
-  double* s_err = sc.take<double>(2 * B);
-  double* s_dist = sc.take<double>(int64_t(1 + nv) * B);
-  double* s_pose = sc.take<double>(n_pose);
-  double* s_eta = sc.take<double>(persistent ? int64_t(na) * B : 0);
-  int32_t* s_res = sc.take<int32_t>(B);
-  int32_t* s_steps = sc.take<int32_t>(B);
-  int32_t* s_stl = sc.take<int32_t>(B);
-  int32_t* s_its = sc.take<int32_t>(B);
-  int32_t* s_status = sc.take<int32_t>(B);
-  int32_t* s_iters = sc.take<int32_t>(B);
-  uint32_t* s_word = sc.take<uint32_t>(T);
-  HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 12, T, S, xt, T, s_xt)));
-  HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 6, T, S, xdt, T, s_xdt)));
+  // the expanded targets and poses, the instances' finals and outcomes, one step's scratch, the groups' words
+  SeedsScratch sc;
+  if (int r = L.carve(&StreamCtx::seeds,
+                      [&](void* p) { return seeds_scratch(p, na, nv, dm.nobst, T, S, persistent, ob_expand); }, &sc))
+    return r;
+  HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 12, T, S, xt, T, sc.xt)));
+  HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 6, T, S, xdt, T, sc.xdt)));
   Obst obe{nullptr, 0};
   if (ob) obe = *ob;
   if (ob_expand) {
-    HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, dm.nobst * 12, T, S, ob->pose, ob->ld, s_pose)));
-    obe = Obst{s_pose, B};
+    HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, dm.nobst * 12, T, S, ob->pose, ob->ld, sc.pose)));
+    obe = Obst{sc.pose, B};
   }
   // the diagnostics are the instances' own result / steps_used
-  const ReachSeedsArgs rs{{max_steps, dt, tau[0], tau[1], s_qf, s_vf, inst_result ? inst_result : s_res,
-                           inst_steps ? inst_steps : s_steps, status_last ? s_stl : nullptr,
-                           iters_total ? s_its : nullptr, s_err, dist_final ? s_dist : nullptr},
-                          T, S, rule, persistent && cancel ? 1 : 0, s_word};
+  const ReachSeedsArgs rs{{max_steps, dt, tau[0], tau[1], sc.qf, sc.vf, inst_result ? inst_result : sc.result,
+                           inst_steps ? inst_steps : sc.steps, status_last ? sc.status_last : nullptr,
+                           iters_total ? sc.iters_total : nullptr, sc.err, dist_final ? sc.dist : nullptr},
+                          T, S, rule, persistent && cancel ? 1 : 0, sc.word};
   const ReachArgs& re = rs.re;
   if (persistent) {
-    IO io = task_io(B, q0, qdot0, s_xt, s_xdt, nullptr, nullptr);
-    io.out = s_eta;
-    io.status = s_status;
-    io.iters = s_iters;
+    IO io = task_io(B, q0, qdot0, sc.xt, sc.xdt, nullptr, nullptr);
+    io.out = sc.eta;
+    io.status = sc.status;
+    io.iters = sc.iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
-    HIP_TRY(hipMemsetAsync(s_word, 0xff, size_t(T) * 4, st));  // kSeedsNoKey
+    HIP_TRY(hipMemsetAsync(sc.word, 0xff, size_t(T) * 4, st));  // kSeedsNoKey
     HIP_TRY(static_cast<hipError_t>(slots ? launch_reach_seeds_obstacle_kernel(grid, st, m->d_model, kt, kq, io, rs, obe)
                                           : launch_reach_seeds_kernel(grid, st, m->d_model, kt, kq, io, rs)));
   } else {
-    if (int rc = reach_locked(m, params, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, s_xt, s_xdt, re.qf, re.vf,
+    if (int rc = reach_locked(m, params, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, sc.xt, sc.xdt, re.qf, re.vf,
                               re.result, re.steps_used, re.status_last, re.iters_total, re.err_final, re.dist_final,
                               stream, ob ? &obe : nullptr))
       return rc;
   }
   const ReachSeedsOut out{seed, result, steps_used, q_sol, qdot_sol, status_last, iters_total, err_final, dist_final};
   HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_select_kernel(st, nv, rs, out)));
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 // QPID pipeline for one call: dynamics launch(es) -> task kernel (QPID stage
@@ -1421,39 +1352,31 @@ static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, 
     if (rc) return rc;
   }
   const DevModel& d = m->hm.dev;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t stride = (kt.rLen + 15) & ~int64_t(15);
-  const int na = kt.na, nv = d.nv;
-  const int64_t dyn_words = stages ? 0 : (int64_t(na) * na + na + (d.kind == 1 ? nv : 0)) * B;
-  double *rec = nullptr, *dM = nullptr, *dG = nullptr, *dGf = nullptr;
-  StreamCtx* cx = nullptr;
-  DoneGuard done_guard{cx, st};
-  {
-    std::lock_guard<std::mutex> g(m->mu);
-    if (int r = stream_ctx(m, st, &cx)) return r;
-    if (!stages)
-      if (int r = ensure_pool(cx, (stride * B + dyn_words) * 8)) return r;
-  }
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
+  const int64_t stride = record_stride(kt.rLen);
+  QpidPool pool;  // (a stage call: nothing)
+  if (int r = L.carve(&StreamCtx::pool,
+                      [&](void* p) { return qpid_pool(p, stride, kt.na, d.nv, B, stages != 0, d.kind == 1); }, &pool))
+    return r;
   if (!stages) {
-    rec = reinterpret_cast<double*>(cx->pool);
-    dM = rec + stride * B;
-    dG = dM + int64_t(na) * na * B;
-    dGf = d.kind == 1 ? dG + int64_t(na) * B : nullptr;
     // getMassMatrix / getGravity (or the *Actuated getters) the equality rows use
-    rc = launch_dynamics(m->d_model, d, d.kind == 1, B, q, qdot, dM, nullptr, dG, nullptr, nullptr, nullptr, st);
-    if (!rc && d.kind == 1) rc = launch_dynamics(m->d_model, d, false, B, q, qdot, nullptr, nullptr, dGf, nullptr, nullptr, nullptr, st);
+    rc = launch_dynamics(m->d_model, d, d.kind == 1, B, q, qdot, pool.M, nullptr, pool.g, nullptr, nullptr, nullptr, st);
+    if (!rc && d.kind == 1)
+      rc = launch_dynamics(m->d_model, d, false, B, q, qdot, nullptr, nullptr, pool.g_joint, nullptr, nullptr, nullptr, st);
     if (rc) return set_err(DRC_ERR_HIP, std::string("dynamics launch: ") + hipGetErrorString(hipGetLastError()));
   }
   const int64_t grid = B < 8192 ? B : 8192;
   KParams kt_c = kt, kq_c = kq;
   kt_c.xcd_map = kq_c.xcd_map = xcd_map_for(B);
   IO io = call;
-  io.rec = rec;
+  io.rec = pool.rec;
   io.rec_stride = stride;
-  io.dM = dM;
-  io.dG = dG;
-  io.dGf = dGf;
+  io.dM = pool.M;
+  io.dG = pool.g;
+  io.dGf = pool.g_joint;
   int* qc = cx->d_queue + StreamCtx::kQueueSlotQpid * StreamCtx::kSlotInts;
   // the task and the QP queue
   HIP_TRY(hipMemsetAsync(qc, 0, (StreamCtx::kSlotQp + StreamCtx::kXcdClasses) * sizeof(int), st));
@@ -1466,8 +1389,7 @@ static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, 
     const size_t lds = static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
     HIP_TRY(static_cast<hipError_t>(launch_qpid_kernel(static_cast<unsigned>(grid), lds, st, m->d_model, kq_c, io)));
   }
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 // Closed-form controllers: [dynamics (OSF: M^-1, g)] -> task_kernel<2>.
@@ -1490,14 +1412,10 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
     pp.mode = DRC_MODE_QPIK;
     int rc = make_kparams(m, &pp, 1, &kt, 2, 3);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    StreamCtx* cx = nullptr;
-    DoneGuard done_guard{cx, st};
-    {
-      std::lock_guard<std::mutex> g(m->mu);
-      if (int r = stream_ctx(m, st, &cx)) return r;
-    }
+    Launch L(m, stream);
+    if (int r = L.begin()) return r;
+    hipStream_t st = L.st;
+    StreamCtx* const cx = L.cx;
     const int64_t grid = B < 8192 ? B : 8192;
     kt.xcd_map = xcd_map_for(B);
     // qdot may be NULL when xdot is not requested.  The stage still loads a
@@ -1512,8 +1430,7 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
     HIP_TRY(static_cast<hipError_t>(launch_task_kernel(2, static_cast<unsigned>(grid),
                                                        static_cast<size_t>(kt.lds_doubles) * sizeof(double), st,
                                                        m->d_model, kt, io)));
-    done_guard.ok = true;
-    return DRC_OK;
+    return L.done();
   }
   if (m->hm.dev.kind != 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "CLIK / OSF are Manipulator::RobotController entries");
   if (int rc = check_batch(B)) return rc;
@@ -1531,43 +1448,29 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
   int rc = make_kparams(m, &pp, 1, &kt, 2, cf);
   if (rc) return rc;
   const DevModel& d = m->hm.dev;
-  HIP_TRY(hipSetDevice(m->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  double *dMi = nullptr, *dG = nullptr;
-  StreamCtx* cx = nullptr;
-  DoneGuard done_guard{cx, st};
-  {
-    std::lock_guard<std::mutex> g(m->mu);
-    if (int r = stream_ctx(m, st, &cx)) return r;
-    if (cf == 2) {
-      if (int r = ensure_pool(cx, (int64_t(d.nv) * d.nv + d.nv) * B * 8)) return r;
-      if (cx->dyn_list_cap < B + 1) {
-        if (cx->dyn_list) HIP_TRY(hipFree(cx->dyn_list));
-        cx->dyn_list = nullptr;
-        cx->dyn_list_cap = 0;
-        HIP_TRY(hipMalloc(&cx->dyn_list, (B + 1) * sizeof(int)));
-        cx->dyn_list_cap = B + 1;
-      }
-    }
-  }
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
+  OsfPool pool{};
   if (cf == 2) {  // getMassMatrixInv (PinvCOD(M)) and getGravity (robot_data.cpp:111-118)
-    dMi = reinterpret_cast<double*>(cx->pool);
-    dG = dMi + int64_t(d.nv) * d.nv * B;
-    rc = launch_dynamics(m->d_model, d, false, B, q, qdot, nullptr, dMi, dG, nullptr, nullptr, cx->dyn_list, st);
+    DynList cod;
+    if (int r = L.carve(&StreamCtx::pool, [&](void* p) { return osf_pool(p, d.nv, B); }, &pool)) return r;
+    if (int r = L.carve(&StreamCtx::dyn_list, [&](void* p) { return dyn_list(p, B); }, &cod)) return r;
+    rc = launch_dynamics(m->d_model, d, false, B, q, qdot, nullptr, pool.Minv, pool.g, nullptr, nullptr, cod.list, st);
     if (rc) return set_err(DRC_ERR_HIP, std::string("dynamics launch: ") + hipGetErrorString(hipGetLastError()));
   }
   const int64_t grid = B < 8192 ? B : 8192;
   kt.xcd_map = xcd_map_for(B);
   IO io = call;
-  io.dM = dMi;
-  io.dG = dG;
+  io.dM = pool.Minv;
+  io.dG = pool.g;
   io.queue = cx->d_queue + StreamCtx::kQueueSlotCf * StreamCtx::kSlotInts + StreamCtx::kSlotTask;
   HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kXcdClasses * sizeof(int), st));
   HIP_TRY(static_cast<hipError_t>(launch_task_kernel(2, static_cast<unsigned>(grid),
                                                      static_cast<size_t>(kt.lds_doubles) * sizeof(double), st,
                                                      m->d_model, kt, io)));
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 }  // namespace drc_amd
@@ -2733,27 +2636,17 @@ int drc_dynamics_batch(drc_model* m, int actuated, int64_t B, const double* q, c
   if (B > 0x7ffffff0) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");
   HIP_TRY(hipSetDevice(m->device));
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  int* list = nullptr;
-  drc_amd::StreamCtx* cx = nullptr;
-  drc_amd::DoneGuard done_guard{cx, reinterpret_cast<hipStream_t>(stream)};
+  drc_amd::Launch L(m, stream);
+  drc_amd::DynList cod{};  // (a context, and the COD list in it, only for M_inv)
   if (M_inv) {
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (int r = drc_amd::stream_ctx(m, reinterpret_cast<hipStream_t>(stream), &cx)) return r;
-    if (cx->dyn_list_cap < B + 1) {
-      if (cx->dyn_list) HIP_TRY(hipFree(cx->dyn_list));
-      cx->dyn_list = nullptr;
-      cx->dyn_list_cap = 0;
-      HIP_TRY(hipMalloc(&cx->dyn_list, (B + 1) * sizeof(int)));
-      cx->dyn_list_cap = B + 1;
-    }
-    list = cx->dyn_list;
+    if (int r = L.context()) return r;
+    if (int r = L.carve(&drc_amd::StreamCtx::dyn_list, [&](void* p) { return drc_amd::dyn_list(p, B); }, &cod)) return r;
   }
   const int rc = drc_amd::launch_dynamics(m->d_model, m->hm.dev, actuated != 0, B, q, qdot, M, M_inv, g, nle, c,
-                                          list, reinterpret_cast<hipStream_t>(stream));
+                                          cod.list, L.st);
   if (rc == 1) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");
   if (rc) return drc_amd::set_err(DRC_ERR_HIP, std::string("dynamics launch: ") + hipGetErrorString(hipGetLastError()));
-  done_guard.ok = true;
-  return DRC_OK;
+  return L.done();
 }
 
 int drc_dynamics_host(drc_model* m, int actuated, int64_t B, const double* q, const double* qdot, double* M,

@@ -1,0 +1,130 @@
+// Host test of csrc/scratch_layout.hpp (tests/test_scratch_layout_host.py):
+// every layout over a grid of dimensions and flags.  Per case the layout is
+// measured without a base, a heap block of exactly `bytes` is allocated, the
+// layout is carved on it, every region is filled with its own tag through the
+// struct's typed pointer and all of them are read back.  One line per case:
+//   LAYOUT k=v ... | bytes | name:elem:offset:count:carved ...
+// (offset: measured; carved: the typed pointer minus the block, -1 for none).
+// Exit code 1 with a message when measuring and carving disagree, a struct
+// member is not the region of its name, or a tag does not read back.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+
+#include "../dyros_robot_controller_amd/csrc/scratch_layout.hpp"
+
+using namespace drc_amd;
+
+// The members of each layout struct, in the order they are taken
+template <class V> void visit(const QpikPool& L, V& v) { v("rec", L.rec), v("hard", L.hard), v("hard_flag", L.hard_flag), v("order", L.order), v("hot", L.hot), v("hot_flag", L.hot_flag); }
+template <class V> void visit(const QpidPool& L, V& v) { v("rec", L.rec), v("M", L.M), v("g", L.g), v("g_joint", L.g_joint); }
+template <class V> void visit(const OsfPool& L, V& v) { v("Minv", L.Minv), v("g", L.g); }
+template <class V> void visit(const DynList& L, V& v) { v("list", L.list); }
+template <class V> void visit(const RolloutScratch& L, V& v) { v("eta", L.eta); }
+template <class V> void visit(const ReachScratch& L, V& v) { v("eta", L.eta), v("pose", L.pose), v("dist", L.dist), v("status", L.status), v("iters", L.iters); }
+template <class V> void visit(const ReachPathScratch& L, V& v) { v("eta", L.eta), v("pose", L.pose), v("dist", L.dist), v("xt", L.xt), v("xdt", L.xdt), v("status", L.status), v("iters", L.iters), v("seg", L.seg); }
+template <class V> void visit(const SeedsScratch& L, V& v) {
+  v("xt", L.xt), v("xdt", L.xdt), v("qf", L.qf), v("vf", L.vf), v("err", L.err), v("dist", L.dist), v("pose", L.pose), v("eta", L.eta);
+  v("result", L.result), v("steps", L.steps), v("status_last", L.status_last), v("iters_total", L.iters_total);
+  v("status", L.status), v("iters", L.iters), v("word", L.word);
+}
+
+[[noreturn]] static void fail(const std::string& what, const char* why, const char* region) {
+  std::fprintf(stderr, "%s: %s (%s)\n", what.c_str(), why, region);
+  std::exit(1);
+}
+
+struct Fill {
+  const std::string& what;
+  const RegionLog& log;
+  bool write;
+  int i = 0;
+  template <class T>
+  void operator()(const char* name, T* p) {
+    if (i >= log.count) fail(what, "more members than regions", name);
+    const RegionLog::Region& r = log.r[i];
+    if (std::strcmp(r.name, name) != 0 || r.elem != int(sizeof(T)) || r.p != static_cast<void*>(p))
+      fail(what, "the struct member is not the region taken under its name", name);
+    const T tag = static_cast<T>(i + 1);
+    for (int64_t k = 0; k < r.n; ++k) {
+      if (write)
+        p[k] = tag;
+      else if (p[k] != tag)
+        fail(what, "a region's tag did not read back", name);
+    }
+    ++i;
+  }
+};
+
+template <class F>
+static void run(const std::string& what, F layout) {
+  RegionLog measured, carved;
+  const int64_t bytes = layout(nullptr, &measured).bytes;
+  std::unique_ptr<char[]> block(new char[bytes]);
+  const auto L = layout(block.get(), &carved);
+  if (L.bytes != bytes || carved.count != measured.count) fail(what, "measuring and carving disagree", "bytes");
+  Fill w{what, carved, true}, r{what, carved, false};
+  visit(L, w);
+  visit(L, r);
+  if (w.i != carved.count) fail(what, "fewer members than regions", "");
+  std::printf("%s | %lld |", what.c_str(), static_cast<long long>(bytes));
+  for (int i = 0; i < measured.count; ++i) {
+    const RegionLog::Region &a = measured.r[i], &b = carved.r[i];
+    if (a.off != b.off || a.n != b.n || a.p) fail(what, "measuring and carving disagree", a.name);
+    std::printf(" %s:%d:%lld:%lld:%lld", a.name, a.elem, static_cast<long long>(a.off), static_cast<long long>(a.n),
+                b.p ? static_cast<long long>(static_cast<char*>(b.p) - block.get()) : -1LL);
+  }
+  std::printf("\n");
+}
+
+static std::string fmt(const char* f, long long a = 0, long long b = 0, long long c = 0, long long d = 0, long long e = 0,
+                       long long g = 0, long long h = 0) {
+  char buf[256];
+  std::snprintf(buf, sizeof buf, f, a, b, c, d, e, g, h);
+  return buf;
+}
+
+int main() {
+  const int NV[] = {1, 6, 7, 10, 16}, RLEN[] = {1, 15, 16, 17, 300}, NOBST[] = {0, 1, 4};
+  const int64_t BATCH[] = {1, 2, 63, 64, 65, 2049, 65536}, TARGETS[] = {1, 3, 64};
+  const int SEEDS[] = {1, 2, 5};
+  for (int rLen : RLEN)
+    for (int64_t B : BATCH)
+      for (int stages = 0; stages < 2; ++stages)
+        for (int ao = 0; ao < 2; ++ao)
+          run(fmt("qpik rLen=%lld B=%lld stages=%lld auto_order=%lld", rLen, B, stages, ao),
+              [&](void* p, RegionLog* l) { return qpik_pool(p, record_stride(rLen), B, stages, ao, l); });
+  for (int64_t B : BATCH) run(fmt("dyn_list B=%lld", B), [&](void* p, RegionLog* l) { return dyn_list(p, B, l); });
+  for (int nv : NV) {
+    for (int64_t B : BATCH) run(fmt("osf nv=%lld B=%lld", nv, B), [&](void* p, RegionLog* l) { return osf_pool(p, nv, B, l); });
+    for (int na : {nv, nv - 3}) {
+      if (na < 1) continue;
+      for (int64_t B : BATCH) {
+        for (int rLen : RLEN)
+          for (int stages = 0; stages < 2; ++stages)
+            for (int wb = 0; wb < 2; ++wb)
+              run(fmt("qpid nv=%lld na=%lld rLen=%lld B=%lld stages=%lld whole_body=%lld", nv, na, rLen, B, stages, wb),
+                  [&](void* p, RegionLog* l) { return qpid_pool(p, record_stride(rLen), na, nv, B, stages, wb, l); });
+        for (int flag = 0; flag < 2; ++flag) {
+          run(fmt("rollout nv=%lld na=%lld B=%lld qdot_traj=%lld", nv, na, B, flag),
+              [&](void* p, RegionLog* l) { return rollout_scratch(p, na, B, flag, l); });
+          run(fmt("reach nv=%lld na=%lld B=%lld persistent=%lld", nv, na, B, flag),
+              [&](void* p, RegionLog* l) { return reach_scratch(p, na, nv, B, flag, l); });
+          run(fmt("reach_path nv=%lld na=%lld B=%lld persistent=%lld", nv, na, B, flag),
+              [&](void* p, RegionLog* l) { return reach_path_scratch(p, na, nv, B, flag, l); });
+        }
+      }
+      for (int64_t T : TARGETS)
+        for (int S : SEEDS)
+          for (int nobst : NOBST)
+            for (int pe = 0; pe < 2; ++pe)
+              for (int ox = 0; ox < 2; ++ox)
+                run(fmt("seeds nv=%lld na=%lld nobst=%lld T=%lld S=%lld persistent=%lld ob_expand=%lld", nv, na, nobst, T, S,
+                        pe, ox),
+                    [&](void* p, RegionLog* l) { return seeds_scratch(p, na, nv, nobst, T, S, pe, ox, l); });
+    }
+  }
+  return 0;
+}
