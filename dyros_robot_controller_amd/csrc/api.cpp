@@ -449,17 +449,22 @@ static int mobile_ik_jacobian(const drc_kinematic_param& p, const double* wheel_
 static const char kMeshStageMsg[] =
     "the model has collision meshes: the lane-per-instance debug stage handles sphere, cylinder and box geometry only";
 
-// Obstacle poses of a call (drc_qpik_*obstacles_batch): [n][12][ld] in
-// x_target's layout, ld = 0 one set shared by the batch (kernel_common.hpp)
-using Obst = ObstIn;
-// ... and their twists (drc_qpik_*moving_obstacles_batch): [n][6][ld] with the
-// poses' ld, and the stage output dist_rate.  A call without twists passes none
-using Rate = RateIn;
+// What a call carries for the task stage's build (launch.hpp StageIn), as its
+// entry states it: nothing (the plain entries: the Plain build), or the obstacle
+// poses (drc_qpik_*obstacles_batch: [n][12][ld] in x_target's layout, ld = 0 one
+// set shared by the batch), or those and their twists
+// (drc_qpik_*moving_obstacles_batch: [n][6][ld] with the poses' ld, and the
+// stage output dist_rate; NULL twists: the obstacle entry itself).
+// check_slots() then holds it against the model
+static StageIn stage_in(const double* obstacle_pose, int64_t obstacle_ld, const double* obstacle_twist = nullptr,
+                        double* dist_rate = nullptr) {
+  if (!obstacle_twist) return {StageBuild::Obst, {obstacle_pose, obstacle_ld}, {}};
+  return {StageBuild::Rate, {obstacle_pose, obstacle_ld}, {obstacle_twist, obstacle_ld, dist_rate}};
+}
 // The twists against the call: the rate reaches the QP as d + (dd/dt) / alpha_cbf
 // (task_stage.hpp RATE), so a call with twists needs alpha_cbf > 0
-static int check_rate(const Rate* rt, const Obst* ob, const drc_qpik_params* params) {
-  if (rt && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_twist without obstacle_pose");
-  if (rt && !(params->alpha_cbf > 0))
+static int check_rate(const StageIn& si, const drc_qpik_params* params) {
+  if (si.build == StageBuild::Rate && !(params->alpha_cbf > 0))
     return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_twist needs alpha_cbf > 0: the rate enters the QP as d + rate / alpha_cbf");
   return DRC_OK;
 }
@@ -469,6 +474,29 @@ static const char kSlotsPlainMsg[] =
 static const char kSlotsUnsupportedMsg[] =
     "the model has obstacle slots: only the drc_qpik_*obstacles_batch entries take their poses "
     "(drc_model_set_obstacles with n = 0 removes the slots)";
+// The call's build against the model: slots need poses (slots_msg: the entry's
+// own "pass their poses through ..."), poses need slots (plain_entry: the entry
+// that runs a model without them, where the text names one).  Then the build
+// is the model's and the call's together (call_plan.hpp stage_build): a plain
+// call on a hull model runs the Mesh build
+static int check_slots(const drc_model_impl* m, StageIn* si, const char* slots_msg, const char* plain_entry = nullptr) {
+  const DevModel& dm = m->hm.dev;
+  const bool slots = dm.nobst > 0, poses = takes_poses(si->build);
+  if (slots && !poses) return set_err(DRC_ERR_INVALID_ARGUMENT, slots_msg);
+  if (!slots && poses)
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   std::string("the model has no obstacle slots (drc_model_set_obstacles declares them)") +
+                       (plain_entry ? std::string(": ") + plain_entry + " runs it" : std::string()));
+  si->build = stage_build(dm.has_mesh != 0, slots, si->build == StageBuild::Rate);
+  return DRC_OK;
+}
+// ... and the poses themselves: [nobst][12][ld] with ld = 0 or at least `cols` columns
+static int check_obstacle_pose(const StageIn& si, int64_t cols, const char* cols_name) {
+  if (takes_poses(si.build) && cols > 0 && (!si.ob.pose || (si.ob.ld != 0 && si.ob.ld < cols)))
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   std::string("obstacle_pose is required, obstacle_ld is 0 (shared) or at least ") + cols_name);
+  return DRC_OK;
+}
 
 static int upload(drc_model_impl* m) {
   HIP_TRY(hipSetDevice(m->device));
@@ -588,8 +616,8 @@ static const PlanKnobs& plan_knobs() {
   return k;
 }
 // ... and its view of a call of B instances on the model (kq: the QP's
-// parameters, none for a stage call)
-static PlanIn plan_in(const drc_model_impl* m, int64_t B, int stages, const KParams* kq) {
+// parameters, none for a stage call; si: what the call carries)
+static PlanIn plan_in(const drc_model_impl* m, int64_t B, int stages, const KParams* kq, const StageIn& si) {
   const DevModel& dm = m->hm.dev;
   PlanIn in;
   in.B = B;
@@ -603,6 +631,7 @@ static PlanIn plan_in(const drc_model_impl* m, int64_t B, int stages, const KPar
   in.ncand_slots = dm.ncand_slots;
   in.has_mesh = dm.has_mesh != 0;
   in.slots = dm.nobst > 0;
+  in.twists = si.build == StageBuild::Rate;
   in.qp_compiled = kq && qp_compiled(kq->nx, kq->ng, kq->np);
   in.qp_group = 64;
   in.max_cand_slots = kMaxCandSlots;
@@ -616,16 +645,12 @@ static PlanIn plan_in(const drc_model_impl* m, int64_t B, int stages, const KPar
 // (the caller holds m->launch_mu: launch() for one call, the stepwise rollout
 // for its whole sequence of steps)
 static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int stages, const IO& call, void* stream,
-                         const Obst* ob = nullptr, const Rate* rt = nullptr) {
+                         StageIn si = {}) {
   const int64_t B = call.B;
   if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
-  const bool slots = m->hm.dev.nobst > 0;
-  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, kSlotsPlainMsg);
-  if (!slots && ob)
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "the model has no obstacle slots (drc_model_set_obstacles declares them)");
-  if (ob && B > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < B)))
-    return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacle_pose is required, obstacle_ld is 0 (shared) or at least the batch");
-  if (int r = check_rate(rt, ob, params)) return r;
+  if (int r = check_slots(m, &si, kSlotsPlainMsg)) return r;
+  if (int r = check_obstacle_pose(si, B, "the batch")) return r;
+  if (int r = check_rate(si, params)) return r;
   if (B == 0) return DRC_OK;
   if (B > 0x7ffffff0) return set_err(DRC_ERR_INVALID_ARGUMENT, "batch too large");  // 32-bit work-queue counters
   if (int r = check_mode_inputs(call, params->mode, "q, qdot and xdot_target are required", "QPIK")) return r;
@@ -646,7 +671,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
   // API writes [field][B]
   const int64_t stride = record_stride(kt.rLen);
   const DevModel& dm = m->hm.dev;
-  const PlanIn pin = plan_in(m, B, stages, stages ? nullptr : &kq);
+  const PlanIn pin = plan_in(m, B, stages, stages ? nullptr : &kq, si);
   const CallPlan plan = plan_call(pin);
   const bool lane = plan.lane, fuse = plan.fuse, auto_order = plan.auto_order;
   const int ls = m->lane_stage, S = plan.S;
@@ -715,7 +740,8 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     if (own) HIP_TRY(hipStreamWaitEvent(cs, m->ln.fork, 0));
     KParams kt_c = kt, kq_c = kq;
     kt_c.xcd_map = kq_c.xcd_map = sb.xcd_map;
-    const int64_t gq = sb.grid_qp, gt = sb.grid_task;
+    const int64_t gq = sb.grid_qp;
+    const unsigned gt = static_cast<unsigned>(sb.grid_task);
     // this sub-batch's record: the caller's arrays, its range, its scratch
     IO io = call;
     io.B = Bc;
@@ -724,8 +750,6 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     io.rec_stride = stride;
     if (stages) io.stamps = nullptr;
     io.order = plan.use_caller_order ? m->d_order : nullptr;
-    const ObstIn obin = ob ? *ob : ObstIn();
-    const RateIn rtin = rt ? *rt : RateIn();  // (twists: the rate builds; without, the obstacle builds as ever)
     int* qc = cx->d_queue + c * StreamCtx::kSlotInts;  // c < 16 (drc_set_concurrency)
     // the whole slot (128 B, one aligned fill; 17 ints took two fill kernels)
     HIP_TRY(hipMemsetAsync(qc, 0, StreamCtx::kSlotInts * sizeof(int), cs));
@@ -748,18 +772,6 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
     }
     const size_t lds_t = static_cast<size_t>(kt_c.lds_doubles) * sizeof(double);
     const size_t lds_q = stages ? 0 : static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
-    auto launch_task = [&](hipStream_t sm) -> int {
-      if (slots && rt)
-        HIP_TRY(static_cast<hipError_t>(
-            launch_task_rate_kernel(static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io, obin, rtin)));
-      else if (slots)
-        HIP_TRY(static_cast<hipError_t>(
-            launch_task_obstacle_kernel(static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c, io, obin)));
-      else
-        HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, static_cast<unsigned>(gt), lds_t, sm, m->d_model, kt_c,
-                                                           io, dm.has_mesh != 0)));
-      return DRC_OK;
-    };
     auto launch_qp = [&]() -> int {
       io.queue = qc + StreamCtx::kSlotQp;
       // compile-time QP shapes of the bundled robots; anything else runs the
@@ -783,14 +795,10 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
       const size_t lds_f = static_cast<size_t>(fused_lds_doubles(kt_c, kq_c)) * sizeof(double);
       io.queue = qc + StreamCtx::kSlotTask;
       HIP_TRY(static_cast<hipError_t>(
-          slots && rt
-              ? launch_fused_rate_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin, rtin)
-          : slots ? launch_fused_obstacle_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, obin)
-                  : launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io,
-                                        dm.has_mesh != 0)));
+          launch_fused_kernel(static_cast<unsigned>(gf), lds_f, cs, m->d_model, kt_c, kq_c, io, si)));
       if (timed) HIP_TRY(hipEventRecord(e1, cs));
     } else if (!lane) {  // wave-per-instance task kernel on every instance, then the QP
-      if (int r = launch_task(cs)) return r;
+      HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, gt, lds_t, cs, m->d_model, kt_c, io, si)));
       if (timed) HIP_TRY(hipEventRecord(e1, cs));
       if (!stages)
         if (int r = launch_qp()) return r;
@@ -805,7 +813,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
       if (timed) HIP_TRY(hipEventRecord(e1, cs));
       io.hard_mode = 1;
       if (stages || ls != 1) {  // hard task kernel, then one QP pass over every instance
-        if (int r = launch_task(cs)) return r;
+        HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, gt, lds_t, cs, m->d_model, kt_c, io, si)));
         io.hard_mode = 0;
         if (!stages)
           if (int r = launch_qp()) return r;
@@ -815,7 +823,7 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
         hipStream_t ss = m->ln.sides[c];
         HIP_TRY(hipEventRecord(m->ln.side_fork[c], cs));
         HIP_TRY(hipStreamWaitEvent(ss, m->ln.side_fork[c], 0));
-        if (int r = launch_task(ss)) return r;
+        HIP_TRY(static_cast<hipError_t>(launch_task_kernel(0, gt, lds_t, ss, m->d_model, kt_c, io, si)));
         HIP_TRY(hipEventRecord(m->ln.side_join[c], ss));
         io.hard_mode = 2;
         if (int r = launch_qp()) return r;
@@ -839,11 +847,11 @@ static int launch_locked(drc_model_impl* m, const drc_qpik_params* params, int s
 }
 
 static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int stages, const IO& call, void* stream,
-                  const Obst* ob = nullptr, const Rate* rt = nullptr) {
+                  const StageIn& si = {}) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  return launch_locked(m, params, stages, call, stream, ob, rt);
+  return launch_locked(m, params, stages, call, stream, si);
 }
 
 // --------------------------------------------------------------------------
@@ -852,26 +860,6 @@ static int launch(const drc_model_impl* cm, const drc_qpik_params* params, int s
 // --------------------------------------------------------------------------
 static bool finite_positive(double x) { return std::isfinite(x) && x > 0; }
 
-// The obstacle arguments against the model: slots need poses (slots_msg: the
-// entry's own "pass their poses through ..."), poses need slots (plain_entry:
-// the entry that runs a model without them, where the text names one)
-static int check_slots(const drc_model_impl* m, const Obst* ob, const char* slots_msg,
-                       const char* plain_entry = nullptr) {
-  const bool slots = m->hm.dev.nobst > 0;
-  if (slots && !ob) return set_err(DRC_ERR_INVALID_ARGUMENT, slots_msg);
-  if (!slots && ob)
-    return set_err(DRC_ERR_INVALID_ARGUMENT,
-                   std::string("the model has no obstacle slots (drc_model_set_obstacles declares them)") +
-                       (plain_entry ? std::string(": ") + plain_entry + " runs it" : std::string()));
-  return DRC_OK;
-}
-// ... and the poses themselves: [nobst][12][ld] with ld = 0 or at least `cols` columns
-static int check_obstacle_pose(const Obst* ob, int64_t cols, const char* cols_name) {
-  if (ob && cols > 0 && (!ob->pose || (ob->ld != 0 && ob->ld < cols)))
-    return set_err(DRC_ERR_INVALID_ARGUMENT,
-                   std::string("obstacle_pose is required, obstacle_ld is 0 (shared) or at least ") + cols_name);
-  return DRC_OK;
-}
 static int check_dt(double dt) {
   if (!finite_positive(dt)) return set_err(DRC_ERR_INVALID_ARGUMENT, "dt must be finite and positive");
   return DRC_OK;
@@ -930,15 +918,15 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
                    const double* q0, const double* qdot0, const double* xt, const double* xdt, const double* xi,
                    const double* xdi, int per_step, double* qf, double* vf, double* qdot_traj, int32_t* status_traj,
                    int32_t* iters_traj, double* q_traj, double* pose_traj, double* dist_traj, void* stream,
-                   const Obst* ob = nullptr, int ob_per_step = 0, const Rate* rt = nullptr) {
+                   StageIn si = {}, int ob_per_step = 0) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  if (int rc = check_slots(m, ob, kSlotsPlainMsg)) return rc;
+  if (int rc = check_slots(m, &si, kSlotsPlainMsg)) return rc;
   if (ob_per_step != 0 && ob_per_step != 1)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "obstacles_per_step must be 0 or 1");
-  if (int rc = check_obstacle_pose(ob, B, "the batch")) return rc;
-  if (int rc = check_rate(rt, ob, params)) return rc;
+  if (int rc = check_obstacle_pose(si, B, "the batch")) return rc;
+  if (int rc = check_rate(si, params)) return rc;
   if (steps < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "steps must be at least 1");
   if (int rc = check_dt(dt)) return rc;
   if (per_step != 0 && per_step != 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "targets_per_step must be 0 or 1");
@@ -969,7 +957,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   // overrides (read per call, so that one process can measure both paths)
   const int64_t rollout_max = env_int("DRC_ROLLOUT_MAX", dm.kind == 0 ? 4096 : 65536, 0);
   // (models with obstacle slots: the stepwise path; no persistent build takes poses)
-  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), rollout_max, true, false);
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq, si), rollout_max, StageFamily::Rollout);
   RolloutScratch sc;
   if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return rollout_scratch(p, na, B, qdot_traj != nullptr); }, &sc))
     return r;
@@ -983,7 +971,7 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_kernel(grid, st, m->d_model, kt, kq, io, steps, per_step, dt, qf, vf,
-                                                          q_traj, pose_traj, dist_traj, out_step, dm.has_mesh != 0)));
+                                                          q_traj, pose_traj, dist_traj, out_step, si)));
     return L.done();
   }
   for (int k = 0; k < steps; ++k) {
@@ -993,14 +981,8 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
     const double* xt_k = per_step && xt ? xt + int64_t(k) * 12 * B : xt;
     const double* xdt_k = per_step ? xdt + int64_t(k) * 6 * B : xdt;
     double* eta_k = eta + k * out_step;
-    Obst ob_k{nullptr, 0};
-    if (ob)  // this step's pose set: [n][12][ld], or the shared [n][12]
-      ob_k = Obst{ob->pose + (ob_per_step ? int64_t(k) * dm.nobst * 12 * (ob->ld ? ob->ld : 1) : 0), ob->ld};
-    const Obst* obp = ob ? &ob_k : nullptr;
-    Rate rt_k;
-    if (rt)  // this step's twists, stepping with the poses
-      rt_k = Rate{rt->twist + (ob_per_step ? int64_t(k) * dm.nobst * 6 * (rt->ld ? rt->ld : 1) : 0), rt->ld, nullptr};
-    const Rate* rtp = rt ? &rt_k : nullptr;
+    // this step's pose set and twists, or the shared ones
+    const StageIn si_k = ob_per_step ? si.at_step(k, dm.nobst) : si;
     IO step = in;
     step.q = qk;
     step.qdot = vk;
@@ -1011,12 +993,12 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
       IO sg = step;
       sg.st_pose = pose_traj ? pose_traj + int64_t(k) * 12 * B : nullptr;
       sg.st_dist = dist_traj ? dist_traj + int64_t(k) * (1 + nv) * B : nullptr;
-      if (int rc = launch_locked(m, &pk, 1, sg, stream, obp)) return rc;
+      if (int rc = launch_locked(m, &pk, 1, sg, stream, si_k.without_twists())) return rc;
     }
     step.out = eta_k;
     step.status = status_traj + int64_t(k) * B;
     step.iters = iters_traj ? iters_traj + int64_t(k) * B : nullptr;
-    if (int rc = launch_locked(m, &pk, 0, step, stream, obp, rtp)) return rc;
+    if (int rc = launch_locked(m, &pk, 0, step, stream, si_k)) return rc;
     HIP_TRY(static_cast<hipError_t>(launch_rollout_integrate_kernel(
         B, st, m->d_model, dt, qk, eta_k, qf, vf, q_traj ? q_traj + int64_t(k) * nv * B : nullptr)));
   }
@@ -1043,9 +1025,9 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
                         double pos_tol, double rot_tol, const double* q0, const double* qdot0, const double* xt,
                         const double* xdt, double* qf, double* vf, int32_t* result, int32_t* steps_used,
                         int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final,
-                        void* stream, const Obst* ob) {
-  if (int rc = check_slots(m, ob, kSlotsReachMsg)) return rc;
-  if (int rc = check_obstacle_pose(ob, B, "the batch")) return rc;
+                        void* stream, StageIn si) {
+  if (int rc = check_slots(m, &si, kSlotsReachMsg)) return rc;
+  if (int rc = check_obstacle_pose(si, B, "the batch")) return rc;
   if (params->mode != DRC_MODE_QPIK_STEP)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_batch runs DRC_MODE_QPIK_STEP only");
   if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
@@ -1075,7 +1057,7 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   // measure both paths).  No persistent build has the hull narrow phase or
   // takes obstacle poses
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, false);
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq, si), reach_max, StageFamily::Reach);
   ReachScratch sc;  // one step's eta, stage outputs, status and iters
   if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return reach_scratch(p, na, nv, B, persistent); }, &sc)) return r;
   const ReachArgs re{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
@@ -1087,7 +1069,7 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
     io.iters = sc.iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
-    HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(grid, st, m->d_model, kt, kq, io, re)));
+    HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(grid, st, m->d_model, kt, kq, io, re, si)));
     return L.done();
   }
   if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, re)) return r;
@@ -1100,9 +1082,9 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   qp.iters = sc.iters;
   for (int k = 0; k <= max_steps; ++k) {
     const int last = k == max_steps;
-    if (int rc = launch_locked(m, params, 1, sg, stream, ob)) return rc;
+    if (int rc = launch_locked(m, params, 1, sg, stream, si)) return rc;
     if (!last)
-      if (int rc = launch_locked(m, params, 0, qp, stream, ob)) return rc;
+      if (int rc = launch_locked(m, params, 0, qp, stream, si)) return rc;
     HIP_TRY(static_cast<hipError_t>(launch_reach_update_kernel(B, st, m->d_model, k, last, re, xt, sc.pose, sc.dist,
                                                                sc.eta, sc.status, sc.iters)));
   }
@@ -1113,12 +1095,12 @@ static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_
                  double pos_tol, double rot_tol, const double* q0, const double* qdot0, const double* xt,
                  const double* xdt, double* qf, double* vf, int32_t* result, int32_t* steps_used,
                  int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final, void* stream,
-                 const Obst* ob = nullptr) {
+                 const StageIn& si = {}) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
   return reach_locked(m, params, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt, qf, vf, result, steps_used,
-                      status_last, iters_total, err_final, dist_final, stream, ob);
+                      status_last, iters_total, err_final, dist_final, stream, si);
 }
 
 static const char kSlotsReachPathMsg[] =
@@ -1141,12 +1123,12 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
                       const double* x_path, const double* xdot_path, double* qf, double* vf, int32_t* result,
                       int32_t* waypoints_reached, int32_t* steps_used, int32_t* status_last, int32_t* iters_total,
                       double* err_final, double* dist_final, double* dist_min, int32_t* steps_at, void* stream,
-                      const Obst* ob = nullptr) {
+                      StageIn si = {}) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  if (int rc = check_slots(m, ob, kSlotsReachPathMsg, "drc_qpik_reach_path_batch")) return rc;
-  if (int rc = check_obstacle_pose(ob, B, "the batch")) return rc;
+  if (int rc = check_slots(m, &si, kSlotsReachPathMsg, "drc_qpik_reach_path_batch")) return rc;
+  if (int rc = check_obstacle_pose(si, B, "the batch")) return rc;
   if (params->mode != DRC_MODE_QPIK_STEP)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_path_batch runs DRC_MODE_QPIK_STEP only");
   if (W < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints must be at least 1");
@@ -1169,7 +1151,6 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   StreamCtx* const cx = L.cx;
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
-  const bool slots = dm.nobst > 0;
   double tau[2];
   reach_thresholds(pos_tol, rot_tol, tau);
   // reach()'s rule and its DRC_REACH_MAX (read per call), with the slots let in:
@@ -1179,7 +1160,7 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   // Husky-FR3 129 against 570 ms) and with four slots and one waypoint (FR3 565
   // against 1 786 ms; profiles/reach_path_bench.json, DESIGN.md "Reach paths")
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, true);
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq, si), reach_max, StageFamily::ReachPath);
   ReachPathScratch sc;  // reach's, the current targets and the segment counters
   if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return reach_path_scratch(p, na, nv, B, persistent); }, &sc))
     return r;
@@ -1193,8 +1174,7 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
     io.iters = sc.iters;
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
-    HIP_TRY(static_cast<hipError_t>(slots ? launch_reach_path_obstacle_kernel(grid, st, m->d_model, kt, kq, io, rp, *ob)
-                                          : launch_reach_path_kernel(grid, st, m->d_model, kt, kq, io, rp)));
+    HIP_TRY(static_cast<hipError_t>(launch_reach_path_kernel(grid, st, m->d_model, kt, kq, io, rp, si)));
     return L.done();
   }
   // reach()'s start, at waypoint 0 with no step taken
@@ -1215,9 +1195,9 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   qp.iters = sc.iters;
   for (int64_t r = 0; r <= rounds; ++r) {
     const int last = r == rounds;
-    if (int rc = launch_locked(m, params, 1, sg, stream, ob)) return rc;
+    if (int rc = launch_locked(m, params, 1, sg, stream, si)) return rc;
     if (!last)
-      if (int rc = launch_locked(m, params, 0, qp, stream, ob)) return rc;
+      if (int rc = launch_locked(m, params, 0, qp, stream, si)) return rc;
     HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, sc.pose,
                                                                     sc.dist, sc.eta, sc.status, sc.iters)));
   }
@@ -1248,16 +1228,16 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
                        const double* qdot0, const double* xt, const double* xdt, int32_t* seed, int32_t* result,
                        int32_t* steps_used, double* q_sol, double* qdot_sol, int32_t* status_last,
                        int32_t* iters_total, double* err_final, double* dist_final, int32_t* inst_result,
-                       int32_t* inst_steps, void* stream, const Obst* ob = nullptr) {
+                       int32_t* inst_steps, void* stream, StageIn si = {}) {
   drc_model_impl* m = const_cast<drc_model_impl*>(cm);
   if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
   std::lock_guard<std::mutex> launch_lock(m->launch_mu);
-  if (int rc = check_slots(m, ob, kSlotsReachSeedsMsg, "drc_qpik_reach_seeds_batch")) return rc;
+  if (int rc = check_slots(m, &si, kSlotsReachSeedsMsg, "drc_qpik_reach_seeds_batch")) return rc;
   if (S < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "seeds must be at least 1");
   if (T < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative number of targets");
   if (rule != DRC_SEEDS_FIRST && rule != DRC_SEEDS_FEWEST_STEPS)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "rule is DRC_SEEDS_FIRST or DRC_SEEDS_FEWEST_STEPS");
-  if (int rc = check_obstacle_pose(ob, T, "the number of targets")) return rc;
+  if (int rc = check_obstacle_pose(si, T, "the number of targets")) return rc;
   if (params->mode != DRC_MODE_QPIK_STEP)
     return set_err(DRC_ERR_INVALID_ARGUMENT, "drc_qpik_reach_seeds_batch runs DRC_MODE_QPIK_STEP only");
   if (max_steps < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "max_steps must not be negative");
@@ -1279,13 +1259,12 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   StreamCtx* const cx = L.cx;
   const DevModel& dm = m->hm.dev;
   const int nv = dm.nv, na = kq.na;
-  const bool slots = dm.nobst > 0;
   const int64_t B = T * S;
   double tau[2];
   reach_thresholds(pos_tol, rot_tol, tau);
   const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(plan_in(m, B, 0, &kq), reach_max, false, true);
-  const bool ob_expand = ob && ob->ld != 0;
+  const bool persistent = persistent_path(plan_in(m, B, 0, &kq, si), reach_max, StageFamily::ReachSeeds);
+  const bool ob_expand = si.ob.ld != 0;
   // the expanded targets and poses, the instances' finals and outcomes, one step's scratch, the groups' words
   SeedsScratch sc;
   if (int r = L.carve(&StreamCtx::seeds,
@@ -1293,11 +1272,10 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
     return r;
   HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 12, T, S, xt, T, sc.xt)));
   HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, 6, T, S, xdt, T, sc.xdt)));
-  Obst obe{nullptr, 0};
-  if (ob) obe = *ob;
-  if (ob_expand) {
-    HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_expand_kernel(st, dm.nobst * 12, T, S, ob->pose, ob->ld, sc.pose)));
-    obe = Obst{sc.pose, B};
+  if (ob_expand) {  // from here on si carries the expanded poses
+    HIP_TRY(static_cast<hipError_t>(
+        launch_reach_seeds_expand_kernel(st, dm.nobst * 12, T, S, si.ob.pose, si.ob.ld, sc.pose)));
+    si.ob = ObstIn{sc.pose, B};
   }
   // the diagnostics are the instances' own result / steps_used
   const ReachSeedsArgs rs{{max_steps, dt, tau[0], tau[1], sc.qf, sc.vf, inst_result ? inst_result : sc.result,
@@ -1313,12 +1291,11 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
     unsigned grid;
     if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
     HIP_TRY(hipMemsetAsync(sc.word, 0xff, size_t(T) * 4, st));  // kSeedsNoKey
-    HIP_TRY(static_cast<hipError_t>(slots ? launch_reach_seeds_obstacle_kernel(grid, st, m->d_model, kt, kq, io, rs, obe)
-                                          : launch_reach_seeds_kernel(grid, st, m->d_model, kt, kq, io, rs)));
+    HIP_TRY(static_cast<hipError_t>(launch_reach_seeds_kernel(grid, st, m->d_model, kt, kq, io, rs, si)));
   } else {
     if (int rc = reach_locked(m, params, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, sc.xt, sc.xdt, re.qf, re.vf,
                               re.result, re.steps_used, re.status_last, re.iters_total, re.err_final, re.dist_final,
-                              stream, ob ? &obe : nullptr))
+                              stream, si))
       return rc;
   }
   const ReachSeedsOut out{seed, result, steps_used, q_sol, qdot_sol, status_last, iters_total, err_final, dist_final};
@@ -1381,9 +1358,10 @@ static int launch_qpid(const drc_model_impl* cm, const drc_qpik_params* params, 
   // the task and the QP queue
   HIP_TRY(hipMemsetAsync(qc, 0, (StreamCtx::kSlotQp + StreamCtx::kXcdClasses) * sizeof(int), st));
   io.queue = qc + StreamCtx::kSlotTask;
+  const StageIn si{stage_build(d.has_mesh != 0, false, false)};  // (no slots here: the hulls alone decide)
   HIP_TRY(static_cast<hipError_t>(launch_task_kernel(1, static_cast<unsigned>(grid),
                                                      static_cast<size_t>(kt_c.lds_doubles) * sizeof(double), st,
-                                                     m->d_model, kt_c, io, m->hm.dev.has_mesh != 0)));
+                                                     m->d_model, kt_c, io, si)));
   if (!stages) {
     io.queue = qc + StreamCtx::kSlotQp;
     const size_t lds = static_cast<size_t>(kq_c.lds_doubles) * sizeof(double);
@@ -1427,9 +1405,10 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
     // fixed assignment when every wave has one instance: no counter reset to enqueue
     io.queue = B > grid ? cx->d_queue + StreamCtx::kQueueSlotCf * StreamCtx::kSlotInts + StreamCtx::kSlotTask : nullptr;
     if (io.queue) HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kXcdClasses * sizeof(int), st));
+    // (no distance stage: hull models run the Plain build too)
     HIP_TRY(static_cast<hipError_t>(launch_task_kernel(2, static_cast<unsigned>(grid),
                                                        static_cast<size_t>(kt.lds_doubles) * sizeof(double), st,
-                                                       m->d_model, kt, io)));
+                                                       m->d_model, kt, io, StageIn())));
     return L.done();
   }
   if (m->hm.dev.kind != 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "CLIK / OSF are Manipulator::RobotController entries");
@@ -1469,7 +1448,7 @@ static int launch_closed_form(const drc_model_impl* cm, const drc_qpik_params* p
   HIP_TRY(hipMemsetAsync(io.queue, 0, StreamCtx::kXcdClasses * sizeof(int), st));
   HIP_TRY(static_cast<hipError_t>(launch_task_kernel(2, static_cast<unsigned>(grid),
                                                      static_cast<size_t>(kt.lds_doubles) * sizeof(double), st,
-                                                     m->d_model, kt, io)));
+                                                     m->d_model, kt, io, StageIn())));
   return L.done();
 }
 
@@ -2062,10 +2041,10 @@ int drc_qpik_rollout_obstacles_batch(const drc_model* m, const drc_qpik_params* 
                                      double* q_final, double* qdot_final, double* qdot_traj, int32_t* status_traj,
                                      int32_t* iters_traj, double* q_traj, double* pose_traj, double* dist_traj,
                                      void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
-  return drc_amd::rollout(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step, q_final, qdot_final,
-                          qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream, &ob,
-                          obstacles_per_step);
+  return drc_qpik_rollout_moving_obstacles_batch(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step,
+                                                 obstacle_pose, nullptr, obstacle_ld, obstacles_per_step, q_final,
+                                                 qdot_final, qdot_traj, status_traj, iters_traj, q_traj, pose_traj,
+                                                 dist_traj, stream);
 }
 
 // ---- moving obstacles: a twist per slot (task_stage.hpp RATE) ------------------------
@@ -2074,13 +2053,11 @@ int drc_qpik_moving_obstacles_batch(const drc_model* m, const drc_qpik_params* p
                                     const double* qdot, const double* xt, const double* xdt, const double* xi,
                                     const double* xdi, const double* obstacle_pose, const double* obstacle_twist,
                                     int64_t obstacle_ld, double* out, int32_t* status, int32_t* iters, void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
-  const drc_amd::Rate rt{obstacle_twist, obstacle_ld, nullptr};
   drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
   io.out = out;
   io.status = status;
   io.iters = iters;
-  return drc_amd::launch(m, p, 0, io, stream, &ob, obstacle_twist ? &rt : nullptr);
+  return drc_amd::launch(m, p, 0, io, stream, drc_amd::stage_in(obstacle_pose, obstacle_ld, obstacle_twist));
 }
 
 int drc_qpik_stages_moving_obstacles_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, const double* q,
@@ -2089,8 +2066,6 @@ int drc_qpik_stages_moving_obstacles_batch(const drc_model* m, const drc_qpik_pa
                                            const double* obstacle_twist, int64_t obstacle_ld, double* pose, double* jac,
                                            double* man, double* dist, int32_t* pair, double* xdd, double* dist_rate,
                                            void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
-  const drc_amd::Rate rt{obstacle_twist, obstacle_ld, dist_rate};
   drc_amd::IO io = drc_amd::task_io(B, q, qdot, xt, xdt, xi, xdi);
   io.st_pose = pose;
   io.st_jac = jac;
@@ -2098,7 +2073,9 @@ int drc_qpik_stages_moving_obstacles_batch(const drc_model* m, const drc_qpik_pa
   io.st_dist = dist;
   io.st_pair = pair;
   io.st_xdd = xdd;
-  if (int rc = drc_amd::launch(m, p, 1, io, stream, &ob, obstacle_twist ? &rt : nullptr)) return rc;
+  if (int rc = drc_amd::launch(m, p, 1, io, stream,
+                               drc_amd::stage_in(obstacle_pose, obstacle_ld, obstacle_twist, dist_rate)))
+    return rc;
   if (!obstacle_twist && dist_rate && B > 0) {  // no twist: nothing but the robot moves
     using drc_amd::set_err;
     HIP_TRY(hipSetDevice(m->device));
@@ -2115,11 +2092,9 @@ int drc_qpik_rollout_moving_obstacles_batch(const drc_model* m, const drc_qpik_p
                                             double* q_final, double* qdot_final, double* qdot_traj,
                                             int32_t* status_traj, int32_t* iters_traj, double* q_traj,
                                             double* pose_traj, double* dist_traj, void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
-  const drc_amd::Rate rt{obstacle_twist, obstacle_ld, nullptr};
   return drc_amd::rollout(m, p, B, steps, dt, q0, qdot0, xt, xdt, xi, xdi, targets_per_step, q_final, qdot_final,
-                          qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream, &ob,
-                          obstacles_per_step, obstacle_twist ? &rt : nullptr);
+                          qdot_traj, status_traj, iters_traj, q_traj, pose_traj, dist_traj, stream,
+                          drc_amd::stage_in(obstacle_pose, obstacle_ld, obstacle_twist), obstacles_per_step);
 }
 
 // ---- goal-reaching rollouts ------------------------------------------------------
@@ -2138,9 +2113,9 @@ int drc_qpik_reach_obstacles_batch(const drc_model* m, const drc_qpik_params* p,
                                    int64_t obstacle_ld, double* q_final, double* qdot_final, int32_t* result,
                                    int32_t* steps_used, int32_t* status_last, int32_t* iters_total,
                                    double* err_final, double* dist_final, void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
   return drc_amd::reach(m, p, B, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt, q_final, qdot_final, result,
-                        steps_used, status_last, iters_total, err_final, dist_final, stream, &ob);
+                        steps_used, status_last, iters_total, err_final, dist_final, stream,
+                        drc_amd::stage_in(obstacle_pose, obstacle_ld));
 }
 
 int drc_qpik_reach_path_batch(const drc_model* m, const drc_qpik_params* p, int64_t B, int waypoints, int max_steps,
@@ -2162,10 +2137,10 @@ int drc_qpik_reach_path_obstacles_batch(const drc_model* m, const drc_qpik_param
                                         int32_t* steps_used, int32_t* status_last, int32_t* iters_total,
                                         double* err_final, double* dist_final, double* dist_min, int32_t* steps_at,
                                         void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
   return drc_amd::reach_path(m, p, B, waypoints, max_steps, dt, pos_tol, rot_tol, q0, qdot0, x_path, xdot_path,
                              q_final, qdot_final, result, waypoints_reached, steps_used, status_last, iters_total,
-                             err_final, dist_final, dist_min, steps_at, stream, &ob);
+                             err_final, dist_final, dist_min, steps_at, stream,
+                             drc_amd::stage_in(obstacle_pose, obstacle_ld));
 }
 
 int drc_qpik_reach_seeds_batch(const drc_model* m, const drc_qpik_params* p, int64_t targets, int seeds, int rule,
@@ -2187,10 +2162,9 @@ int drc_qpik_reach_seeds_obstacles_batch(const drc_model* m, const drc_qpik_para
                                          double* qdot_sol, int32_t* status_last, int32_t* iters_total,
                                          double* err_final, double* dist_final, int32_t* inst_result,
                                          int32_t* inst_steps, void* stream) {
-  const drc_amd::Obst ob{obstacle_pose, obstacle_ld};
   return drc_amd::reach_seeds(m, p, targets, seeds, rule, cancel, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt,
                               seed, result, steps_used, q_sol, qdot_sol, status_last, iters_total, err_final,
-                              dist_final, inst_result, inst_steps, stream, &ob);
+                              dist_final, inst_result, inst_steps, stream, drc_amd::stage_in(obstacle_pose, obstacle_ld));
 }
 
 int drc_reach_thresholds(double pos_tol, double rot_tol, double out[2]) {

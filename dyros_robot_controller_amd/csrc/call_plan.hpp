@@ -1,12 +1,13 @@
 // The dispatch plan of a QPIK call: which task stage runs, whether the call is
 // one fused kernel or the task -> QP pipeline, in which order the instances
 // are handed out, into how many concurrent sub-batches the batch is cut and
-// how large each sub-batch's persistent grids are -- and the rule by which the
-// closed-loop entries pick their persistent kernel.  Pure integer logic on the
-// batch size, a few model facts and the DRC_* knobs (api.cpp reads the
-// environment and fills PlanIn; tools/call_plan_host_test.cpp runs the rules
-// with the host compiler).  Every threshold stands here with the measurement
-// that set it.
+// how large each sub-batch's persistent grids are -- then which build of the
+// task stage a model and a call need and which kernel family has it, and with
+// that the rule by which the closed-loop entries pick their persistent kernel.
+// Pure integer logic on the batch size, a few model facts and the DRC_* knobs
+// (api.cpp reads the environment and fills PlanIn;
+// tools/call_plan_host_test.cpp runs the rules with the host compiler).  Every
+// threshold stands here with the measurement that set it.
 #pragma once
 #include <cstdint>
 
@@ -35,6 +36,7 @@ struct PlanIn {
   int ncand_slots = 0;
   bool has_mesh = false;     // collision hulls
   bool slots = false;        // obstacle slots (nobst > 0)
+  bool twists = false;       // the call carries the slots' twists
   bool qp_compiled = false;  // the QP shape has a compile-time instantiation (qp_compiled())
   int qp_group = 64;         // kQpGroup: lanes per QP instance
   int max_cand_slots = 0;    // kMaxCandSlots
@@ -141,17 +143,57 @@ inline SubBatch plan_sub_batch(const PlanIn& in, const CallPlan& p, int c) {
   return s;
 }
 
+// The builds of the task stage, task_instance<PROBLEM, MESH, OBST, RATE>
+// (task_stage.hpp): plain, with the hull narrow phase, with obstacle slots
+// whose poses the call carries, and with the slots' twists as well
+enum class StageBuild { Plain, Mesh, Obst, Rate };
+constexpr int kStageBuilds = 4;
+
+// Hulls together with slots have no build: drc_model_set_obstacles refuses
+// slots on a hull model (model.cpp), so no model asks for one
+constexpr bool stage_build_exists(bool has_mesh, bool slots) { return !(has_mesh && slots); }
+// The build a model and a call need -- the one place that decides it.  twists:
+// the call carries obstacle twists (they count with slots only)
+constexpr StageBuild stage_build(bool has_mesh, bool slots, bool twists) {
+  return slots ? (twists ? StageBuild::Rate : StageBuild::Obst) : has_mesh ? StageBuild::Mesh : StageBuild::Plain;
+}
+// the builds whose calls carry the slots' poses
+constexpr bool takes_poses(StageBuild b) { return b == StageBuild::Obst || b == StageBuild::Rate; }
+
+// The kernel families that contain the stage: task_kernel's three problems
+// (the QPIK stage, the QPID stage, closed-form CLIK / OSF), the fused kernel
+// and the closed-loop entries' persistent kernels
+enum class StageFamily { Task0, Task1, Task2, Fused, Rollout, Reach, ReachPath, ReachSeeds };
+constexpr int kStageFamilies = 8;
+
+// Which family is compiled in which build (its launcher returns
+// hipErrorInvalidValue for any other).  Task2 has no distance stage, so hull
+// models run its plain build
+constexpr bool has_build(StageFamily f, StageBuild b) {
+  switch (f) {
+    case StageFamily::Task0:
+    case StageFamily::Fused: return true;
+    case StageFamily::Task1:
+    case StageFamily::Rollout: return b == StageBuild::Plain || b == StageBuild::Mesh;
+    case StageFamily::Task2:
+    case StageFamily::Reach: return b == StageBuild::Plain;
+    case StageFamily::ReachPath:
+    case StageFamily::ReachSeeds: return b == StageBuild::Plain || b == StageBuild::Obst;
+  }
+  return false;
+}
+
 // The fusion rule selects a closed-loop entry's persistent kernel (rollout,
 // reach, reach_path, reach_seeds): the compiled QP shapes up to max_b
-// instances, where the entry has a build that serves the model's hulls /
-// obstacle slots.  It asks for lane_stage == 0 where plan_call asks for !lane:
+// instances, where the entry's family has the build that the model and the
+// call need.  It asks for lane_stage == 0 where plan_call asks for !lane:
 // the persistent kernels have no lane stage, so any lane-stage mode that is
 // set sends these entries down their stepwise path -- also where the stepwise
 // calls then run without the lane stage themselves (mode 3 on a QP call, a
 // joint count without a lane build, a model with hulls or slots)
-inline bool persistent_path(const PlanIn& in, int64_t max_b, bool serves_hulls, bool serves_slots) {
-  return fusable_shape(in) && in.lane_stage == 0 && in.B <= max_b && (serves_slots || !in.slots) &&
-         (serves_hulls || !in.has_mesh);
+inline bool persistent_path(const PlanIn& in, int64_t max_b, StageFamily family) {
+  return fusable_shape(in) && in.lane_stage == 0 && in.B <= max_b && stage_build_exists(in.has_mesh, in.slots) &&
+         has_build(family, stage_build(in.has_mesh, in.slots, in.twists));
 }
 
 }  // namespace drc_amd

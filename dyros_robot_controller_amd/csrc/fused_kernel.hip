@@ -92,9 +92,19 @@ int launch_fused_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const De
 #else
 int launch_fused_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
                              const KParams& kq, const IO& io);
+int launch_fused_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                                 const KParams& kq, const IO& io, const ObstIn& ob);
+int launch_fused_rate_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
+                             const KParams& kq, const IO& io, const ObstIn& ob, const RateIn& rt);
 int launch_fused_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
-                        const KParams& kq, const IO& io, bool mesh) {
-  return mesh ? launch_fused_mesh_kernel(grid, lds, st, m, kt, kq, io) : launch_fused<false>(grid, lds, st, m, kt, kq, io);
+                        const KParams& kq, const IO& io, const StageIn& si) {
+  switch (si.build) {
+    case StageBuild::Plain: return launch_fused<false>(grid, lds, st, m, kt, kq, io);
+    case StageBuild::Mesh: return launch_fused_mesh_kernel(grid, lds, st, m, kt, kq, io);
+    case StageBuild::Obst: return launch_fused_obstacle_kernel(grid, lds, st, m, kt, kq, io, si.ob);
+    case StageBuild::Rate: return launch_fused_rate_kernel(grid, lds, st, m, kt, kq, io, si.ob, si.rt);
+  }
+  return hipErrorInvalidValue;
 }
 
 #ifdef DRC_PHASE_TIMING

@@ -1,19 +1,45 @@
-// Host-side launchers of the kernel translation units (task_kernel.hip,
-// qp_kernel.hip, qpid_kernel.hip), called by the C-ABI in api.cpp.  Each
+// Host-side launchers of the kernel translation units, called by the C-ABI in
+// api.cpp: the task stage (task_kernel.hip), the QP kernels (qp_kernel.hip,
+// qp_dense_kernel.hip, qpid_kernel.hip), the fused kernel (fused_kernel.hip),
+// the rollout and reach kernels (rollout_kernel.hip, reach_kernel.hip) and the
+// order kernel (order_kernel.hip); reach_path.hpp and reach_seeds.hpp declare
+// those of their entries.  A family that contains the task stage has one
+// launcher, which takes the call's StageIn and launches that build, from the
+// family's own or a sibling unit (*_mesh_kernel.hip, *_obstacle_kernel.hip,
+// *_rate_kernel.hip; call_plan.hpp has_build: which family has which).  Each
 // returns the hipError_t of its launch (0 = hipSuccess).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "call_plan.hpp"
 #include "kernel_common.hpp"
 
 namespace drc_amd {
 
-// task_kernel<problem>: 0 QPIK stage, 1 QPID stage, 2 closed-form CLIK / OSF
-// mesh: the model has convex-hull geometry (problems 0 and 1 then run the
-// build with the hull narrow phase; 2 has no distance stage)
+// What a launch of the task stage needs beyond IO: the build, and what the
+// Obst and Rate builds' kernels take as arguments of their own
+// (kernel_common.hpp) -- ob the call's poses, rt its twists
+struct StageIn {
+  StageBuild build = StageBuild::Plain;
+  ObstIn ob;
+  RateIn rt;
+  // step k of a per-step set of nobst slots: poses [steps][nobst][12][ld] and
+  // twists [steps][nobst][6][ld] (ld = 0: [steps][nobst][12 | 6])
+  StageIn at_step(int k, int nobst) const {
+    StageIn s = *this;
+    if (ob.pose) s.ob.pose += int64_t(k) * nobst * 12 * (ob.ld ? ob.ld : 1);
+    if (rt.twist) s.rt.twist += int64_t(k) * nobst * 6 * (rt.ld ? rt.ld : 1);
+    return s;
+  }
+  // the same poses without their twists: the Obst build where this is the Rate build
+  StageIn without_twists() const { return {build == StageBuild::Rate ? StageBuild::Obst : build, ob, RateIn()}; }
+};
+
+// task_kernel<problem>: 0 QPIK stage, 1 QPID stage, 2 closed-form CLIK / OSF;
+// hipErrorInvalidValue for a build the problem does not have
 int launch_task_kernel(int problem, unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
-                       const IO& io, bool mesh = false);
+                       const IO& io, const StageIn& si);
 // register-budget waves per SIMD of the task build launch_task_kernel picks
 // for a plan of `lds` bytes per wave, and of the QP kernel
 int task_waves_per_simd(int problem, size_t lds);
@@ -49,32 +75,18 @@ int launch_qp_dense_kernel(unsigned grid, size_t lds, hipStream_t st, const DevM
 int launch_qpid_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp, const IO& io);
 // fused task + QP kernel (compiled QPIK shapes; hipErrorInvalidValue otherwise);
 // lds = both plans' maximum plus the record slot
-// mesh: the build with the hull narrow phase, as for launch_task_kernel
 int launch_fused_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
-                        const KParams& kq, const IO& io, bool mesh = false);
-// the builds for models with obstacle slots (task_obstacle_kernel.hip,
-// fused_obstacle_kernel.hip): the QPIK stage and the fused kernel with
-// task_instance<0, false, OBST = true>, ob the call's poses
-int launch_task_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
-                                const IO& io, const ObstIn& ob);
-int launch_fused_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
-                                 const KParams& kq, const IO& io, const ObstIn& ob);
-// ... and for moving slots (task_rate_kernel.hip, fused_rate_kernel.hip):
-// task_instance<0, false, OBST = true, RATE = true>, rt the call's twists
-int launch_task_rate_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
-                            const IO& io, const ObstIn& ob, const RateIn& rt);
-int launch_fused_rate_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kt,
-                             const KParams& kq, const IO& io, const ObstIn& ob, const RateIn& rt);
+                        const KParams& kq, const IO& io, const StageIn& si);
 
-// persistent rollout kernel (rollout_kernel.hip; compiled QPIK shapes,
-// hipErrorInvalidValue otherwise): per instance `steps` times task stage, QP
-// and state update.  io as for launch_fused_kernel, with out / status / iters
+// persistent rollout kernel (rollout_kernel.hip; compiled QPIK shapes in the
+// Plain and Mesh builds, hipErrorInvalidValue otherwise): per instance `steps`
+// times task stage, QP and state update.  io as for launch_fused_kernel, with out / status / iters
 // the [steps][...] trajectories (out_step doubles between two steps' io.out);
 // qf / vf [dof][B] hold the state between steps; q_traj, pose_traj, dist_traj
 // may be NULL.  The LDS size follows from kt and kq
 int launch_rollout_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
                           const IO& io, int steps, int per_step, double dt, double* qf, double* vf, double* q_traj,
-                          double* pose_traj, double* dist_traj, int64_t out_step, bool mesh);
+                          double* pose_traj, double* dist_traj, int64_t out_step, const StageIn& si);
 // one rollout step's state update for the stepwise path: v = S(q_in) eta,
 // qf = q_in + dt v (q_in may be qf), also into q_traj unless NULL
 int launch_rollout_integrate_kernel(int64_t B, hipStream_t st, const DevModel* m, double dt, const double* q_in,
@@ -93,13 +105,13 @@ struct ReachArgs {
 };
 // `result` of an instance that has not stopped yet (stepwise path; every byte 0xff)
 constexpr int32_t kReachActive = -1;
-// persistent reach kernel (compiled QPIK shapes without hulls or obstacle
-// slots, hipErrorInvalidValue otherwise): per instance task stage, verdict, QP
+// persistent reach kernel (compiled QPIK shapes in the Plain build -- no hulls,
+// no obstacle slots -- hipErrorInvalidValue otherwise): per instance task stage, verdict, QP
 // and state update until it stops.  io as for launch_fused_kernel, with out /
 // status / iters one step's scratch (all three required) and xt the target.
 // The LDS size follows from kt and kq
 int launch_reach_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
-                        const IO& io, const ReachArgs& re);
+                        const IO& io, const ReachArgs& re, const StageIn& si);
 // step k of the stepwise path: the verdict of every instance still active from
 // the stage outputs pose [12][B] / dist [1+dof][B] at the state in re.qf /
 // re.vf, then (last = 0) the step's status and the state update from eta

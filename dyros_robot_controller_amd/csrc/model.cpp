@@ -23,6 +23,7 @@
 #include <sstream>
 
 #include "../../include/drc_amd.h"
+#include "call_plan.hpp"
 #include "mesh.hpp"
 
 namespace drc_amd {
@@ -563,7 +564,7 @@ int set_obstacles(HostModel* hm, int n, const int* type, const double* param, co
     *err = "set_obstacles: negative count or missing array";
     return DRC_ERR_INVALID_ARGUMENT;
   }
-  if (n > 0 && hm->has_mesh()) {
+  if (!stage_build_exists(hm->has_mesh(), n > 0)) {
     *err = "the model has collision meshes: obstacle slots are not built for hull models";
     return DRC_ERR_UNSUPPORTED;
   }

@@ -132,7 +132,8 @@ reach_kernel(const DevModel* __restrict__ M0, const KParams kt, const KParams kq
 }
 
 int launch_reach_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
-                        const IO& io, const ReachArgs& re) {
+                        const IO& io, const ReachArgs& re, const StageIn& si) {
+  if (!has_build(StageFamily::Reach, si.build)) return hipErrorInvalidValue;  // (the plain build only)
   const size_t lds = closed_loop_lds_bytes(kt, kq);
   const dim3 g(grid), blk(64);
   if (int r = with_compiled_shape(kq.nx, kq.ng, kq.np, [&](auto qd) {

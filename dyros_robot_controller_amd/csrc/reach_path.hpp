@@ -25,15 +25,12 @@ struct ReachPathArgs {
   int32_t* seg;
 };
 
-// persistent kernel (compiled QPIK shapes without hulls, hipErrorInvalidValue
-// otherwise): per instance task stage, verdict / waypoint advance, QP and
-// state update until it stops.  io as for launch_reach_kernel, its xt / xdt
-// unused (the kernel points them at the current waypoint's block)
+// persistent kernel (compiled QPIK shapes in the Plain and Obst builds,
+// hipErrorInvalidValue otherwise): per instance task stage, verdict / waypoint
+// advance, QP and state update until it stops.  io as for launch_reach_kernel,
+// its xt / xdt unused (the kernel points them at the current waypoint's block)
 int launch_reach_path_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
-                             const IO& io, const ReachPathArgs& rp);
-// the build for models with obstacle slots, ob the call's poses
-int launch_reach_path_obstacle_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt,
-                                      const KParams& kq, const IO& io, const ReachPathArgs& rp, const ObstIn& ob);
+                             const IO& io, const ReachPathArgs& rp, const StageIn& si);
 // one round of the stepwise path: verdict, waypoint advance (gathering the new
 // target into cur_xt / cur_xdt) or state update of every instance still
 // active, from the stage outputs pose [12][B] / dist [1+dof][B] at the state

@@ -192,9 +192,15 @@ int launch_reach_path_obstacle_kernel(unsigned grid, hipStream_t st, const DevMo
   return launch_shapes(grid, st, m, kt, kq, io, rp, ob);
 }
 #else
+int launch_reach_path_obstacle_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt,
+                                      const KParams& kq, const IO& io, const ReachPathArgs& rp, const ObstIn& ob);
 int launch_reach_path_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
-                             const IO& io, const ReachPathArgs& rp) {
-  return launch_shapes(grid, st, m, kt, kq, io, rp);
+                             const IO& io, const ReachPathArgs& rp, const StageIn& si) {
+  switch (si.build) {
+    case StageBuild::Plain: return launch_shapes(grid, st, m, kt, kq, io, rp);
+    case StageBuild::Obst: return launch_reach_path_obstacle_kernel(grid, st, m, kt, kq, io, rp, si.ob);
+    default: return hipErrorInvalidValue;  // (no build for hulls or twists)
+  }
 }
 
 // Stepwise path, one round.  Instances that have stopped (result !=

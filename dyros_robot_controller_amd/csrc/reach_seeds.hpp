@@ -124,16 +124,13 @@ struct ReachSeedsOut {
   double *err_final, *dist_final;
 };
 
-// persistent kernel (compiled QPIK shapes without hulls, hipErrorInvalidValue
-// otherwise): reach_kernel's loop per instance, with the publish and the
-// cancel check of its group's word.  io as for launch_reach_kernel, xt / xdt
-// the targets expanded to [..][S T]
+// persistent kernel (compiled QPIK shapes in the Plain and Obst builds,
+// hipErrorInvalidValue otherwise): reach_kernel's loop per instance, with the
+// publish and the cancel check of its group's word.  io as for
+// launch_reach_kernel, xt / xdt the targets expanded to [..][S T]; si.ob the
+// call's poses (ld 0, or expanded to [n][12][S T])
 int launch_reach_seeds_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
-                              const IO& io, const ReachSeedsArgs& rs);
-// the build for models with obstacle slots, ob the call's poses (ld 0, or
-// expanded to [n][12][S T])
-int launch_reach_seeds_obstacle_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt,
-                                       const KParams& kq, const IO& io, const ReachSeedsArgs& rs, const ObstIn& ob);
+                              const IO& io, const ReachSeedsArgs& rs, const StageIn& si);
 // dst [rows][S T] from src [rows][ld], ld >= T: column s T + t is column t
 int launch_reach_seeds_expand_kernel(hipStream_t st, int rows, int64_t T, int S, const double* src, int64_t ld,
                                      double* dst);

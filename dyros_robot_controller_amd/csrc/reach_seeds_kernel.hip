@@ -131,9 +131,15 @@ int launch_reach_seeds_obstacle_kernel(unsigned grid, hipStream_t st, const DevM
   return launch_shapes(grid, st, m, kt, kq, io, rs, ob);
 }
 #else
+int launch_reach_seeds_obstacle_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt,
+                                       const KParams& kq, const IO& io, const ReachSeedsArgs& rs, const ObstIn& ob);
 int launch_reach_seeds_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
-                              const IO& io, const ReachSeedsArgs& rs) {
-  return launch_shapes(grid, st, m, kt, kq, io, rs);
+                              const IO& io, const ReachSeedsArgs& rs, const StageIn& si) {
+  switch (si.build) {
+    case StageBuild::Plain: return launch_shapes(grid, st, m, kt, kq, io, rs);
+    case StageBuild::Obst: return launch_reach_seeds_obstacle_kernel(grid, st, m, kt, kq, io, rs, si.ob);
+    default: return hipErrorInvalidValue;  // (no build for hulls or twists)
+  }
 }
 
 // dst [rows][S T] from src [rows][ld]: one thread per element of dst

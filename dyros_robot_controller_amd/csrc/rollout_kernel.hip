@@ -157,11 +157,14 @@ int launch_rollout_mesh_kernel(unsigned grid, size_t lds, hipStream_t st, const 
                                const KParams& kq, const IO& io, const Rollout& ro);
 int launch_rollout_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
                           const IO& io, int steps, int per_step, double dt, double* qf, double* vf, double* q_traj,
-                          double* pose_traj, double* dist_traj, int64_t out_step, bool mesh) {
+                          double* pose_traj, double* dist_traj, int64_t out_step, const StageIn& si) {
   const Rollout ro{steps, per_step, dt, qf, vf, q_traj, pose_traj, dist_traj, out_step};
   const size_t lds = closed_loop_lds_bytes(kt, kq);
-  return mesh ? launch_rollout_mesh_kernel(grid, lds, st, m, kt, kq, io, ro)
-              : launch_rollout<false>(grid, lds, st, m, kt, kq, io, ro);
+  switch (si.build) {
+    case StageBuild::Plain: return launch_rollout<false>(grid, lds, st, m, kt, kq, io, ro);
+    case StageBuild::Mesh: return launch_rollout_mesh_kernel(grid, lds, st, m, kt, kq, io, ro);
+    default: return hipErrorInvalidValue;  // (no build takes poses: the stepwise path runs models with slots)
+  }
 }
 
 int launch_rollout_integrate_kernel(int64_t B, hipStream_t st, const DevModel* m, double dt, const double* q_in,

@@ -67,21 +67,38 @@ int task_waves_per_simd(int problem, size_t lds) {
   return problem == 0 && w3 ? 3 : DRC_TASK_WAVES;
 }
 
+// The QPIK stage's Obst and Rate builds are translation units of their own
+// (task_obstacle_kernel.hip, task_rate_kernel.hip includes it with
+// DRC_TASK_RATE defined), so that this unit compiles to what it was without them
+int launch_task_obstacle_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                                const IO& io, const ObstIn& ob);
+int launch_task_rate_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                            const IO& io, const ObstIn& ob, const RateIn& rt);
+
 int launch_task_kernel(int problem, unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
-                       const IO& io, bool mesh) {
+                       const IO& io, const StageIn& si) {
+  const StageFamily family = problem == 0 ? StageFamily::Task0 : problem == 1 ? StageFamily::Task1 : StageFamily::Task2;
+  if (!has_build(family, si.build)) return hipErrorInvalidValue;
   const bool w3 = task_waves_per_simd(problem, lds) == 3 && DRC_TASK_WAVES != 3;
-  if (mesh && problem == 0)  // (one build for hull models: the two-wave register budget)
-    hipLaunchKernelGGL((task_kernel<0, DRC_TASK_WAVES, true>), dim3(grid), dim3(64), lds, st, m, kp, io);
-  else if (mesh && problem == 1)
-    hipLaunchKernelGGL((task_kernel<1, DRC_TASK_WAVES, true>), dim3(grid), dim3(64), lds, st, m, kp, io);
-  else if (problem == 0 && w3)
-    hipLaunchKernelGGL((task_kernel<0, 3>), dim3(grid), dim3(64), lds, st, m, kp, io);
-  else if (problem == 0)
-    hipLaunchKernelGGL(task_kernel<0>, dim3(grid), dim3(64), lds, st, m, kp, io);
-  else if (problem == 1)
-    hipLaunchKernelGGL(task_kernel<1>, dim3(grid), dim3(64), lds, st, m, kp, io);
-  else
-    hipLaunchKernelGGL(task_kernel<2>, dim3(grid), dim3(64), lds, st, m, kp, io);
+  switch (si.build) {
+    case StageBuild::Rate: return launch_task_rate_kernel(grid, lds, st, m, kp, io, si.ob, si.rt);
+    case StageBuild::Obst: return launch_task_obstacle_kernel(grid, lds, st, m, kp, io, si.ob);
+    case StageBuild::Mesh:  // (one build for hull models: the two-wave register budget)
+      if (problem == 0)
+        hipLaunchKernelGGL((task_kernel<0, DRC_TASK_WAVES, true>), dim3(grid), dim3(64), lds, st, m, kp, io);
+      else
+        hipLaunchKernelGGL((task_kernel<1, DRC_TASK_WAVES, true>), dim3(grid), dim3(64), lds, st, m, kp, io);
+      break;
+    case StageBuild::Plain:
+      if (problem == 0 && w3)
+        hipLaunchKernelGGL((task_kernel<0, 3>), dim3(grid), dim3(64), lds, st, m, kp, io);
+      else if (problem == 0)
+        hipLaunchKernelGGL(task_kernel<0>, dim3(grid), dim3(64), lds, st, m, kp, io);
+      else if (problem == 1)
+        hipLaunchKernelGGL(task_kernel<1>, dim3(grid), dim3(64), lds, st, m, kp, io);
+      else
+        hipLaunchKernelGGL(task_kernel<2>, dim3(grid), dim3(64), lds, st, m, kp, io);
+  }
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 """csrc/call_plan.hpp -- the dispatch plan of a QPIK call and the rule that
-picks a closed-loop entry's persistent kernel -- compiled with the host
+picks a closed-loop entry's persistent kernel from the table of stage builds
+-- compiled with the host
 compiler (tools/call_plan_host_test.cpp).  The expected values below are
 written out from the rules as api.cpp documented them before the plan had a
 header of its own (thresholds: DRC_FUSE_MAX 16 384, DRC_ORDER_MIN / _MAX 2 049
@@ -31,6 +32,12 @@ def case(name, what, expect, extra=(), knobs=(), **kw):
     assert name not in CASES and set(kw) <= set(BASE), name
     f = dict(BASE, **kw)
     line = " ".join(list(knobs) + [what] + [str(f[k]) for k in FIELDS] + [str(x) for x in extra])
+    CASES[name] = (line, what, expect)
+
+
+def raw(name, line, what, expect):
+    """A query on the stage builds alone: no call behind it."""
+    assert name not in CASES, name
     CASES[name] = (line, what, expect)
 
 
@@ -110,17 +117,38 @@ case("sub_grid_knobs", "sub", dict(b0=0, Bc=5000, grid_task=1024, grid_qp=8, gri
 case("sub_grid_knobs_small", "sub", dict(grid_task=17, grid_qp=17, grid_fused=17), extra=[0], B=17,
      knobs=["grid_task=24", "grid_qp=31", "grid_fused=4000"])
 
-# ---- the persistent-path predicate, as its four users ask: (max_b, serves_hulls, serves_slots)
-ROLLOUT = [4096, 1, 0]      # manipulators; whole-body robots 65 536
-REACH = [65536, 0, 0]
-REACH_PATH = [65536, 0, 1]
-REACH_SEEDS = [65536, 0, 1]
-for who, args in (("rollout", ROLLOUT), ("reach", REACH), ("reach_path", REACH_PATH), ("reach_seeds", REACH_SEEDS)):
-    mx, hulls, slots = args
+# ---- the stage builds (DESIGN.md "Stage builds"): the build a model and a call need ...
+for mesh, slots, twists, name in ((0, 0, 0, "plain"), (0, 0, 1, "plain"), (1, 0, 0, "mesh"), (1, 0, 1, "mesh"),
+                                  (0, 1, 0, "obst"), (0, 1, 1, "rate"), (1, 1, 0, "none"), (1, 1, 1, "none")):
+    raw("build_%d%d%d" % (mesh, slots, twists), "build %d %d %d" % (mesh, slots, twists), "build", name)
+# ... and the whole table of which kernel family is compiled in which
+BUILDS = ("plain", "mesh", "obst", "rate")
+HAS = {
+    "problem0": ("plain", "mesh", "obst", "rate"),   # the QPIK task stage
+    "problem1": ("plain", "mesh"),                   # the QPID stage
+    "problem2": ("plain",),                          # closed-form (hull models run it too: no distance stage)
+    "fused": ("plain", "mesh", "obst", "rate"),
+    "rollout": ("plain", "mesh"),
+    "reach": ("plain",),
+    "reach_path": ("plain", "obst"),
+    "reach_seeds": ("plain", "obst"),
+}
+for fam, have in HAS.items():
+    for b in BUILDS:
+        raw("has_%s_%s" % (fam, b), "has %s %s" % (fam, b), "has", int(b in have))
+
+# ---- the persistent-path predicate, as its four users ask: (max_b, family), against the table above
+ROLLOUT_MAX = 4096      # manipulators; whole-body robots 65 536
+REACH_MAX = 65536
+for who, mx in (("rollout", ROLLOUT_MAX), ("reach", REACH_MAX), ("reach_path", REACH_MAX), ("reach_seeds", REACH_MAX)):
+    args = [mx, who]
     case("pers_%s_plain" % who, "pers", 1, extra=args, B=mx, fused=1)
     case("pers_%s_above_max" % who, "pers", 0, extra=args, B=mx + 1, fused=1)
-    case("pers_%s_hulls" % who, "pers", hulls, extra=args, B=256, fused=1, has_mesh=1)
-    case("pers_%s_slots" % who, "pers", slots, extra=args, B=256, fused=1, slots=1)
+    case("pers_%s_hulls" % who, "pers", int("mesh" in HAS[who]), extra=args, B=256, fused=1, has_mesh=1)
+    case("pers_%s_slots" % who, "pers", int("obst" in HAS[who]), extra=args, B=256, fused=1, slots=1)
+    case("pers_%s_moving_slots" % who, "pers", int("rate" in HAS[who]), extra=args, B=256, fused=1, slots=1,
+         knobs=["twists=1"])
+    case("pers_%s_twists_no_slots" % who, "pers", 1, extra=args, B=256, fused=1, knobs=["twists=1"])
     case("pers_%s_fusion_off" % who, "pers", 0, extra=args, B=256, fused=0)
     case("pers_%s_uncompiled" % who, "pers", 0, extra=args, B=256, fused=1, compiled=0)
     case("pers_%s_group_32" % who, "pers", 0, extra=args, B=256, fused=1, knobs=["qp_group=32"])
@@ -128,8 +156,8 @@ for who, args in (("rollout", ROLLOUT), ("reach", REACH), ("reach_path", REACH_P
     case("pers_%s_lane_mode1" % who, "pers", 0, extra=args, B=256, fused=1, lane_stage=1)
     case("pers_%s_lane_mode3" % who, "pers", 0, extra=args, B=256, fused=1, lane_stage=3)
     case("pers_%s_lane_mode1_nv8" % who, "pers", 0, extra=args, B=256, fused=1, lane_stage=1, nv=8)
-case("pers_rollout_whole_body", "pers", 1, extra=[65536, 1, 0], B=65536, fused=1, kind=1, nv=9)
-case("pers_hulls_and_slots", "pers", 0, extra=[65536, 1, 0], B=256, fused=1, has_mesh=1, slots=1)
+case("pers_rollout_whole_body", "pers", 1, extra=[65536, "rollout"], B=65536, fused=1, kind=1, nv=9)
+case("pers_hulls_and_slots", "pers", 0, extra=[65536, "rollout"], B=256, fused=1, has_mesh=1, slots=1)
 # ... where plan_call, asked for the same model, runs without the lane stage and fuses
 case("plan_lane_mode3_fuses", "plan", dict(lane=0, fuse=1), B=256, fused=1, lane_stage=3)
 case("plan_lane_mode1_nv8_fuses", "plan", dict(lane=0, fuse=1), B=256, fused=1, lane_stage=1, nv=8)
@@ -154,8 +182,11 @@ def test_plan(answers, name):
     line, what, expect = CASES[name]
     tok = answers[name].split()
     assert tok[0] == what, (line, answers[name])
+    if what == "build":
+        assert tok[1:] == [expect], (line, answers[name])
+        return
     got = [int(t) for t in tok[1:]]
-    if what == "pers":
+    if what in ("pers", "has"):
         assert got == [expect], (line, answers[name])
         return
     out = dict(zip(PLAN_OUT if what == "plan" else SUB_OUT, got))

@@ -155,6 +155,33 @@ def test_fr3_box_as_mesh_fused_and_qpid(cuda, tmp_path, fr3_primitive):
     assert np.median(e) <= 1e-9 and e.max() <= 1e-4 * max(1.0, np.abs(both[1][1]).max())
 
 
+def test_fr3_box_as_mesh_qpid_stage(cuda, tmp_path, fr3_primitive):
+    """The QPID stage's hull build at three states whose closest pair is one of
+    the hull's: its distance row equals the QPIK stage's bit for bit
+    (tests/test_gpu_qpid.py holds that for the primitives) and the oracle's on
+    the primitive twin within the distance tolerances above.  A QPID stage
+    without the hull narrow phase forms another row at these states."""
+    from dyros_robot_controller_amd import _batch
+    P = fr3_primitive
+    urdf, _ = _box_as_mesh_urdf(tmp_path, "fr3", "package://pkg/meshes/box.stl")
+    rd = manipulator.RobotData(urdf, robot_path("fr3", "srdf"), str(tmp_path), device=cuda)
+    ctrl = manipulator.RobotController(0.001, rd, solver_mode="exact")
+    q, qd, xt, xdt = (np.ascontiguousarray(P[k][:, -3:]) for k in ("q", "qd", "xt", "xdt"))
+    p = ctrl._pbd.params(LINK["fr3"], _capi.MODE_QPID_STEP, ctrl.Kp_task_, ctrl.Kv_task_)
+    a = lambda v: _batch.as_device(v, cuda)
+    st = {k: v.cpu().numpy() for k, v in _batch.qpid_stages_batch(rd.model, p, a(q), a(qd), a(xt), a(xdt)).items()}
+    ik = {k: v.cpu().numpy() for k, v in _batch.stages_batch(rd.model, p, a(q), a(qd), a(xt), a(xdt)).items()}
+    assert np.isin(st["pair"], P["box_pairs"]).all()   # the hull decides the distance row
+    for k in ("pose", "jac", "man", "dist", "pair"):
+        np.testing.assert_array_equal(st[k], ik[k], err_msg=k)
+    _, om, _ = O.load("fr3")
+    for b in range(3):
+        d, dg, pr = O.min_distance(om, q[:, b])
+        print("instance %d: pair %d (oracle %d), d %.6f, |d - oracle| %.3e, max |grad - oracle| %.3e" %
+              (b, st["pair"][b], pr, d, abs(st["dist"][0, b] - d), np.abs(st["dist"][1:, b] - dg).max()))
+        assert _dist_close(st["dist"][0, b], d), (b, st["dist"][0, b], d)
+
+
 def test_husky_fr3_chassis_as_mesh(cuda, tmp_path):
     MM = mobile_manipulator
     spec = O.ROBOTS["husky_fr3"]

@@ -27,7 +27,7 @@ import pytest
 
 import oracle as O
 import pyref as R
-from _common import LINK, make_manipulator, make_moma, moma_step_inputs, step_inputs
+from _common import LINK, make_manipulator, make_moma, moma_step_inputs, oracle_batch, stage_step, step_inputs
 from _mesh_io import box_triangles, write_stl_ascii
 from dyros_robot_controller_amd import _batch, _capi, manipulator, mobile_manipulator, robot_path
 
@@ -258,9 +258,9 @@ def test_aliasing_and_optional_outputs(cuda, robot):
 
 
 # 6 ------------------------------------------------------------------------
-def test_urdf_with_a_collision_mesh(cuda, tmp_path):
+def _hull_fr3(cuda, tmp_path):
     """FR3 with its box primitive as a 12-triangle STL of the same size (the
-    fixture of tests/test_gpu_mesh_model.py): the MESH build of the kernel."""
+    fixture of tests/test_gpu_mesh_model.py)."""
     import re
     text = open(robot_path("fr3")).read()
     m = re.search(r'<box size="([^"]+)"/>', text)
@@ -270,11 +270,52 @@ def test_urdf_with_a_collision_mesh(cuda, tmp_path):
     (tmp_path / "pkg" / "urdf").mkdir()
     urdf = tmp_path / "pkg" / "urdf" / "fr3_mesh.urdf"
     urdf.write_text(text[:m.start()] + '<mesh filename="package://pkg/meshes/box.stl"/>' + text[m.end():])
-    rd = manipulator.RobotData(str(urdf), robot_path("fr3", "srdf"), str(tmp_path), device=cuda)
+    return manipulator.RobotData(str(urdf), robot_path("fr3", "srdf"), str(tmp_path), device=cuda)
+
+
+def test_urdf_with_a_collision_mesh(cuda, tmp_path):
+    """The hull FR3: the MESH build of the kernel."""
+    rd = _hull_fr3(cuda, tmp_path)
     S = dict(_setup("fr3", cuda), rd=rd, ctrl=manipulator.RobotController(DT, rd, solver_mode="exact"))
     whole = _roll(S, "step", 2, link=LINK["fr3"])
     _assert_same(whole, _chain(S, "step", 2, LINK["fr3"]))
     assert (whole["status_traj"] == 1).any()
+
+
+def test_hull_decides_the_distance(cuda, tmp_path):
+    """The hull FR3 at three states whose closest pair is one of the hull's:
+    the persistent kernel against the stepwise path (the task kernel's and the
+    fused kernel's hull builds, which tests/test_gpu_mesh_model.py holds
+    against the primitive twin), bit for bit, and step 0 against the oracle on
+    the primitive twin within the end-to-end bound of tests/test_gpu_parity.py.
+    A persistent kernel without the hull narrow phase forms another distance
+    row at these states."""
+    rd = _hull_fr3(cuda, tmp_path)
+    _, om, _ = O.load("fr3")
+    box = [g for g in range(om.ngeom) if om.gtype[g] == 2]
+    box_pairs = [p for p in range(om.npairs) if box[0] in (om.pair_a[p], om.pair_b[p])]
+    q, qd, xt, xdt = step_inputs(rd, "fr3", 42, 2048, cuda)
+    pick = np.flatnonzero(np.isin(stage_step(rd.model, cuda, q, qd, xt, xdt, LINK["fr3"])["pair"], box_pairs))[:3]
+    assert len(pick) == 3
+    q, qd, xt, xdt = (np.ascontiguousarray(v[:, pick]) for v in (q, qd, xt, xdt))
+    S = dict(rd=rd, ctrl=manipulator.RobotController(DT, rd, solver_mode="exact"), q=q, qd=qd, xt=xt, xdt=xdt)
+    got = {}
+    try:
+        for fused in (1, 0):
+            _set_fusion(S, fused)
+            got[fused] = _roll(S, "step", 2, link=LINK["fr3"])
+    finally:
+        _set_fusion(S, 1)
+    _assert_same(got[1], got[0])
+    st = stage_step(rd.model, cuda, q, qd, xt, xdt, LINK["fr3"])
+    assert np.isin(st["pair"], box_pairs).all()   # a hull pair is the closest at step 0 ...
+    np.testing.assert_array_equal(got[1]["dist_traj"][0], st["dist"])   # ... and that is the row the kernel formed
+    ref, rstat, _, _ = oracle_batch("fr3", q, qd, xt, xdt, exact=True)
+    np.testing.assert_array_equal(got[1]["status_traj"][0], rstat)
+    err = np.abs(got[1]["qdot_traj"][0] - ref).max(axis=0)
+    print("hull pairs %s, d %s; step 0 against the oracle: max %.3e" % (st["pair"].tolist(), st["dist"][0].tolist(),
+                                                                         err.max()))
+    assert (rstat == 1).any() and err.max() <= 1e-4, err
 
 
 # 7 ------------------------------------------------------------------------
