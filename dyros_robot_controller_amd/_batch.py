@@ -471,6 +471,66 @@ def qpik_reach_seeds_batch(model, params, q, qdot, x_target, xdot_target, max_st
     return res
 
 
+class ClearanceResult:
+    """Device tensors of one ``drc_clearance_path_batch`` call, one entry per
+    path: ``result`` [B] (FREE / BLOCKED / INVALID), ``sample_stop`` [B] (-1
+    when FREE), ``d_min`` [B], ``sample_min`` [B], ``pair_min`` [B], and
+    ``dist_traj`` [N][B] when asked for (None otherwise; entries past a stop
+    hold what the tensor held before the call)."""
+    FREE, BLOCKED, INVALID = _capi.CLEAR_FREE, _capi.CLEAR_BLOCKED, _capi.CLEAR_INVALID
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def clearance_path_batch(model, q_path, substeps=1, d_stop=None, obstacle_pose=None, dist_traj=False, stream=None):
+    """Launch ``drc_clearance_path_batch`` on a device tensor ``q_path``
+    [waypoints][dof][B] (a rollout's ``q_traj`` fits): the minimum distance over
+    the N = (waypoints - 1) substeps + 1 samples of each path, stopping at the
+    first sample below ``d_stop`` (None: -inf, the whole profile).
+    ``obstacle_pose`` [n][12] or [n][12][B] (see obstacle_poses):
+    ``drc_clearance_path_obstacles_batch``.  ``dist_traj``: True allocates the
+    [N][B] profile (zeros), a tensor of that shape is filled in place."""
+    torch = _torch()
+    dev = q_path.device
+    nv = model.dof
+    if q_path.dim() != 3 or q_path.shape[1] != nv or q_path.dtype != torch.float64 or not q_path.is_contiguous():
+        raise ValueError("q_path must be a contiguous float64 [waypoints][%d][B] tensor, got %s"
+                         % (nv, tuple(q_path.shape)))
+    W, B = int(q_path.shape[0]), int(q_path.shape[2])
+    substeps = int(substeps)
+    N = (W - 1) * substeps + 1
+    if isinstance(dist_traj, torch.Tensor):
+        if tuple(dist_traj.shape) != (N, B) or dist_traj.dtype != torch.float64 or not dist_traj.is_contiguous():
+            raise ValueError("dist_traj must be a contiguous float64 [N=%d][B=%d] tensor, got %s"
+                             % (N, B, tuple(dist_traj.shape)))
+        traj = dist_traj
+    else:
+        traj = torch.zeros((max(N, 0), B), dtype=torch.float64, device=dev) if dist_traj else None
+    i = lambda: torch.empty(B, dtype=torch.int32, device=dev)
+    res = ClearanceResult(result=i(), sample_stop=i(), d_min=torch.empty(B, dtype=torch.float64, device=dev),
+                          sample_min=i(), pair_min=i(), dist_traj=traj)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    head = (model.handle, C.c_int64(B), C.c_int(W), C.c_int(substeps),
+            C.c_double(-np.inf if d_stop is None else d_stop), _ptr(q_path))
+    tail = (_ptr(res.result), _ptr(res.sample_stop), _ptr(res.d_min), _ptr(res.sample_min), _ptr(res.pair_min),
+            _ptr(res.dist_traj), C.c_void_p(stream))
+    if obstacle_pose is not None:
+        op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
+        _capi.check(_capi.lib().drc_clearance_path_obstacles_batch(*head, _ptr(op), C.c_int64(ld), *tail))
+    else:
+        _capi.check(_capi.lib().drc_clearance_path_batch(*head, *tail))
+    return res
+
+
+def clearance_grid(model):
+    """``drc_debug_clearance_grid``: the waves of the model's last clearance launch (0: none yet)."""
+    g = C.c_int64()
+    _capi.check(_capi.lib().drc_debug_clearance_grid(model.handle, C.byref(g)))
+    return g.value
+
+
 def qpid_batch(model, params, q, qdot, x_target=None, xdot_target=None, x_init=None, xdot_init=None,
                qddot=None, tau=None, status=None, iters=None, stream=None):
     """Launch ``drc_qpid_batch``: returns (qddot [na][B],

@@ -20,6 +20,7 @@
 #include "../../include/drc_amd.h"
 #include "../../include/drc_amd_debug.h"
 #include "call_plan.hpp"
+#include "clearance.hpp"
 #include "dynamics.hpp"
 #include "host_staging.hpp"
 #include "kernel_common.hpp"
@@ -112,6 +113,7 @@ struct drc_model_impl {
   int eqp_small_cap = -1;  // drc_debug_eqp_small_cap: -1 the compiled tiers, 0 general EQP only, k small EQP for N <= k
   bool qp_dense = false;   // drc_debug_qp_dense: the manipulator shapes' QP kernel with dense G loops
   int64_t qp_dense_launches = 0;
+  int64_t clearance_grid_last = 0;  // drc_debug_clearance_grid: waves of the last clearance launch
   // timed calls: the events and the call's sub-batch count S.  S > 1: {call
   // start, call end, then per sub-batch task start, task end, QP end}; S = 1:
   // {task start, last, task start, task end, last} (last: the QP's end, or the
@@ -611,6 +613,7 @@ static const PlanKnobs& plan_knobs() {
     v.grid_task = env_int("DRC_GRID_TASK", v.grid_task, 8);
     v.grid_qp = env_int("DRC_GRID_QP", v.grid_qp, 8);
     v.grid_fused = env_int("DRC_GRID_FUSED", v.grid_fused, 8);
+    v.grid_clear = env_int("DRC_GRID_CLEAR", v.grid_clear, 8);
     return v;
   }();
   return k;
@@ -1303,6 +1306,51 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   return L.done();
 }
 
+// --------------------------------------------------------------------------
+// Path clearance (drc_clearance_path_batch): one launch of the persistent
+// clearance kernel (clearance_kernel.hip) on the caller's stream -- every model
+// runs it, there is no stepwise form.  params: defaults (the distance stage
+// reads none of them; they size the task plan).  The queue is slot 0's, as a
+// closed-loop entry's single launch
+// --------------------------------------------------------------------------
+static_assert(kClearFree == DRC_CLEAR_FREE && kClearBlocked == DRC_CLEAR_BLOCKED && kClearInvalid == DRC_CLEAR_INVALID,
+              "clearance.hpp and drc_amd.h agree on the verdicts");
+static const char kSlotsClearanceMsg[] =
+    "the model has obstacle slots: pass their poses through drc_clearance_path_obstacles_batch";
+
+static int clearance(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int waypoints, int substeps,
+                     double d_stop, const double* q_path, int32_t* result, int32_t* sample_stop, double* d_min,
+                     int32_t* sample_min, int32_t* pair_min, double* dist_traj, void* stream, StageIn si = {}) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  if (int rc = check_batch(B)) return rc;
+  if (int r = check_slots(m, &si, kSlotsClearanceMsg, "drc_clearance_path_batch")) return r;
+  if (int r = check_obstacle_pose(si, B, "the batch")) return r;
+  if (waypoints < 1 || substeps < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints and substeps must be at least 1");
+  if (d_stop != d_stop) return set_err(DRC_ERR_INVALID_ARGUMENT, "d_stop is NaN (-INFINITY never blocks)");
+  if (clearance_samples(waypoints, substeps) > 0x7fffffff)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "(waypoints - 1) substeps + 1 samples do not fit 31 bits");
+  if (B == 0) return DRC_OK;
+  if (!q_path || !result || !sample_stop || !d_min || !sample_min || !pair_min)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "q_path, result, sample_stop, d_min, sample_min and pair_min are required");
+  KParams kt;
+  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  IO io = make_io(B);
+  kt.xcd_map = xcd_map_for(B);
+  HIP_TRY(hipMemsetAsync(L.cx->d_queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+  io.queue = L.cx->d_queue + StreamCtx::kSlotTask;
+  const ClearArgs ca{waypoints, substeps, d_stop, q_path, result, sample_stop, d_min, sample_min, pair_min, dist_traj};
+  const unsigned grid = static_cast<unsigned>(clearance_grid(B, plan_knobs()));
+  HIP_TRY(static_cast<hipError_t>(launch_clearance_kernel(
+      grid, static_cast<size_t>(kt.lds_doubles) * sizeof(double), st, m->d_model, kt, io, ca, si)));
+  m->clearance_grid_last = grid;
+  return L.done();
+}
+
 // QPID pipeline for one call: dynamics launch(es) -> task kernel (QPID stage
 // data into the records) -> QPID kernel; or, with stages, the task kernel
 // writing the stage outputs.  Model-owned scratch holds the records and the
@@ -1653,6 +1701,13 @@ int drc_debug_qp_dense(drc_model* m, int on) {
   if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
   std::lock_guard<std::mutex> g(m->launch_mu);
   m->qp_dense = on != 0;
+  return DRC_OK;
+}
+
+int drc_debug_clearance_grid(drc_model* m, int64_t* grid) {
+  if (!m || !grid) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null argument");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  *grid = m->clearance_grid_last;
   return DRC_OK;
 }
 
@@ -2176,6 +2231,35 @@ int drc_reach_thresholds(double pos_tol, double rot_tol, double out[2]) {
   return DRC_OK;
 }
 
+// ---- path clearance ------------------------------------------------------------
+// (the distance stage reads no drc_qpik_params field: the defaults size its plan)
+static int clearance_params(const drc_model* m, drc_qpik_params* pp) {
+  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  if (int rc = drc_default_qpik_params(m, 1, pp)) return rc;
+  pp->mode = DRC_MODE_QPIK;
+  pp->frame_id = -1;
+  return DRC_OK;
+}
+
+int drc_clearance_path_batch(const drc_model* m, int64_t B, int waypoints, int substeps, double d_stop,
+                             const double* q_path, int32_t* result, int32_t* sample_stop, double* d_min,
+                             int32_t* sample_min, int32_t* pair_min, double* dist_traj, void* stream) {
+  drc_qpik_params pp;
+  if (int rc = clearance_params(m, &pp)) return rc;
+  return drc_amd::clearance(m, &pp, B, waypoints, substeps, d_stop, q_path, result, sample_stop, d_min, sample_min,
+                            pair_min, dist_traj, stream);
+}
+
+int drc_clearance_path_obstacles_batch(const drc_model* m, int64_t B, int waypoints, int substeps, double d_stop,
+                                       const double* q_path, const double* obstacle_pose, int64_t obstacle_ld,
+                                       int32_t* result, int32_t* sample_stop, double* d_min, int32_t* sample_min,
+                                       int32_t* pair_min, double* dist_traj, void* stream) {
+  drc_qpik_params pp;
+  if (int rc = clearance_params(m, &pp)) return rc;
+  return drc_amd::clearance(m, &pp, B, waypoints, substeps, d_stop, q_path, result, sample_stop, d_min, sample_min,
+                            pair_min, dist_traj, stream, drc_amd::stage_in(obstacle_pose, obstacle_ld));
+}
+
 // ---- QPID -------------------------------------------------
 int drc_default_qpid_params(const drc_model* m, int exact, drc_qpik_params* p) {
   int rc = drc_default_qpik_params(m, exact, p);
@@ -2470,6 +2554,39 @@ int drc_qpik_stages_host(drc_model* m, const drc_qpik_params* p, int64_t B, cons
   st.out(xdd, 6 * B, &io.st_xdd);
   st.out(pair, B, &io.st_pair);
   return st.run([&] { return drc_amd::launch(m, p, 1, io, m->hstream); });
+}
+
+// dist_traj goes both ways: the entries the walk does not reach keep what the
+// caller's array held, so its content is staged in and copied under the
+// kernel's stores before the launch
+int drc_clearance_path_host(drc_model* m, int64_t B, int waypoints, int substeps, double d_stop, const double* q_path,
+                            int32_t* result, int32_t* sample_stop, double* d_min, int32_t* sample_min,
+                            int32_t* pair_min, double* dist_traj) {
+  using drc_amd::set_err;
+  if (!m) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  if (B < 0) return set_err(DRC_ERR_INVALID_ARGUMENT, "negative batch");
+  if (waypoints < 1 || substeps < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints and substeps must be at least 1");
+  const int64_t N = drc_amd::clearance_samples(waypoints, substeps);
+  if (N > 0x7fffffff) return set_err(DRC_ERR_INVALID_ARGUMENT, "(waypoints - 1) substeps + 1 samples do not fit 31 bits");
+  if (B == 0) return DRC_OK;
+  HostStage st(m);
+  const double *dq, *dprev;
+  int32_t *dres, *dstop, *dsmin, *dpmin;
+  double *ddmin, *dtraj;
+  st.in(q_path, int64_t(waypoints) * m->hm.dev.nv * B, &dq);
+  st.in(static_cast<const double*>(dist_traj), N * B, &dprev);
+  st.out(result, B, &dres);
+  st.out(sample_stop, B, &dstop);
+  st.out(d_min, B, &ddmin);
+  st.out(sample_min, B, &dsmin);
+  st.out(pair_min, B, &dpmin);
+  st.out(dist_traj, N * B, &dtraj);
+  return st.run([&]() -> int {
+    if (dtraj && hipMemcpyAsync(dtraj, dprev, size_t(N) * B * 8, hipMemcpyDeviceToDevice, m->hstream) != hipSuccess)
+      return set_err(DRC_ERR_HIP, "hipMemcpyAsync(dist_traj)");
+    return drc_clearance_path_batch(m, B, waypoints, substeps, d_stop, dq, dres, dstop, ddmin, dsmin, dpmin, dtraj,
+                                    m->hstream);
+  });
 }
 
 

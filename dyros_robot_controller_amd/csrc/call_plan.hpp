@@ -22,6 +22,7 @@ struct PlanKnobs {
   int64_t grid_task = 1024;     // DRC_GRID_TASK (>= 8)
   int64_t grid_qp = 4096;       // DRC_GRID_QP (>= 8)
   int64_t grid_fused = 2048;    // DRC_GRID_FUSED (>= 8)
+  int64_t grid_clear = 3072;    // DRC_GRID_CLEAR (>= 8)
 };
 
 struct PlanIn {
@@ -143,6 +144,18 @@ inline SubBatch plan_sub_batch(const PlanIn& in, const CallPlan& p, int c) {
   return s;
 }
 
+// The persistent grid of a path-clearance call (drc_clearance_path_batch,
+// clearance_kernel.hip): one launch for the whole batch, one path per wave.
+// No QP kernel shares the CUs with it, so the pipeline's 1 024 task waves were
+// no evidence for it.  Swept with the register budget on FR3, B = 65 536,
+// substeps 8, no stop (tools/bench_clearance.py --sweep,
+// profiles/clearance_grid.json; the numbers in DESIGN.md "Path clearance"):
+// 1 024 waves leave half of the wave slots empty and cost 1.6 to 1.9 times
+// the call of 2 048 or 3 072 waves; with the three-wave build 3 072 is the
+// fastest.  At B = 4 096 (two-wave build, profiles/clearance_grid_b4096.json)
+// 2 048 and 3 072 are equal and 7 % ahead of 1 024.  DRC_GRID_CLEAR overrides
+inline int64_t clearance_grid(int64_t B, const PlanKnobs& knobs) { return persistent_grid(B, knobs.grid_clear); }
+
 // The builds of the task stage, task_instance<PROBLEM, MESH, OBST, RATE>
 // (task_stage.hpp): plain, with the hull narrow phase, with obstacle slots
 // whose poses the call carries, and with the slots' twists as well
@@ -162,9 +175,10 @@ constexpr bool takes_poses(StageBuild b) { return b == StageBuild::Obst || b == 
 
 // The kernel families that contain the stage: task_kernel's three problems
 // (the QPIK stage, the QPID stage, closed-form CLIK / OSF), the fused kernel
-// and the closed-loop entries' persistent kernels
-enum class StageFamily { Task0, Task1, Task2, Fused, Rollout, Reach, ReachPath, ReachSeeds };
-constexpr int kStageFamilies = 8;
+// and the closed-loop entries' persistent kernels; Clearance is the distance
+// stage alone along a path (clearance_kernel.hip)
+enum class StageFamily { Task0, Task1, Task2, Fused, Rollout, Reach, ReachPath, ReachSeeds, Clearance };
+constexpr int kStageFamilies = 9;
 
 // Which family is compiled in which build (its launcher returns
 // hipErrorInvalidValue for any other).  Task2 has no distance stage, so hull
@@ -179,6 +193,7 @@ constexpr bool has_build(StageFamily f, StageBuild b) {
     case StageFamily::Reach: return b == StageBuild::Plain;
     case StageFamily::ReachPath:
     case StageFamily::ReachSeeds: return b == StageBuild::Plain || b == StageBuild::Obst;
+    case StageFamily::Clearance: return b != StageBuild::Rate;  // (static slots: no twists)
   }
   return false;
 }

@@ -1,7 +1,8 @@
 // Host-side launchers of the kernel translation units, called by the C-ABI in
 // api.cpp: the task stage (task_kernel.hip), the QP kernels (qp_kernel.hip,
 // qp_dense_kernel.hip, qpid_kernel.hip), the fused kernel (fused_kernel.hip),
-// the rollout and reach kernels (rollout_kernel.hip, reach_kernel.hip) and the
+// the rollout and reach kernels (rollout_kernel.hip, reach_kernel.hip), the
+// path-clearance kernel (clearance_kernel.hip) and the
 // order kernel (order_kernel.hip); reach_path.hpp and reach_seeds.hpp declare
 // those of their entries.  A family that contains the task stage has one
 // launcher, which takes the call's StageIn and launches that build, from the
@@ -119,6 +120,27 @@ int launch_reach_kernel(unsigned grid, hipStream_t st, const DevModel* m, const 
 int launch_reach_update_kernel(int64_t B, hipStream_t st, const DevModel* m, int k, int last, const ReachArgs& re,
                                const double* xt, const double* pose, const double* dist, const double* eta,
                                const int32_t* status, const int32_t* iters);
+
+// drc_clearance_path_batch (clearance_kernel.hip): what its kernel takes beyond
+// IO, as an argument of its own (IO and KParams keep their size: DESIGN.md
+// "Obstacle slots").  q_path [waypoints][dof][ld]; result, sample_stop, d_min,
+// sample_min, pair_min [B]; dist_traj [N][ld] or NULL
+struct ClearArgs {
+  int waypoints, substeps;
+  double d_stop;
+  const double* q_path;
+  int32_t *result, *sample_stop;
+  double* d_min;
+  int32_t *sample_min, *pair_min;
+  double* dist_traj;
+};
+// persistent clearance kernel (the Plain, Mesh and Obst builds; any model, no
+// QP shape involved; hipErrorInvalidValue for Rate): one path per wave from the
+// work queue io.queue, the distance stage sample after sample until the rule
+// of clearance.hpp stops the walk.  kp: the task plan (lds its bytes); of io it
+// reads B, b0, ld and queue
+int launch_clearance_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                            const IO& io, const ClearArgs& ca, const StageIn& si);
 
 // queue order of one sub-batch (order_kernel.hip): penetration-prone
 // instances first (*hot_n zeroed; hot_list [B], hot_flag [B] scratch), then the

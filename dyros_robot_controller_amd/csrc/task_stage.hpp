@@ -482,7 +482,16 @@ __device__ __noinline__ void pose_pair(const DevModel* M, const double* T, doubl
 }
 
 // One instance b of the task stage on this wave (S: the wave's LDS plan kp).
-// PROBLEM 0: QPIK stage data; 1: also the QPID extras; 2: closed-form CLIK / OSF.
+// PROBLEM 0: QPIK stage data; 1: also the QPID extras; 2: closed-form CLIK / OSF;
+// 3: the distance stage alone (clearance_kernel.hip): FK chain, geometry poses,
+// pass 1, the candidate passes, EPA and the winner's refinement -- no targets,
+// frame Jacobian, task velocity, manipulability, grad d or record.  Its state
+// is what the caller left in the plan's kq (io.q is not read), and its result
+// stays in the plan: SC_DIST and SC_PAIR hold what the QPIK stage returns as
+// dist[0] and pair.  What it skips is switched off by the compile-time kTask
+// inside the statements' own conditions, never by a scope around them: the
+// other instantiations see the same scopes, hence the same lifetimes, and
+// compile to what they were (DESIGN.md "Path clearance").
 // MESH: the model has convex-hull geometry (GeomType kMesh).  A build of its
 // own, chosen at launch, so the kernels of mesh-free models carry none of it.
 // OBST: the model has obstacle slots (DevModel::nobst): geometries whose pose is
@@ -497,6 +506,7 @@ template <int PROBLEM, bool MESH = false, bool OBST = false, bool RATE = false>
 __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, const KParams& kp, const IO& io, double* S,
                                               int64_t b, [[maybe_unused]] const ObstIn ob = ObstIn(),
                                               [[maybe_unused]] const RateIn rt = RateIn()) {
+  constexpr bool kTask = PROBLEM != 3;  // the task data around the distance stage
   const int l = lane_id();
   const int nv = kp.nv;
   EpaPoly* ews = reinterpret_cast<EpaPoly*>(S + kp.kEpa);  // LDS-resident polytope
@@ -511,7 +521,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   // ---------------- state in ----------------
   double* qv = S + kp.kq;
   double* qd = S + kp.kqd;
-  if (l < nv) {
+  if (kTask && l < nv) {
     qv[l] = io.q[l * LD + gb];
     qd[l] = io.qdot[l * LD + gb];
   }
@@ -529,8 +539,8 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   for (int i = 0; i < 12; ++i) jpl[i] = M->jplace[jm][i];
   const V3 axl = ld3(M->axis[jm]);
   double tgt = 0.0;
-  if (PROBLEM == 2 && kp.cf == 3) {
-    // kinematics only (drc_kinematics_batch): no task targets
+  if (!kTask || (PROBLEM == 2 && kp.cf == 3)) {
+    // kinematics only (drc_kinematics_batch), the distance stage alone: no task targets
   } else if (l < 12) {
     if (kp.mode != DRC_MODE_QPIK) tgt = io.xt[l * LD + gb];
   } else if (l < 18) {
@@ -611,8 +621,8 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     wsync();
   }
   double* Te = S + kp.kTe;
-  if (l >= 1 && l <= nv) st3(Zw + 3 * l, rot(T + 12 * l, axl));
-  if (l == 0) tmul(T + 12 * kp.frame_joint, kp.frame_place, Te);
+  if (kTask && l >= 1 && l <= nv) st3(Zw + 3 * l, rot(T + 12 * l, axl));
+  if (kTask && l == 0) tmul(T + 12 * kp.frame_joint, kp.frame_place, Te);
   wsync();
   // geometry poses
   double* Tg = S + kp.kTg;
@@ -629,9 +639,10 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   PH(0);
   // ---------------- frame Jacobian (LWA), 6 x nv row-major -------------
   double* J = S + kp.kJ;
+  // (PROBLEM 3 never writes Te and uses neither pe nor anc_e: dead there, not inputs of the distance stage)
   const V3 pe = v3(Te[9], Te[10], Te[11]);
   const uint32_t anc_e = M->anc[kp.frame_joint];
-  if (l < nv) {
+  if (kTask && l < nv) {
     const int j = l + 1;
     V3 lin = v3(0, 0, 0), ang = v3(0, 0, 0);
     if (anc_e & (1u << l)) {
@@ -651,9 +662,9 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   double* xdd = S + kp.kxdd;
   // getVelocity = J qdot (robot_data.cpp:419-422), row r on lane r
   double jq = 0.0;
-  if (l < 6)
+  if (kTask && l < 6)
     for (int c = 0; c < nv; ++c) jq += J[l * nv + c] * qd[c];
-  if (l == 0) {
+  if (kTask && l == 0) {
     if (kp.mode == DRC_MODE_QPIK) {
       for (int i = 0; i < 6; ++i) xdd[i] = rd_lane(tgt, 12 + i);
     } else {
@@ -735,14 +746,14 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   const int narm = kp.narm, c0 = kp.c0;
   double* A6 = S + kp.kA6;
   double* Ai = S + kp.kAi;
-  if (l < 36) {
+  if (kTask && l < 36) {
     int a = l / 6, bb = l % 6;
     double s = 0;
     for (int c = 0; c < narm; ++c) s += J[a * nv + c0 + c] * J[bb * nv + c0 + c];
     A6[l] = s;
   }
   wsync();
-  {
+  if constexpr (kTask) {
     // JJ^T (SPD) inverted by six lane-parallel Jordan exchanges (36 lanes),
     // det = product of the pivots.  Ill-conditioned JJ^T (Frobenius
     // condition estimate >= 1e5) takes the serial COD path (rank by pivoted
@@ -792,7 +803,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     wsync();
   }
   double* W = S + kp.kW;  // narm x 6 = Jr^T Ai
-  for (int e = l; e < narm * 6; e += 64) {
+  for (int e = l; kTask && e < narm * 6; e += 64) {
     int c = e / 6, a = e % 6;
     double s = 0;
     for (int i = 0; i < 6; ++i) s += J[i * nv + c0 + c] * Ai[i * 6 + a];
@@ -801,7 +812,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   wsync();
   double* part = S + kp.kPart;
   const AncBits ancb = anc_bits(M);
-  for (int e = l; e < narm * narm; e += 64) {
+  for (int e = l; kTask && e < narm * narm; e += 64) {
     const int kk = e / narm, c = e % narm;
     const int jk = c0 + kk + 1, ji = c0 + c + 1;  // joint ids of q_k and column i
     double acc = 0;
@@ -829,7 +840,7 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
   }
   wsync();
   double* mg = S + kp.kmg;
-  if (l < narm) {
+  if (kTask && l < narm) {
     double s = 0;
     for (int c = 0; c < narm; ++c) s += part[l * narm + c];
     mg[l] = S[kp.oSc + SC_MAN] * s;
@@ -1174,9 +1185,13 @@ __device__ __forceinline__ void task_instance(const DevModel* __restrict__ M0, c
     S[kp.oSc + SC_PAIR] = besti;
   }
   wsync();
-  if constexpr (PROBLEM == 1) {
+  if constexpr (PROBLEM == 1 || PROBLEM == 3) {
     if (l == 0 && S[kp.oSc + SC_HOW] != 0) refine_winner();
     wsync();
+  }
+  if constexpr (PROBLEM == 3) {  // SC_DIST, SC_PAIR: the caller reads them (clearance_kernel.hip)
+    PH_FLUSH(0);
+    return;
   }
   bestd = S[kp.oSc + SC_DIST];
   PH(6);

@@ -370,6 +370,16 @@ class RobotData:
         return _batch.dynamics_batch(self.model, _batch.as_device(q, self.device),
                                      _batch.as_device(qdot, self.device), actuated=actuated, fields=fields)
 
+    def min_distance_path_batch(self, q_path, substeps=1, d_stop=None, obstacle_pose=None, dist_traj=False):
+        """Path clearance on device tensors: the minimum distance along the
+        joint-space paths ``q_path`` [waypoints][dof][B] (full joint vectors; the base yaw is
+        interpolated like any coordinate), each segment
+        walked in ``substeps`` steps, stopping at the first sample below
+        ``d_stop`` (None: never).  Returns a ``_batch.ClearanceResult``; see
+        _batch.clearance_path_batch."""
+        return _batch.clearance_path_batch(self.model, _batch.as_device(q_path, self.device), substeps=substeps,
+                                           d_stop=d_stop, obstacle_pose=obstacle_pose, dist_traj=dist_traj)
+
 
 class RobotController:
     """MobileManipulator::RobotController QPIK entries

@@ -669,6 +669,74 @@ int drc_qpik_reach_seeds_obstacles_batch(const drc_model* model, const drc_qpik_
  * is not finite and positive, out NULL. */
 int drc_reach_thresholds(double pos_tol, double rot_tol, double out[2]);
 
+/* ---- path clearance: the minimum distance along joint-space paths -----------
+ * Is the joint-space motion collision-free, and if not, where does it stop
+ * being so?  Each of the B instances is one path of `waypoints` full states
+ * (q_path [waypoints][dof][B], the layout of a rollout's q_traj, which can be
+ * passed straight in; dof is the full state: virtual joints and wheels
+ * included, the base yaw interpolated like any coordinate).  A segment between
+ * two waypoints is walked in `substeps` steps, N = (waypoints - 1) substeps + 1
+ * samples per path:
+ *   sample 0                waypoint 0
+ *   sample j substeps + i   1 <= i <= substeps, on segment j: waypoint j + 1
+ *                           itself for i == substeps, otherwise
+ *                           qa + t (qb - qa), t = double(i) / double(substeps),
+ *                           the difference, the product and the sum each
+ *                           rounded once: numpy's qa + (i / substeps) * (qb - qa).
+ * d_n, pair_n: the distance stage at sample n, bit for bit dist[0] and pair of
+ * drc_qpik_stages_batch at that state (the refined distance; hulls and
+ * obstacle slots included).  They depend on no drc_qpik_params field and not
+ * on qdot, so the entry takes neither.  The rule:
+ *   1. d_min = +inf, sample_min = pair_min = -1.
+ *   2. For n = 0 .. N - 1 in order:
+ *        d_n NaN:        result = DRC_CLEAR_INVALID, sample_stop = n, stop;
+ *        d_n < d_min:    (d_min, sample_min, pair_min) = (d_n, n, pair_n) -- strict:
+ *                        the lowest sample wins a tie;
+ *        d_n < d_stop:   result = DRC_CLEAR_BLOCKED, sample_stop = n, stop.
+ *   3. After the last sample: DRC_CLEAR_FREE, sample_stop = -1.
+ * d_stop = -INFINITY never blocks and gives the whole profile.  dist_traj
+ * [N][B] (may be NULL) receives d_n of the samples evaluated and is left
+ * untouched after a stop; the last clear sample is sample_stop - 1.  Samples
+ * past a stop are not evaluated: a path costs the samples it needs.
+ * One persistent kernel, one path per wave, for every model (no QP shape is
+ * involved); asynchronous on `stream`, no host synchronisation.
+ * DRC_ERR_INVALID_ARGUMENT: waypoints < 1, substeps < 1, d_stop NaN, N not
+ * below 2^31, B negative or above the work-queue limit, q_path or one of result
+ * / sample_stop / d_min / sample_min / pair_min NULL, a model with obstacle
+ * slots (drc_clearance_path_obstacles_batch takes their poses).  B = 0:
+ * DRC_OK, nothing is touched. */
+enum {
+    DRC_CLEAR_FREE = 0,          /* no sample below d_stop                              */
+    DRC_CLEAR_BLOCKED = 1,       /* sample_stop is the first sample with d < d_stop     */
+    DRC_CLEAR_INVALID = 2        /* the distance at sample_stop is NaN                  */
+};
+int drc_clearance_path_batch(const drc_model* model, int64_t B, int waypoints, int substeps,
+                             double d_stop, const double* q_path,
+                             int32_t* result, int32_t* sample_stop,
+                             double* d_min, int32_t* sample_min, int32_t* pair_min,
+                             double* dist_traj, void* stream);
+
+/* drc_clearance_path_batch on a model with obstacle slots.  The slots are
+ * static for the call: obstacle_pose [n][12][obstacle_ld], obstacle_ld = 0 one
+ * scene for every path, obstacle_ld >= B one scene per path (column b); in the
+ * world frame for mobile manipulators.  DRC_ERR_INVALID_ARGUMENT on a model
+ * without slots (drc_clearance_path_batch runs it). */
+int drc_clearance_path_obstacles_batch(const drc_model* model, int64_t B, int waypoints,
+                                       int substeps, double d_stop, const double* q_path,
+                                       const double* obstacle_pose, int64_t obstacle_ld,
+                                       int32_t* result, int32_t* sample_stop,
+                                       double* d_min, int32_t* sample_min, int32_t* pair_min,
+                                       double* dist_traj, void* stream);
+
+/* Host-buffer form of drc_clearance_path_batch: every array is a HOST array,
+ * staged in one round trip like drc_qpik_host.  dist_traj comes back whole: the
+ * entries past a stop hold what the caller's array held. */
+int drc_clearance_path_host(drc_model* model, int64_t B, int waypoints, int substeps,
+                            double d_stop, const double* q_path,
+                            int32_t* result, int32_t* sample_stop,
+                            double* d_min, int32_t* sample_min, int32_t* pair_min,
+                            double* dist_traj);
+
 /* Host-buffer forms of drc_qpik_batch / drc_qpik_stages_batch: same
  * arguments, but every array is a HOST array ([field][B], row stride B).  The
  * call stages them through model-owned device memory on an internal stream

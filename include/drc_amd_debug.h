@@ -102,6 +102,11 @@ int drc_debug_task_plan_wide(drc_model* model, int on);
 int drc_debug_qp_dense(drc_model* model, int on);
 int drc_debug_qp_dense_launches(drc_model* model, int64_t* count);
 
+/* The grid (waves) of the model's last drc_clearance_path_batch launch, 0
+ * before the first: min(B, DRC_GRID_CLEAR rounded down to a multiple of 8).
+ * What tests and tools/bench_clearance.py read to see the knob take effect. */
+int drc_debug_clearance_grid(drc_model* model, int64_t* grid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,9 +12,12 @@
 // and, on the stage builds alone,
 //   build has_mesh slots twists -> "build plain|mesh|obst|rate", or "build none"
 //   has family build            -> "has 0|1"
-// family: problem0 problem1 problem2 fused rollout reach reach_path reach_seeds.
+// and, on the path-clearance grid (clearance_grid),
+//   [grid_clear=value] clear B  -> "clear grid"
+// family: problem0 problem1 problem2 fused rollout reach reach_path reach_seeds
+// clearance.
 // Knobs: fuse_max, order_min, order_max, min_subbatch, grid_task, grid_qp,
-// grid_fused (default: PlanKnobs'), qp_group (64), max_cand (16) and twists (0:
+// grid_fused, grid_clear (default: PlanKnobs'), qp_group (64), max_cand (16) and twists (0:
 // the call carries obstacle twists).
 #include <iostream>
 #include <sstream>
@@ -26,8 +29,8 @@
 using namespace drc_amd;
 
 static const char* const kBuildName[kStageBuilds] = {"plain", "mesh", "obst", "rate"};
-static const char* const kFamilyName[kStageFamilies] = {"problem0", "problem1",   "problem2",   "fused",
-                                                        "rollout",  "reach",      "reach_path", "reach_seeds"};
+static const char* const kFamilyName[kStageFamilies] = {"problem0", "problem1",   "problem2",    "fused",    "rollout",
+                                                        "reach",    "reach_path", "reach_seeds", "clearance"};
 static int index_of(const char* const* names, int n, const std::string& s) {
   for (int i = 0; i < n; ++i)
     if (s == names[i]) return i;
@@ -52,6 +55,7 @@ static bool answer(const std::string& line, std::ostream& out) {
     else if (k == "grid_task") in.knobs.grid_task = v;
     else if (k == "grid_qp") in.knobs.grid_qp = v;
     else if (k == "grid_fused") in.knobs.grid_fused = v;
+    else if (k == "grid_clear") in.knobs.grid_clear = v;
     else if (k == "qp_group") in.qp_group = static_cast<int>(v);
     else if (k == "max_cand") in.max_cand_slots = static_cast<int>(v);
     else if (k == "twists") in.twists = v != 0;
@@ -68,6 +72,10 @@ static bool answer(const std::string& line, std::ostream& out) {
     const int f = index_of(kFamilyName, kStageFamilies, tok[a + 1]), b = index_of(kBuildName, kStageBuilds, tok[a + 2]);
     if (f < 0 || b < 0) return false;
     out << "has " << (has_build(static_cast<StageFamily>(f), static_cast<StageBuild>(b)) ? 1 : 0) << '\n';
+    return true;
+  }
+  if (a < tok.size() && tok[a] == "clear" && tok.size() == a + 2) {
+    out << "clear " << clearance_grid(std::stoll(tok[a + 1]), in.knobs) << '\n';
     return true;
   }
   if (tok.size() < a + 13) return false;
@@ -99,7 +107,7 @@ static bool answer(const std::string& line, std::ostream& out) {
     out << "sub " << s.b0 << ' ' << s.Bc << ' ' << s.xcd_map << ' ' << s.grid_task << ' ' << s.grid_qp << ' '
         << s.grid_fused << '\n';
   } else if (what == "pers" && family < 0 && v.size() == 15) {
-    for (int f = static_cast<int>(StageFamily::Rollout); f < kStageFamilies && family < 0; ++f)
+    for (int f = static_cast<int>(StageFamily::Rollout); f <= static_cast<int>(StageFamily::ReachSeeds) && family < 0; ++f)
       if (has_build(static_cast<StageFamily>(f), StageBuild::Mesh) == (v[13] != 0) &&
           has_build(static_cast<StageFamily>(f), StageBuild::Obst) == (v[14] != 0))
         family = f;
