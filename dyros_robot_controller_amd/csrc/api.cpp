@@ -909,6 +909,22 @@ static int stepwise_reach_init(hipStream_t st, int64_t B, int nv, const double* 
   return DRC_OK;
 }
 
+// Whether a reach entry of `family` runs its persistent kernel: the rollout's
+// rule, up to the largest batch at which the persistent kernel was measured to
+// beat the stepwise path -- every size measured, through 65 536: one waypoint
+// of 32 steps (FR3 556 against 1 674 ms, Husky-FR3 43.9 against 151.7 ms;
+// profiles/reach_bench.json, DESIGN.md "Reach"), 3 waypoints of 32 steps (FR3
+// 1 191 against 8 654 ms, Husky-FR3 129 against 570 ms) and four slots with
+// one waypoint (FR3 565 against 1 786 ms; profiles/reach_path_bench.json,
+// DESIGN.md "Reach paths").  Unlike a rollout's, a reach call's stepwise path
+// pays the horizon for every instance.  DRC_REACH_MAX overrides (read per
+// call, so that one process can measure both paths).  No persistent build has
+// the hull narrow phase
+static bool reach_persistent(const drc_model_impl* m, int64_t B, const KParams& kq, const StageIn& si,
+                             StageFamily family) {
+  return persistent_path(plan_in(m, B, 0, &kq, si), env_int("DRC_REACH_MAX", 65536, 0), family);
+}
+
 // drc_qpik_rollout_batch: `steps` control cycles (QPIK*, then the state
 // update) enqueued on the caller's stream.  The compiled QP shapes up to
 // rollout_max instances run the persistent kernel (rollout_kernel.hip: one
@@ -1008,20 +1024,110 @@ static int rollout(const drc_model_impl* cm, const drc_qpik_params* params, int6
   return L.done();
 }
 
+// The reach entries' core: the QPIKStep loop through W waypoints with
+// per-instance stopping (include/drc_amd.h), enqueued on the caller's stream;
+// drc_qpik_reach_batch is the path of one waypoint.  The caller holds
+// m->launch_mu and has made its entry's checks.  family: the entry's row of
+// has_build (call_plan.hpp).  The compiled QP shapes in a build that the
+// family has, up to reach_max instances, run the persistent kernel
+// (reach_path_kernel.hip, reach_path_obstacle_kernel.hip: a wave leaves an
+// instance when it stops and takes the next).  Everything else runs in rounds
+// of the stage launch at every instance's current target (stream scratch,
+// gathered by the update kernel when the instance advances), drc_qpik_batch's
+// launch sequence and the update kernel, which skips the instances that have
+// stopped.  That path cannot end early -- no host synchronisation, so the host
+// does not know who is still active -- and enqueues the most rounds an instance
+// can need.  An active instance has exactly one event per round, a step or an
+// advance to the next waypoint; it has at most W max_steps steps and W - 1
+// advances that do not finish it.  So one that is still active after
+// R0 = W max_steps + W - 1 rounds stands before waypoint W - 1 with its
+// segment's budget spent: its next verdict is REACHED or BUDGET, and no QP is
+// needed.  R0 rounds with a QP are enqueued, then one stage launch and update
+// that settle whoever is left.  Same device functions either way: identical
+// bits (tests/test_gpu_reach.py, tests/test_gpu_reach_path.py).
+// waypoints_reached: NULL for an entry without one (stream scratch holds it)
+static int reach_path_locked(drc_model_impl* m, const drc_qpik_params* params, StageFamily family, int64_t B, int W,
+                             int max_steps, double dt, double pos_tol, double rot_tol, const double* q0,
+                             const double* qdot0, const double* x_path, const double* xdot_path, double* qf,
+                             double* vf, int32_t* result, int32_t* waypoints_reached, int32_t* steps_used,
+                             int32_t* status_last, int32_t* iters_total, double* err_final, double* dist_final,
+                             double* dist_min, int32_t* steps_at, void* stream, const StageIn& si) {
+  KParams kt, kq;
+  if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
+  if (B == 0) return DRC_OK;
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  StreamCtx* const cx = L.cx;
+  const DevModel& dm = m->hm.dev;
+  const int nv = dm.nv, na = kq.na;
+  double tau[2];
+  reach_thresholds(pos_tol, rot_tol, tau);
+  const bool persistent = reach_persistent(m, B, kq, si, family);
+  ReachScratch sc;  // one step's eta, stage outputs, status and iters, the current targets, the segment counters
+  if (int r = L.carve(
+          &StreamCtx::roll,
+          [&](void* p) {
+            if (!waypoints_reached) return reach_scratch(p, na, nv, B, persistent);
+            return ReachScratch{reach_path_scratch(p, na, nv, B, persistent), nullptr};
+          },
+          &sc))
+    return r;
+  if (!waypoints_reached) waypoints_reached = sc.wp;
+  const ReachPathArgs rp{{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
+                          err_final, dist_final},
+                         W, x_path, xdot_path, waypoints_reached, dist_min, steps_at, sc.xt, sc.xdt, sc.seg};
+  if (persistent) {
+    IO io = task_io(B, q0, qdot0, x_path, xdot_path, nullptr, nullptr);
+    io.out = sc.eta;
+    io.status = sc.status;
+    io.iters = sc.iters;
+    unsigned grid;
+    if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
+    // The one family-specific step: the reach entry keeps its own kernel, the
+    // same loop without the waypoint advance: under this same host code
+    // reach_path_kernel with W = 1 measured 0.6 to 1.1 % slower on FR3
+    // (DESIGN.md "Reach entries unified")
+    if (family == StageFamily::Reach)
+      HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(grid, st, m->d_model, kt, kq, io, rp.re, si)));
+    else
+      HIP_TRY(static_cast<hipError_t>(launch_reach_path_kernel(grid, st, m->d_model, kt, kq, io, rp, si)));
+    return L.done();
+  }
+  // the finals carry the state from the start, every instance active at
+  // waypoint 0 with no step taken
+  if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, rp.re)) return r;
+  HIP_TRY(hipMemcpyAsync(sc.xt, x_path, size_t(12) * B * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(sc.xdt, xdot_path, size_t(6) * B * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemsetAsync(waypoints_reached, 0, size_t(B) * 4, st));
+  HIP_TRY(hipMemsetAsync(steps_used, 0, size_t(B) * 4, st));
+  HIP_TRY(hipMemsetAsync(sc.seg, 0, size_t(B) * 4, st));
+  if (steps_at) HIP_TRY(hipMemsetAsync(steps_at, 0xff, size_t(W) * B * 4, st));  // -1: never reached
+  const int64_t rounds = int64_t(W) * max_steps + W - 1;  // R0
+  IO qp = task_io(B, qf, vf, sc.xt, sc.xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
+  IO sg = qp;
+  sg.st_pose = sc.pose;
+  sg.st_dist = sc.dist;
+  qp.out = sc.eta;
+  qp.status = sc.status;
+  qp.iters = sc.iters;
+  for (int64_t r = 0; r <= rounds; ++r) {
+    const int last = r == rounds;
+    if (int rc = launch_locked(m, params, 1, sg, stream, si)) return rc;
+    if (!last)
+      if (int rc = launch_locked(m, params, 0, qp, stream, si)) return rc;
+    HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, sc.pose,
+                                                                    sc.dist, sc.eta, sc.status, sc.iters)));
+  }
+  return L.done();
+}
+
 static const char kSlotsReachMsg[] =
     "the model has obstacle slots: pass their poses through drc_qpik_reach_obstacles_batch";
 
-// drc_qpik_reach_batch: the QPIKStep loop towards x_target with per-instance
-// stopping (include/drc_amd.h), enqueued on the caller's stream.  The compiled
-// QP shapes without hulls or slots, up to reach_max instances, run the
-// persistent kernel (reach_kernel.hip: a wave leaves an instance when it stops
-// and takes the next).  Everything else runs step by step: the stage launch
-// (pose, d, grad d at the state), drc_qpik_batch's launch sequence and the
-// update kernel, which skips the instances that have stopped.  That path
-// cannot end early -- no host synchronisation, so the host does not know who
-// is still active: it enqueues max_steps steps, then one more stage launch
-// and update that settle the instances still active.  Same device functions
-// either way: identical bits (tests/test_gpu_reach.py).
+// drc_qpik_reach_batch: its own checks, then the core with x_target as a path
+// of one waypoint.  Its family is Reach, whose one build is the plain one: a
+// model with hulls or slots runs stepwise.
 // (reach_locked: the caller holds m->launch_mu -- reach() for one call,
 // reach_seeds() for its stepwise path)
 static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_t B, int max_steps, double dt,
@@ -1040,58 +1146,9 @@ static int reach_locked(drc_model_impl* m, const drc_qpik_params* params, int64_
   if (int rc = check_batch(B)) return rc;
   if (B > 0 && (!q0 || !qdot0 || !xt || !xdt))
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_target and xdot_target are required");
-  KParams kt, kq;
-  if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
-  if (B == 0) return DRC_OK;
-  Launch L(m, stream);
-  if (int r = L.begin()) return r;
-  hipStream_t st = L.st;
-  StreamCtx* const cx = L.cx;
-  const DevModel& dm = m->hm.dev;
-  const int nv = dm.nv, na = kq.na;
-  double tau[2];
-  reach_thresholds(pos_tol, rot_tol, tau);
-  // The rollout's rule, up to the largest batch at which the persistent kernel
-  // was measured to beat the stepwise path at 32 steps -- every size measured,
-  // through 65 536, for both kinds (FR3 556 against 1 674 ms, Husky-FR3 43.9
-  // against 151.7 ms; profiles/reach_bench.json, DESIGN.md "Reach"): unlike a
-  // rollout's, a reach call's stepwise path pays the horizon for every
-  // instance.  DRC_REACH_MAX overrides (read per call, so that one process can
-  // measure both paths).  No persistent build has the hull narrow phase or
-  // takes obstacle poses
-  const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(plan_in(m, B, 0, &kq, si), reach_max, StageFamily::Reach);
-  ReachScratch sc;  // one step's eta, stage outputs, status and iters
-  if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return reach_scratch(p, na, nv, B, persistent); }, &sc)) return r;
-  const ReachArgs re{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
-                     err_final, dist_final};
-  if (persistent) {
-    IO io = task_io(B, q0, qdot0, xt, xdt, nullptr, nullptr);
-    io.out = sc.eta;
-    io.status = sc.status;
-    io.iters = sc.iters;
-    unsigned grid;
-    if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
-    HIP_TRY(static_cast<hipError_t>(launch_reach_kernel(grid, st, m->d_model, kt, kq, io, re, si)));
-    return L.done();
-  }
-  if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, re)) return r;
-  IO qp = task_io(B, qf, vf, xt, xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
-  IO sg = qp;
-  sg.st_pose = sc.pose;
-  sg.st_dist = sc.dist;
-  qp.out = sc.eta;
-  qp.status = sc.status;
-  qp.iters = sc.iters;
-  for (int k = 0; k <= max_steps; ++k) {
-    const int last = k == max_steps;
-    if (int rc = launch_locked(m, params, 1, sg, stream, si)) return rc;
-    if (!last)
-      if (int rc = launch_locked(m, params, 0, qp, stream, si)) return rc;
-    HIP_TRY(static_cast<hipError_t>(launch_reach_update_kernel(B, st, m->d_model, k, last, re, xt, sc.pose, sc.dist,
-                                                               sc.eta, sc.status, sc.iters)));
-  }
-  return L.done();
+  return reach_path_locked(m, params, StageFamily::Reach, B, 1, max_steps, dt, pos_tol, rot_tol, q0, qdot0, xt, xdt, qf,
+                           vf, result, nullptr, steps_used, status_last, iters_total, err_final, dist_final, nullptr,
+                           nullptr, stream, si);
 }
 
 static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int max_steps, double dt,
@@ -1109,18 +1166,9 @@ static int reach(const drc_model_impl* cm, const drc_qpik_params* params, int64_
 static const char kSlotsReachPathMsg[] =
     "the model has obstacle slots: pass their poses through drc_qpik_reach_path_obstacles_batch";
 
-// drc_qpik_reach_path_batch: the loop of reach() through W waypoints
-// (include/drc_amd.h), enqueued on the caller's stream.  The compiled QP
-// shapes without hulls, up to reach_max instances, run the persistent kernel
-// (reach_path_kernel.hip); models with obstacle slots too, through its ObstIn
-// builds (reach_path_obstacle_kernel.hip).  Everything else runs in rounds of
-// the stage launch at every instance's current target (stream scratch, gathered
-// by the update kernel when the instance advances), drc_qpik_batch's launch
-// sequence and the update kernel.  An active instance steps or advances in
-// every round, at most W max_steps + W - 1 times, so W (max_steps + 1) rounds
-// stop every instance; one more stage launch and update without a QP settle
-// whatever is left.  Same device functions either way: identical bits
-// (tests/test_gpu_reach_path.py).
+// drc_qpik_reach_path_batch: its own checks, then the core.  Its family has
+// the builds that take the slots' poses, so models with slots run the
+// persistent kernel too
 static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int W, int max_steps,
                       double dt, double pos_tol, double rot_tol, const double* q0, const double* qdot0,
                       const double* x_path, const double* xdot_path, double* qf, double* vf, int32_t* result,
@@ -1145,66 +1193,9 @@ static int reach_path(const drc_model_impl* cm, const drc_qpik_params* params, i
   if (int rc = check_batch(B)) return rc;
   if (B > 0 && (!q0 || !qdot0 || !x_path || !xdot_path))
     return set_err(DRC_ERR_INVALID_ARGUMENT, "q0, qdot0, x_path and xdot_path are required");
-  KParams kt, kq;
-  if (int rc = make_kparams_pair(m, params, &kt, &kq)) return rc;
-  if (B == 0) return DRC_OK;
-  Launch L(m, stream);
-  if (int r = L.begin()) return r;
-  hipStream_t st = L.st;
-  StreamCtx* const cx = L.cx;
-  const DevModel& dm = m->hm.dev;
-  const int nv = dm.nv, na = kq.na;
-  double tau[2];
-  reach_thresholds(pos_tol, rot_tol, tau);
-  // reach()'s rule and its DRC_REACH_MAX (read per call), with the slots let in:
-  // the persistent kernel has builds that take their poses.  The default stays
-  // 65 536: the persistent kernel beat the stepwise path at every size measured
-  // through it, with 3 waypoints of 32 steps (FR3 1 191 against 8 654 ms,
-  // Husky-FR3 129 against 570 ms) and with four slots and one waypoint (FR3 565
-  // against 1 786 ms; profiles/reach_path_bench.json, DESIGN.md "Reach paths")
-  const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(plan_in(m, B, 0, &kq, si), reach_max, StageFamily::ReachPath);
-  ReachPathScratch sc;  // reach's, the current targets and the segment counters
-  if (int r = L.carve(&StreamCtx::roll, [&](void* p) { return reach_path_scratch(p, na, nv, B, persistent); }, &sc))
-    return r;
-  const ReachPathArgs rp{{max_steps, dt, tau[0], tau[1], qf, vf, result, steps_used, status_last, iters_total,
-                          err_final, dist_final},
-                         W, x_path, xdot_path, waypoints_reached, dist_min, steps_at, sc.xt, sc.xdt, sc.seg};
-  if (persistent) {
-    IO io = task_io(B, q0, qdot0, x_path, xdot_path, nullptr, nullptr);
-    io.out = sc.eta;
-    io.status = sc.status;
-    io.iters = sc.iters;
-    unsigned grid;
-    if (int r = persistent_setup(cx, st, &kt, &kq, &io, &grid)) return r;
-    HIP_TRY(static_cast<hipError_t>(launch_reach_path_kernel(grid, st, m->d_model, kt, kq, io, rp, si)));
-    return L.done();
-  }
-  // reach()'s start, at waypoint 0 with no step taken
-  if (int r = stepwise_reach_init(st, B, nv, q0, qdot0, rp.re)) return r;
-  HIP_TRY(hipMemcpyAsync(sc.xt, x_path, size_t(12) * B * 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(sc.xdt, xdot_path, size_t(6) * B * 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemsetAsync(waypoints_reached, 0, size_t(B) * 4, st));
-  HIP_TRY(hipMemsetAsync(steps_used, 0, size_t(B) * 4, st));
-  HIP_TRY(hipMemsetAsync(sc.seg, 0, size_t(B) * 4, st));
-  if (steps_at) HIP_TRY(hipMemsetAsync(steps_at, 0xff, size_t(W) * B * 4, st));  // -1: never reached
-  const int64_t rounds = int64_t(W) * (int64_t(max_steps) + 1);
-  IO qp = task_io(B, qf, vf, sc.xt, sc.xdt, nullptr, nullptr);  // a step's QPIK call on the finals, and its stage launch
-  IO sg = qp;
-  sg.st_pose = sc.pose;
-  sg.st_dist = sc.dist;
-  qp.out = sc.eta;
-  qp.status = sc.status;
-  qp.iters = sc.iters;
-  for (int64_t r = 0; r <= rounds; ++r) {
-    const int last = r == rounds;
-    if (int rc = launch_locked(m, params, 1, sg, stream, si)) return rc;
-    if (!last)
-      if (int rc = launch_locked(m, params, 0, qp, stream, si)) return rc;
-    HIP_TRY(static_cast<hipError_t>(launch_reach_path_update_kernel(B, st, m->d_model, r == 0, last, rp, sc.pose,
-                                                                    sc.dist, sc.eta, sc.status, sc.iters)));
-  }
-  return L.done();
+  return reach_path_locked(m, params, StageFamily::ReachPath, B, W, max_steps, dt, pos_tol, rot_tol, q0, qdot0, x_path,
+                           xdot_path, qf, vf, result, waypoints_reached, steps_used, status_last, iters_total,
+                           err_final, dist_final, dist_min, steps_at, stream, si);
 }
 
 static const char kSlotsReachSeedsMsg[] =
@@ -1265,8 +1256,7 @@ static int reach_seeds(const drc_model_impl* cm, const drc_qpik_params* params, 
   const int64_t B = T * S;
   double tau[2];
   reach_thresholds(pos_tol, rot_tol, tau);
-  const int64_t reach_max = env_int("DRC_REACH_MAX", 65536, 0);
-  const bool persistent = persistent_path(plan_in(m, B, 0, &kq, si), reach_max, StageFamily::ReachSeeds);
+  const bool persistent = reach_persistent(m, B, kq, si, StageFamily::ReachSeeds);
   const bool ob_expand = si.ob.ld != 0;
   // the expanded targets and poses, the instances' finals and outcomes, one step's scratch, the groups' words
   SeedsScratch sc;

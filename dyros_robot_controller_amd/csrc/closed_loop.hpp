@@ -1,6 +1,6 @@
 // The parts of a closed-loop step that the persistent kernels reach_kernel and
 // reach_seeds_kernel and the stepwise path's update kernels
-// (rollout_integrate_kernel, reach_update_kernel, reach_path_update_kernel)
+// (rollout_integrate_kernel, reach_path_update_kernel)
 // have in common, as plain functions: every kernel
 // keeps its own step loop -- stage, verdict, QP, status, update -- with its stop
 // rules in place, and calls these for the blocks that are the same everywhere.

@@ -93,7 +93,8 @@ int launch_rollout_kernel(unsigned grid, hipStream_t st, const DevModel* m, cons
 int launch_rollout_integrate_kernel(int64_t B, hipStream_t st, const DevModel* m, double dt, const double* q_in,
                                     const double* eta, double* qf, double* vf, double* q_traj);
 
-// drc_qpik_reach_batch (reach_kernel.hip): what its kernels need beyond IO.
+// The reach entries (drc_qpik_reach_batch and its kin; reach_path.hpp and
+// reach_seeds.hpp have the others' launchers): what their kernels need beyond IO.
 // tau_p, tau_r: the thresholds of reach.hpp; qf / vf [dof][B] hold the state;
 // result / steps_used [B]; status_last, iters_total [B], err_final [2][B] and
 // dist_final [1+dof][B] may be NULL
@@ -106,17 +107,15 @@ struct ReachArgs {
 };
 // `result` of an instance that has not stopped yet (stepwise path; every byte 0xff)
 constexpr int32_t kReachActive = -1;
-// persistent reach kernel (compiled QPIK shapes in the Plain build -- no hulls,
-// no obstacle slots -- hipErrorInvalidValue otherwise): per instance task stage, verdict, QP
-// and state update until it stops.  io as for launch_fused_kernel, with out /
+// drc_qpik_reach_batch's persistent kernel (reach_kernel.hip; compiled QPIK
+// shapes in the Plain build -- no hulls, no obstacle slots --
+// hipErrorInvalidValue otherwise): per instance task stage, verdict, QP and
+// state update until it stops.  io as for launch_fused_kernel, with out /
 // status / iters one step's scratch (all three required) and xt the target.
 // The LDS size follows from kt and kq
 int launch_reach_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
                         const IO& io, const ReachArgs& re, const StageIn& si);
-// step k of the stepwise path: the verdict of every instance still active from
-// the stage outputs pose [12][B] / dist [1+dof][B] at the state in re.qf /
-// re.vf, then (last = 0) the step's status and the state update from eta
-// [na][B]; last = 1: k = max_steps, no QP ran (eta, status, iters unused)
+// (not called any more: reach_kernel.hip says why reach_update_kernel is still in its unit)
 int launch_reach_update_kernel(int64_t B, hipStream_t st, const DevModel* m, int k, int last, const ReachArgs& re,
                                const double* xt, const double* pose, const double* dist, const double* eta,
                                const int32_t* status, const int32_t* iters);

@@ -7,7 +7,8 @@
 // so "within pos_tol metres and rot_tol radians" is e_p <= pos_tol^2 and
 // e_R <= 8 sin^2(rot_tol / 2) without a square root, an acos or a logarithm of
 // a rotation.  Both sums are formed in a fixed order with contraction off, so
-// the persistent kernel, the stepwise path's update kernel (reach_kernel.hip),
+// the persistent kernels (reach_kernel.hip, reach_path_kernel.hip), the
+// stepwise path's update kernel (reach_path_kernel.hip),
 // the host compiler (tools/reach_host_test.cpp, tests/test_reach_host.py) and
 // numpy on the same doubles give the same bits.
 //

@@ -1,27 +1,30 @@
-// Goal-reaching rollouts with per-instance stopping (drc_qpik_reach_batch):
-// the closed loop of drc_qpik_rollout_batch in mode QPIKStep, where every
-// instance stops on its own -- the pose is within the tolerances of the target
-// (reach.hpp), the step budget is spent, or its QP is not solved (eta = 0: it
-// would stay where it is for the rest of a fixed horizon).  Reference: no
-// counterpart.
+// drc_qpik_reach_batch's persistent kernel.  The entry runs as a reach path of
+// one waypoint (api.cpp reach_path_locked; reach_path_kernel.hip has the loop's
+// description and the stepwise path's update kernel) and keeps this kernel for
+// its persistent launch: with W = 1 reach_path_kernel makes the same stops in
+// the same order from the same values, but under the same host code it
+// measured 0.6 to 1.1 % slower on FR3 (DESIGN.md "Reach entries unified").
 //
-// reach_kernel: the persistent form for the compiled QP shapes: one instance
-// per wave from the work queue, the task record in LDS, the state in the
-// caller's q_final / qdot_final arrays.  The verdict is wave-uniform, so the
-// three stops are uniform branches that leave the step loop, and the wave takes
-// the next instance from the queue: an instance costs the steps it needs, not
-// the horizon.  Its own here: the step loop with the three stops; the blocks
-// between them -- LDS views, the stores at the state, status read-back, state
-// update, epilogue -- are closed_loop.hpp's, which reach_seeds_kernel calls too
-// (rollout_kernel and reach_path_kernel keep the same blocks as their own text;
-// only their update kernels and launchers use the header).
+// reach_kernel: one instance per wave from the work queue, the task record in
+// LDS, the state in the caller's q_final / qdot_final arrays.  The verdict is
+// wave-uniform, so the three stops are uniform branches that leave the step
+// loop, and the wave takes the next instance from the queue: an instance costs
+// the steps it needs, not the horizon.  Its own here: the step loop with the
+// three stops; the blocks between them -- LDS views, the stores at the state,
+// status read-back, state update, epilogue -- are closed_loop.hpp's, which
+// reach_seeds_kernel calls too (rollout_kernel and reach_path_kernel keep the
+// same blocks as their own text).  The same functions of closed_loop.hpp as
+// reach_path_update_kernel (reach.hpp's and rollout_update.hpp's arithmetic)
+// on the same values, so the two paths return identical bits
+// (tests/test_gpu_reach.py).
 //
-// reach_update_kernel: verdict and state update alone, one thread per
-// instance, for the stepwise path (api.cpp: the stage launch and
-// drc_qpik_batch's launch sequence per step, then this kernel).  Both forms
-// go through the same functions of closed_loop.hpp (reach.hpp's and
-// rollout_update.hpp's arithmetic) on the same values, so the two paths return
-// identical bits (tests/test_gpu_reach.py).
+// reach_update_kernel: the stepwise update of one target, which nothing
+// launches any more (reach_path_update_kernel with W = 1 took its place).  Its
+// text stays for one measured reason: without it every function of this unit
+// moves up in the code object, and reach_kernel, its instructions unchanged,
+// ran 0.4 to 1.0 % slower on FR3; aligning the kernels to 1 or 4 KiB did not
+// bring it back (DESIGN.md "Reach entries unified").  It goes with
+// reach_kernel, or once the placement is understood.
 #include "task_stage.hpp"
 #include "qp_solver.hpp"
 #include "closed_loop.hpp"

@@ -27,8 +27,10 @@ struct ReachPathArgs {
 
 // persistent kernel (compiled QPIK shapes in the Plain and Obst builds,
 // hipErrorInvalidValue otherwise): per instance task stage, verdict / waypoint
-// advance, QP and state update until it stops.  io as for launch_reach_kernel,
-// its xt / xdt unused (the kernel points them at the current waypoint's block)
+// advance, QP and state update until it stops.  io as for launch_fused_kernel,
+// with out / status / iters one step's scratch (all three required); its xt /
+// xdt unused (the kernel points them at the current waypoint's block).  The
+// LDS size follows from kt and kq
 int launch_reach_path_kernel(unsigned grid, hipStream_t st, const DevModel* m, const KParams& kt, const KParams& kq,
                              const IO& io, const ReachPathArgs& rp, const StageIn& si);
 // one round of the stepwise path: verdict, waypoint advance (gathering the new

@@ -1,10 +1,14 @@
-// Goal-reaching rollouts through waypoints (drc_qpik_reach_path_batch): the
-// loop of drc_qpik_reach_batch (reach_kernel.hip) towards waypoint w of x_path
-// [W][12][B], where an instance that comes within the tolerances of waypoint w
-// goes on to waypoint w + 1 from the same state, with a fresh step budget, and
-// stops once it has passed the last one.  Bit for bit W chained
-// drc_qpik_reach_batch calls, without the call boundaries: a wave leaves an
-// instance the moment it stops.  Reference: no counterpart.
+// Goal-reaching rollouts with per-instance stopping, through waypoints
+// (drc_qpik_reach_path_batch; drc_qpik_reach_batch is the path of one
+// waypoint): the closed loop of drc_qpik_rollout_batch in mode QPIKStep
+// towards waypoint w of x_path [W][12][B], where every instance stops on its
+// own -- the step budget of the segment is spent, or its QP is not solved
+// (eta = 0: it would stay where it is) -- and an instance that comes within
+// the tolerances of waypoint w (reach.hpp) goes on to waypoint w + 1 from the
+// same state, with a fresh step budget, and stops once it has passed the last
+// one.  Bit for bit W chained drc_qpik_reach_batch calls, without the call
+// boundaries: a wave leaves an instance the moment it stops.  Reference: no
+// counterpart.
 //
 // reach_path_kernel: the persistent form for the compiled QP shapes: one
 // instance per wave from the work queue, the task record in LDS, the state in
@@ -77,7 +81,8 @@ reach_path_kernel(const DevModel* __restrict__ M0, const KParams kt, const KPara
         const double d = iol.rec[kt.rDist];  // (a NaN is never taken)
         if (d < dmin) dmin = d;
       }
-      // the pose at q_k from the task plan (reach_kernel) against waypoint w and,
+      // the pose at q_k from the task plan (the pure copies of the stage entry's
+      // pose output) against waypoint w and,
       // while it is within, against the next ones: every lane forms the same
       // numbers.  The record was formed against the waypoint the stage started
       // with, so an advance runs the stage again before the QP reads it
@@ -210,9 +215,10 @@ int launch_reach_path_kernel(unsigned grid, hipStream_t st, const DevModel* m, c
 // passing the last waypoint, it gathers waypoint w's target into cur_xt /
 // cur_xdt and ignores the round's QP, which was formed against the old one.
 // Otherwise, unless it stops, it takes the update from the round's eta /
-// status / iters.  last: no QP ran (by then every instance has stopped: an
-// active instance steps or advances in every round, at most W max_steps + W - 1
-// times).  The state is updated in place as in reach_update_kernel.
+// status / iters.  last: no QP ran (an instance still active by then has used
+// its W max_steps steps and W - 1 advances, one per round: it stands before the
+// last waypoint with seg == max_steps, and its verdict is REACHED or BUDGET).
+// The state is updated in place (thread_state_update).
 __global__ void __launch_bounds__(256)
 reach_path_update_kernel(const DevModel* __restrict__ M, int64_t B, int first, int last, const ReachPathArgs rp,
                          const double* pose, const double* dist, const double* eta, const int32_t* status,

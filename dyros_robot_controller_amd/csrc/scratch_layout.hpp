@@ -132,36 +132,16 @@ inline RolloutScratch rollout_scratch(void* base, int na, int64_t B, bool qdot_t
   return L;
 }
 
-// roll, drc_qpik_reach_batch: one step's eta [na][B], then (stepwise) the
-// stage outputs pose [12][B] and dist [1+nv][B], then status [B] and iters [B]
-struct ReachScratch {
-  double *eta, *pose, *dist;
-  int32_t *status, *iters;
-  int64_t bytes;
-};
-inline ReachScratch reach_scratch(void* base, int na, int nv, int64_t B, bool persistent, RegionLog* log = nullptr) {
-  Carver c{static_cast<char*>(base), log};
-  ReachScratch L;
-  L.eta = c.take<double>("eta", int64_t(na) * B);
-  L.pose = c.take<double>("pose", persistent ? 0 : 12 * B);
-  L.dist = c.take<double>("dist", persistent ? 0 : int64_t(1 + nv) * B);
-  L.status = c.take<int32_t>("status", B);
-  L.iters = c.take<int32_t>("iters", B);
-  L.bytes = c.off;
-  return L;
-}
-
-// roll, drc_qpik_reach_path_batch: reach's, with (stepwise) the current
-// targets [12][B], [6][B] after dist and the segment counters [B] at the end
+// roll, drc_qpik_reach_path_batch: one step's eta [na][B], then (stepwise) the
+// stage outputs pose [12][B] and dist [1+nv][B] and the current targets
+// [12][B], [6][B], then status [B], iters [B] and the segment counters [B]
 struct ReachPathScratch {
   double *eta, *pose, *dist, *xt, *xdt;
   int32_t *status, *iters, *seg;
   int64_t bytes;
 };
-inline ReachPathScratch reach_path_scratch(void* base, int na, int nv, int64_t B, bool persistent,
-                                           RegionLog* log = nullptr) {
-  Carver c{static_cast<char*>(base), log};
-  ReachPathScratch L;
+// (the regions, for the two layouts that hold them)
+inline void take_reach_path(Carver& c, ReachPathScratch& L, int na, int nv, int64_t B, bool persistent) {
   L.eta = c.take<double>("eta", int64_t(na) * B);
   L.pose = c.take<double>("pose", persistent ? 0 : 12 * B);
   L.dist = c.take<double>("dist", persistent ? 0 : int64_t(1 + nv) * B);
@@ -170,6 +150,26 @@ inline ReachPathScratch reach_path_scratch(void* base, int na, int nv, int64_t B
   L.status = c.take<int32_t>("status", B);
   L.iters = c.take<int32_t>("iters", B);
   L.seg = c.take<int32_t>("seg", B);
+  L.bytes = c.off;
+}
+inline ReachPathScratch reach_path_scratch(void* base, int na, int nv, int64_t B, bool persistent,
+                                           RegionLog* log = nullptr) {
+  Carver c{static_cast<char*>(base), log};
+  ReachPathScratch L;
+  take_reach_path(c, L, na, nv, B, persistent);
+  return L;
+}
+
+// roll, drc_qpik_reach_batch, a reach path of one waypoint: reach path's, then
+// wp [B], the waypoints_reached that the reach entry's caller does not have
+struct ReachScratch : ReachPathScratch {
+  int32_t* wp;
+};
+inline ReachScratch reach_scratch(void* base, int na, int nv, int64_t B, bool persistent, RegionLog* log = nullptr) {
+  Carver c{static_cast<char*>(base), log};
+  ReachScratch L;
+  take_reach_path(c, L, na, nv, B, persistent);
+  L.wp = c.take<int32_t>("wp", B);
   L.bytes = c.off;
   return L;
 }

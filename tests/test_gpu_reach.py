@@ -9,7 +9,8 @@ state update, whose finals are taken for the instances still active.  Every
 field of the ReachResult must equal it (test 1; with obstacle slots 4; a hull
 model, which runs step by step, 5), and the persistent kernel
 (reach_kernel.hip), the stepwise path (drc_set_fusion 0) and every batch size
-return the same bits (test 3).
+return the same bits (test 3).  The entry's host side is the reach path's with
+one waypoint (test 8).
 
 Census inputs: instance i draws from numpy.random.default_rng(i) a start in
 the middle 40 % of the position limits (clipped to +-3) and a goal within 0.15
@@ -408,3 +409,21 @@ def test_controller_entry(cuda, robot):
     assert (res.REACHED, res.BUDGET, res.QP_FAILED) == (0, 1, 2)
     assert res.thresholds == RC.thresholds(POS_TOL, ROT_TOL)
     _assert_same(_np(res), _reach(S))
+
+
+# 8 ------------------------------------------------------------------------
+@pytest.mark.parametrize("robot", ["fr3", "husky_fr3"])
+def test_is_a_reach_path_of_one_waypoint(cuda, robot):
+    """drc_qpik_reach_batch hands its arguments to the reach-path code with
+    W = 1: every field the two results share, bit for bit, on both dispatch
+    paths."""
+    S = _setup(robot, cuda, 70)
+    a = lambda t: _batch.as_device(np.array(t), cuda)
+    try:
+        for fused in (1, 0):
+            _set_fusion(S, fused)
+            path = _batch.qpik_reach_path_batch(S["rd"].model, S["p"], a(S["q"]), a(S["v"]), a(S["xt"][None]),
+                                                a(S["xdt"][None]), MAX_STEPS, S["dt"], POS_TOL, ROT_TOL)
+            _assert_same(_reach(S), _np(path), msg="fused=%d" % fused)
+    finally:
+        _set_fusion(S, 1)

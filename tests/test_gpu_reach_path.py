@@ -298,6 +298,52 @@ def test_path_and_batch_size_independence(cuda, robot):
         assert (r["waypoints_reached"] > 1).any() and (r["steps_used"] > K).any()
 
 
+def test_the_last_round_settles_the_worst_case(cuda):
+    """The stepwise path enqueues R0 = W max_steps + W - 1 rounds with a QP and
+    one that settles (api.cpp reach_path_locked).  W = 2, max_steps = 1: an
+    instance that steps (round 0), comes within waypoint 0 (round 1), steps
+    towards waypoint 1 (round 2) and is out of budget uses all R0 = 3 rounds, one
+    event in each, and takes its verdict from the settling round."""
+    B, W = 4, 2
+    S = TR._setup("fr3", cuda, 70)
+    q, v, xt, xdt = (np.ascontiguousarray(S[k][:, :B]) for k in ("q", "v", "xt", "xdt"))
+    # every instance's errors at the start and after one step towards its census target
+    e0 = TR._reach(S, q=q, v=v, xt=xt, xdt=xdt, max_steps=0)["err_final"]
+    e1 = TR._reach(S, q=q, v=v, xt=xt, xdt=xdt, max_steps=1)["err_final"]
+    fell = np.all(e1 < e0, axis=0)
+    # one tolerance pair with the start outside and the state after one step inside: the pair between the two
+    # states of an instance (geometric means of its errors), that of the instance it separates the most for
+    best, tol = np.zeros(B, bool), None
+    for i in np.flatnonzero(fell):
+        pos_tol = float(np.sqrt(np.sqrt(e0[0, i] * e1[0, i])))
+        rot_tol = float(2.0 * np.arcsin(np.sqrt(np.sqrt(e0[1, i] * e1[1, i]) / 8.0)))
+        tau_p, tau_r = RC.thresholds(pos_tol, rot_tol)
+        sep = fell & ~((e0[0] <= tau_p) & (e0[1] <= tau_r)) & (e1[0] <= tau_p) & (e1[1] <= tau_r)
+        if sep.sum() > best.sum():
+            best, tol = sep, (pos_tol, rot_tol)
+    print("errors at the start %s, after one step %s, separated %s by %s" % (e0.tolist(), e1.tolist(), best, tol))
+    assert best.any()
+    xp = np.stack([xt, xt])
+    xp[1][11] -= 5.0   # five metres below the floor
+    xdp = np.zeros((W, 6, B))
+    a = lambda t: _batch.as_device(np.array(t), cuda)
+    got = {}
+    try:
+        for fused in (1, 0):
+            TR._set_fusion(S, fused)
+            got[fused] = _np(_batch.qpik_reach_path_batch(S["rd"].model, S["p"], a(q), a(v), a(xp), a(xdp), 1, S["dt"],
+                                                          *tol))
+    finally:
+        TR._set_fusion(S, 1)
+    r = got[0]
+    assert set(np.unique(r["result"])) <= {RC.REACHED, RC.BUDGET, RC.QP_FAILED}, r["result"]   # none left at -1
+    np.testing.assert_array_equal(r["waypoints_reached"][best], 1)
+    np.testing.assert_array_equal(r["steps_used"][best], 2)
+    np.testing.assert_array_equal(r["result"][best], RC.BUDGET)
+    np.testing.assert_array_equal(r["steps_at"][:, best], np.repeat([[1], [-1]], best.sum(), axis=1))
+    _assert_same(r, got[1])
+
+
 # 4 ------------------------------------------------------------------------
 def _fr3_obstacles(cuda):
     if "obst" not in _PATHS:

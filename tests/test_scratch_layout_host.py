@@ -15,7 +15,10 @@ The byte count and every offset of the whole grid are pinned in
 tests/golden/scratch_layout_parent.txt, recorded from the size formulas and
 address expressions that api.cpp spelled out per launch path before the
 layouts had a header: `WHAT | bytes | offset ...`, -1 where no address is
-formed."""
+formed.  The reach layout is no row of that file: it is the reach-path layout
+followed by wp [B] int32 (drc_qpik_reach_batch runs as a reach path of one
+waypoint), and test_reach_is_reach_path_then_wp holds every reach case to the
+pinned reach_path case of the same nv, na, B and persistent."""
 import itertools
 import os
 import shutil
@@ -91,9 +94,7 @@ def off_regions(c):
         return {"rec", "M", "g", "g_joint"} if p["stages"] else on(["g_joint"], not p["whole_body"])
     if k == "rollout":
         return on(["eta"], p["qdot_traj"])
-    if k == "reach":
-        return on(["pose", "dist"], p["persistent"])
-    if k == "reach_path":
+    if k in ("reach", "reach_path"):
         return on(["pose", "dist", "xt", "xdt"], p["persistent"])
     if k == "seeds":
         return on(["eta"], not p["persistent"]) | on(["pose"], not (p["ob_expand"] and p["nobst"]))
@@ -125,7 +126,21 @@ def test_rules(cases):
 def test_offsets_and_sizes_unchanged(cases):
     with open(GOLDEN) as fh:
         want = [ln.rstrip("\n") for ln in fh if not ln.startswith("#")]
-    got = ["%s | %d | %s" % (c["what"], c["bytes"], " ".join(str(r[4]) for r in c["regions"])) for c in cases]
+    got = ["%s | %d | %s" % (c["what"], c["bytes"], " ".join(str(r[4]) for r in c["regions"])) for c in cases
+           if c["layout"] != "reach"]
     assert len(got) == len(want)
     for g, w in zip(got, want):
         assert g == w
+
+
+def test_reach_is_reach_path_then_wp(cases):
+    key = lambda c: tuple(sorted(c["par"].items()))
+    path = {key(c): c for c in cases if c["layout"] == "reach_path"}
+    reach = [c for c in cases if c["layout"] == "reach"]
+    assert len(reach) == len(path) > 0
+    for c in reach:
+        p = path[key(c)]                          # (pinned by test_offsets_and_sizes_unchanged)
+        B = c["par"]["B"]
+        assert c["regions"][:-1] == p["regions"], c["what"]
+        assert c["regions"][-1] == ("wp", 4, p["bytes"], B, p["bytes"]), c["what"]
+        assert c["bytes"] == p["bytes"] + 4 * B, c["what"]

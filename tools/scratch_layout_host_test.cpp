@@ -23,8 +23,8 @@ template <class V> void visit(const QpidPool& L, V& v) { v("rec", L.rec), v("M",
 template <class V> void visit(const OsfPool& L, V& v) { v("Minv", L.Minv), v("g", L.g); }
 template <class V> void visit(const DynList& L, V& v) { v("list", L.list); }
 template <class V> void visit(const RolloutScratch& L, V& v) { v("eta", L.eta); }
-template <class V> void visit(const ReachScratch& L, V& v) { v("eta", L.eta), v("pose", L.pose), v("dist", L.dist), v("status", L.status), v("iters", L.iters); }
 template <class V> void visit(const ReachPathScratch& L, V& v) { v("eta", L.eta), v("pose", L.pose), v("dist", L.dist), v("xt", L.xt), v("xdt", L.xdt), v("status", L.status), v("iters", L.iters), v("seg", L.seg); }
+template <class V> void visit(const ReachScratch& L, V& v) { visit(static_cast<const ReachPathScratch&>(L), v), v("wp", L.wp); }
 template <class V> void visit(const SeedsScratch& L, V& v) {
   v("xt", L.xt), v("xdt", L.xdt), v("qf", L.qf), v("vf", L.vf), v("err", L.err), v("dist", L.dist), v("pose", L.pose), v("eta", L.eta);
   v("result", L.result), v("steps", L.steps), v("status_last", L.status_last), v("iters_total", L.iters_total);
