@@ -24,7 +24,7 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -ff
 # (and of the toolchain: the same sources built by another hipcc / ROCm are another build)
 BUILD_ID=$(cat $CSRC/*.hip $CSRC/*.hpp $CSRC/*.cpp include/drc_amd.h include/drc_amd_debug.h build.sh | { cat; echo "$FLAGS"; $HIPCC --version 2>&1; } | sha256sum | cut -c1-16)
 pids=()
-for src in task_kernel.hip task_obstacle_kernel.hip task_rate_kernel.hip fused_rate_kernel.hip qp_kernel.hip qp_dense_kernel.hip fused_kernel.hip fused_mesh_kernel.hip fused_obstacle_kernel.hip rollout_kernel.hip rollout_mesh_kernel.hip reach_kernel.hip reach_path_kernel.hip reach_path_obstacle_kernel.hip reach_seeds_kernel.hip reach_seeds_obstacle_kernel.hip clearance_kernel.hip clearance_mesh_kernel.hip clearance_obstacle_kernel.hip qpid_kernel.hip dynamics.hip order_kernel.hip api.cpp model.cpp mesh.cpp; do
+for src in task_kernel.hip task_obstacle_kernel.hip task_rate_kernel.hip fused_rate_kernel.hip qp_kernel.hip qp_dense_kernel.hip fused_kernel.hip fused_mesh_kernel.hip fused_obstacle_kernel.hip rollout_kernel.hip rollout_mesh_kernel.hip reach_kernel.hip reach_path_kernel.hip reach_path_obstacle_kernel.hip reach_seeds_kernel.hip reach_seeds_obstacle_kernel.hip clearance_kernel.hip clearance_mesh_kernel.hip clearance_obstacle_kernel.hip certify_kernel.hip certify_mesh_kernel.hip certify_obstacle_kernel.hip qpid_kernel.hip dynamics.hip order_kernel.hip api.cpp model.cpp mesh.cpp; do
   XF=""
   [ "$src" = api.cpp ] && XF="-DDRC_BUILD_ID=\"$BUILD_ID\""
   $HIPCC $FLAGS $XF -c $CSRC/$src -o "$OBJ/${src%.*}.o" &
@@ -34,10 +34,11 @@ rc=0
 for p in "${pids[@]}"; do wait "$p" || rc=1; done
 [ $rc -eq 0 ] || { echo "build.sh: a HIP translation unit failed to compile" >&2; exit 1; }
 # (the reach seeds units are linked last: DESIGN.md "Reach seeds", headline; then the dense QP reference unit,
-# then the moving-obstacle units, then the path-clearance units)
+# then the moving-obstacle units, then the path-clearance units, then the certified-clearance units)
 $HIPCC --offload-arch=gfx950 -shared -fPIC "$OBJ"/task_kernel.o "$OBJ"/task_obstacle_kernel.o "$OBJ"/qp_kernel.o "$OBJ"/fused_kernel.o "$OBJ"/fused_mesh_kernel.o "$OBJ"/fused_obstacle_kernel.o "$OBJ"/rollout_kernel.o "$OBJ"/rollout_mesh_kernel.o "$OBJ"/reach_kernel.o "$OBJ"/reach_path_kernel.o "$OBJ"/reach_path_obstacle_kernel.o "$OBJ"/qpid_kernel.o \
   "$OBJ"/dynamics.o "$OBJ"/order_kernel.o "$OBJ"/api.o "$OBJ"/model.o "$OBJ"/mesh.o "$OBJ"/reach_seeds_kernel.o "$OBJ"/reach_seeds_obstacle_kernel.o "$OBJ"/qp_dense_kernel.o "$OBJ"/task_rate_kernel.o "$OBJ"/fused_rate_kernel.o \
-  "$OBJ"/clearance_kernel.o "$OBJ"/clearance_mesh_kernel.o "$OBJ"/clearance_obstacle_kernel.o -o "$OUT" -Wl,-rpath,/opt/rocm/lib
+  "$OBJ"/clearance_kernel.o "$OBJ"/clearance_mesh_kernel.o "$OBJ"/clearance_obstacle_kernel.o \
+  "$OBJ"/certify_kernel.o "$OBJ"/certify_mesh_kernel.o "$OBJ"/certify_obstacle_kernel.o -o "$OUT" -Wl,-rpath,/opt/rocm/lib
 [ -n "$DRC_VARIANT" ] && exit 0
 # test-only: the narrow-phase device code on one wave per pair (tests/test_gpu_narrow.py,
 # and the hull narrow phase: tests/test_gpu_mesh_narrow.py)

@@ -524,6 +524,77 @@ def clearance_path_batch(model, q_path, substeps=1, d_stop=None, obstacle_pose=N
     return res
 
 
+class CertifyResult:
+    """Device tensors of one ``drc_clearance_certify_batch`` call, one entry per
+    path: ``result`` [B] (FREE / BLOCKED / INVALID / UNDECIDED), ``seg_stop``,
+    ``t_stop`` [B] (-1 when FREE), ``d_min``, ``seg_min``, ``t_min``,
+    ``pair_min`` [B], ``d_lower`` [B] (the certified lower bound of the
+    continuous path when FREE), ``samples_used`` [B], and ``motion_bound``
+    [waypoints - 1][B] when asked for (None otherwise; segments that were not
+    started hold what the tensor held before the call)."""
+    FREE, BLOCKED, INVALID, UNDECIDED = _capi.CLEAR_FREE, _capi.CLEAR_BLOCKED, _capi.CLEAR_INVALID, _capi.CLEAR_UNDECIDED
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def clearance_certify_batch(model, q_path, d_stop=0.0, max_depth=8, obstacle_pose=None, motion_bound=False,
+                            stream=None):
+    """Launch ``drc_clearance_certify_batch`` on a device tensor ``q_path``
+    [waypoints][dof][B]: the continuous check of each path against ``d_stop``
+    by adaptive bisection down to ``max_depth`` (include/drc_amd.h states the
+    rule).  ``obstacle_pose`` [n][12] or [n][12][B] (see obstacle_poses):
+    ``drc_clearance_certify_obstacles_batch``.  ``motion_bound``: True allocates
+    the [waypoints - 1][B] bounds (zeros), a tensor of that shape is filled in
+    place."""
+    torch = _torch()
+    dev = q_path.device
+    nv = model.dof
+    if q_path.dim() != 3 or q_path.shape[1] != nv or q_path.dtype != torch.float64 or not q_path.is_contiguous():
+        raise ValueError("q_path must be a contiguous float64 [waypoints][%d][B] tensor, got %s"
+                         % (nv, tuple(q_path.shape)))
+    W, B = int(q_path.shape[0]), int(q_path.shape[2])
+    if isinstance(motion_bound, torch.Tensor):
+        if tuple(motion_bound.shape) != (W - 1, B) or motion_bound.dtype != torch.float64 \
+                or not motion_bound.is_contiguous():
+            raise ValueError("motion_bound must be a contiguous float64 [waypoints - 1 = %d][B = %d] tensor, got %s"
+                             % (W - 1, B, tuple(motion_bound.shape)))
+        mb = motion_bound
+    else:
+        mb = torch.zeros((max(W - 1, 0), B), dtype=torch.float64, device=dev) if motion_bound else None
+    i = lambda: torch.empty(B, dtype=torch.int32, device=dev)
+    d = lambda: torch.empty(B, dtype=torch.float64, device=dev)
+    res = CertifyResult(result=i(), seg_stop=i(), t_stop=d(), d_min=d(), seg_min=i(), t_min=d(), pair_min=i(),
+                        d_lower=d(), samples_used=i(), motion_bound=mb)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    head = (model.handle, C.c_int64(B), C.c_int(W), C.c_double(d_stop), C.c_int(int(max_depth)), _ptr(q_path))
+    tail = (_ptr(res.result), _ptr(res.seg_stop), _ptr(res.t_stop), _ptr(res.d_min), _ptr(res.seg_min),
+            _ptr(res.t_min), _ptr(res.pair_min), _ptr(res.d_lower), _ptr(res.samples_used), _ptr(res.motion_bound),
+            C.c_void_p(stream))
+    if obstacle_pose is not None:
+        op, ld, _ = obstacle_poses(model, obstacle_pose, B, dev)
+        _capi.check(_capi.lib().drc_clearance_certify_obstacles_batch(*head, _ptr(op), C.c_int64(ld), *tail))
+    else:
+        _capi.check(_capi.lib().drc_clearance_certify_batch(*head, *tail))
+    return res
+
+
+def motion_weights(model):
+    """``drc_model_motion_weights``: (rho [dof][n_geoms], wt [dof][n_pairs],
+    travel_mask) of the model as it stands (obstacle slots included), numpy."""
+    dof, ngeom, npairs = C.c_int(), C.c_int(), C.c_int()
+    _capi.check(_capi.lib().drc_model_info(model.handle, C.byref(dof), None, None, None, C.byref(ngeom),
+                                           C.byref(npairs)))
+    rho = np.zeros((dof.value, ngeom.value), dtype=np.float64)
+    wt = np.zeros((dof.value, npairs.value), dtype=np.float64)
+    mask = C.c_uint32()
+    dp = C.POINTER(C.c_double)
+    _capi.check(_capi.lib().drc_model_motion_weights(model.handle, rho.ctypes.data_as(dp), wt.ctypes.data_as(dp),
+                                                     C.byref(mask)))
+    return rho, wt, mask.value
+
+
 def clearance_grid(model):
     """``drc_debug_clearance_grid``: the waves of the model's last clearance launch (0: none yet)."""
     g = C.c_int64()

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "drc_qpik_reach_seeds_batch", "drc_qpik_reach_seeds_obstacles_batch",
     "drc_clearance_path_batch", "drc_clearance_path_obstacles_batch", "drc_clearance_path_host",
     "drc_debug_clearance_grid",
+    "drc_clearance_certify_batch", "drc_clearance_certify_obstacles_batch", "drc_model_motion_weights",
 )
 # the goal-reaching rollouts (absent from older A/B builds)
 REACH_SYMBOLS = ("drc_qpik_reach_batch", "drc_qpik_reach_obstacles_batch", "drc_reach_thresholds")
@@ -67,6 +68,9 @@ REACH_SEEDS_SYMBOLS = ("drc_qpik_reach_seeds_batch", "drc_qpik_reach_seeds_obsta
 CLEARANCE_SYMBOLS = ("drc_clearance_path_batch", "drc_clearance_path_obstacles_batch", "drc_clearance_path_host",
                      "drc_debug_clearance_grid")
 CLEAR_FREE, CLEAR_BLOCKED, CLEAR_INVALID = 0, 1, 2
+# certified path clearance (absent from older A/B builds), its verdict and its depth limit
+CERTIFY_SYMBOLS = ("drc_clearance_certify_batch", "drc_clearance_certify_obstacles_batch", "drc_model_motion_weights")
+CLEAR_UNDECIDED, CERTIFY_MAX_DEPTH = 3, 20
 # the dense reference build of the manipulator QP kernels (absent from older A/B builds)
 QP_DENSE_SYMBOLS = ("drc_debug_qp_dense", "drc_debug_qp_dense_launches")
 # drc_qpik_reach_batch's result codes
@@ -229,6 +233,13 @@ def _load():
         lib.drc_clearance_path_host.argtypes = [vp, C.c_int64, C.c_int, C.c_int, C.c_double, dp,
                                                 ip, ip, dp, ip, ip, dp]
         lib.drc_debug_clearance_grid.argtypes = [vp, C.POINTER(C.c_int64)]
+    if hasattr(lib, "drc_clearance_certify_batch"):  # certified clearance: absent from older A/B builds
+        lib.drc_clearance_certify_batch.argtypes = [vp, C.c_int64, C.c_int, C.c_double, C.c_int, vp,
+                                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.drc_clearance_certify_obstacles_batch.argtypes = [vp, C.c_int64, C.c_int, C.c_double, C.c_int, vp,
+                                                              vp, C.c_int64,
+                                                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.drc_model_motion_weights.argtypes = [vp, dp, dp, C.POINTER(C.c_uint32)]
     lib.drc_debug_kernel_timing.argtypes = [vp, C.c_int]
     # diagnostics added in r05: bound only when present, so A/B runs can load
     # an older build (tests/test_capi_symbols.py checks the product exports them)
@@ -278,7 +289,7 @@ def _load():
         if name in ("drc_debug_lds_plan", "drc_debug_waves", "drc_debug_host_timeline",
                     "drc_debug_qpik_stamps", "drc_debug_instance_order", "drc_model_geom_info", "drc_debug_task_plan_wide",
                     "drc_mesh_convex_hull", "drc_qpik_rollout_batch") + OBSTACLE_SYMBOLS + MOVING_OBSTACLE_SYMBOLS + REACH_SYMBOLS + REACH_PATH_SYMBOLS \
-                + REACH_SEEDS_SYMBOLS + QP_DENSE_SYMBOLS + CLEARANCE_SYMBOLS \
+                + REACH_SEEDS_SYMBOLS + QP_DENSE_SYMBOLS + CLEARANCE_SYMBOLS + CERTIFY_SYMBOLS \
                 and not hasattr(lib, name):
             continue  # diagnostics an older A/B build may lack
         if name not in ("drc_model_destroy", "drc_error_string", "drc_last_error", "drc_build_id"):

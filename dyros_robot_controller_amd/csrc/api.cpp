@@ -21,6 +21,7 @@
 #include "../../include/drc_amd_debug.h"
 #include "call_plan.hpp"
 #include "clearance.hpp"
+#include "clearance_certify.hpp"
 #include "dynamics.hpp"
 #include "host_staging.hpp"
 #include "kernel_common.hpp"
@@ -100,6 +101,7 @@ struct drc_model_impl {
   DevModel* d_model = nullptr;
   double* d_mesh = nullptr;  // hull vertices of the collision meshes (DevModel::mesh_verts)
   double* d_pair_tab = nullptr;  // per-pair records of the task stage (DevModel::pair_tab)
+  double* d_motion_wt = nullptr;  // motion weights of the certified clearance (DevModel::motion_wt)
   int device = 0;
   drc_kinematic_param kparam{};
   drc_joint_index jidx{};
@@ -515,6 +517,14 @@ static int upload(drc_model_impl* m) {
     HIP_TRY(hipMalloc(&m->d_pair_tab, bytes));
     HIP_TRY(hipMemcpy(m->d_pair_tab, m->hm.pair_tab.data(), bytes, hipMemcpyHostToDevice));
     m->hm.dev.pair_tab = m->d_pair_tab;
+  }
+  {  // the certified clearance's motion weights (model.cpp build_motion_tables)
+    const size_t bytes = m->hm.motion_wt.size() * sizeof(double);
+    if (m->d_motion_wt) HIP_TRY(hipFree(m->d_motion_wt));  // a re-upload (drc_model_set_obstacles)
+    m->d_motion_wt = nullptr;
+    HIP_TRY(hipMalloc(&m->d_motion_wt, bytes));
+    HIP_TRY(hipMemcpy(m->d_motion_wt, m->hm.motion_wt.data(), bytes, hipMemcpyHostToDevice));
+    m->hm.dev.motion_wt = m->d_motion_wt;
   }
   if (!m->d_model) HIP_TRY(hipMalloc(&m->d_model, sizeof(DevModel)));
   HIP_TRY(hipMemcpy(m->d_model, &m->hm.dev, sizeof(DevModel), hipMemcpyHostToDevice));
@@ -1341,6 +1351,58 @@ static int clearance(const drc_model_impl* cm, const drc_qpik_params* params, in
   return L.done();
 }
 
+// --------------------------------------------------------------------------
+// Certified path clearance (drc_clearance_certify_batch): one launch of the
+// persistent certify kernel (certify_kernel.hip), prepared as clearance() is;
+// the grid is the clearance kernel's
+// --------------------------------------------------------------------------
+static_assert(kClearUndecided == DRC_CLEAR_UNDECIDED, "clearance_certify.hpp and drc_amd.h agree on the verdict");
+static_assert(kCertMaxDepth == DRC_CERTIFY_MAX_DEPTH, "clearance_certify.hpp and drc_amd.h agree on the depth");
+static const char kSlotsCertifyMsg[] =
+    "the model has obstacle slots: pass their poses through drc_clearance_certify_obstacles_batch";
+
+static int certify(const drc_model_impl* cm, const drc_qpik_params* params, int64_t B, int waypoints, double d_stop,
+                   int max_depth, const double* q_path, int32_t* result, int32_t* seg_stop, double* t_stop,
+                   double* d_min, int32_t* seg_min, double* t_min, int32_t* pair_min, double* d_lower,
+                   int32_t* samples_used, double* motion_bound, void* stream, StageIn si = {}) {
+  drc_model_impl* m = const_cast<drc_model_impl*>(cm);
+  if (!m || !params) return set_err(DRC_ERR_INVALID_ARGUMENT, "null model/params");
+  std::lock_guard<std::mutex> launch_lock(m->launch_mu);
+  if (int rc = check_batch(B)) return rc;
+  if (int r = check_slots(m, &si, kSlotsCertifyMsg, "drc_clearance_certify_batch")) return r;
+  if (int r = check_obstacle_pose(si, B, "the batch")) return r;
+  if (waypoints < 1) return set_err(DRC_ERR_INVALID_ARGUMENT, "waypoints must be at least 1");
+  if (max_depth < 0 || max_depth > kCertMaxDepth)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "max_depth must be in 0 .. " + std::to_string(kCertMaxDepth));
+  if (d_stop != d_stop) return set_err(DRC_ERR_INVALID_ARGUMENT, "d_stop is NaN (-INFINITY certifies every segment at depth 0)");
+  if (certify_max_samples(waypoints, max_depth) > 0x7fffffff)
+    return set_err(DRC_ERR_INVALID_ARGUMENT, "(waypoints - 1) 2^max_depth + 1 evaluations do not fit 31 bits");
+  if (m->hm.motion_unbounded)
+    return set_err(DRC_ERR_UNSUPPORTED,
+                   "a prismatic joint below a revolute one has no finite limit: the motion weights are unbounded");
+  if (B == 0) return DRC_OK;
+  if (!q_path || !result || !seg_stop || !t_stop || !d_min || !seg_min || !t_min || !pair_min || !d_lower ||
+      !samples_used)
+    return set_err(DRC_ERR_INVALID_ARGUMENT,
+                   "q_path, result, seg_stop, t_stop, d_min, seg_min, t_min, pair_min, d_lower and samples_used are required");
+  KParams kt;
+  if (int rc = make_kparams(m, params, 1, &kt)) return rc;
+  Launch L(m, stream);
+  if (int r = L.begin()) return r;
+  hipStream_t st = L.st;
+  IO io = make_io(B);
+  kt.xcd_map = xcd_map_for(B);
+  HIP_TRY(hipMemsetAsync(L.cx->d_queue, 0, StreamCtx::kSlotInts * sizeof(int), st));
+  io.queue = L.cx->d_queue + StreamCtx::kSlotTask;
+  const CertArgs ca{waypoints, max_depth, d_stop,   q_path,  result,       seg_stop,    t_stop, d_min,
+                    seg_min,   t_min,     pair_min, d_lower, samples_used, motion_bound};
+  const unsigned grid = static_cast<unsigned>(clearance_grid(B, plan_knobs()));
+  HIP_TRY(static_cast<hipError_t>(launch_certify_kernel(
+      grid, static_cast<size_t>(kt.lds_doubles) * sizeof(double), st, m->d_model, kt, io, ca, si)));
+  m->clearance_grid_last = grid;
+  return L.done();
+}
+
 // QPID pipeline for one call: dynamics launch(es) -> task kernel (QPID stage
 // data into the records) -> QPID kernel; or, with stages, the task kernel
 // writing the stage outputs.  Model-owned scratch holds the records and the
@@ -1811,6 +1873,7 @@ void drc_model_destroy(drc_model* m) {
   if (m->d_model) (void)hipFree(m->d_model);
   if (m->d_mesh) (void)hipFree(m->d_mesh);
   if (m->d_pair_tab) (void)hipFree(m->d_pair_tab);
+  if (m->d_motion_wt) (void)hipFree(m->d_motion_wt);
   if (m->d_order) (void)hipFree(m->d_order);
   if (m->hstream) (void)hipStreamSynchronize(m->hstream), (void)hipStreamDestroy(m->hstream);
   if (m->stage) (void)hipFree(m->stage);
@@ -1849,6 +1912,19 @@ int drc_model_geom_info(const drc_model* m, int geom, int* type, double param[3]
   const bool urdf_geom = geom < static_cast<int>(m->hm.mesh_count.size());  // (obstacle slots: primitives)
   if (n_vertices) *n_vertices = urdf_geom ? m->hm.mesh_count[geom] : 0;
   if (hull_residual) *hull_residual = urdf_geom ? m->hm.mesh_residual[geom] : 0.0;
+  return DRC_OK;
+}
+
+int drc_model_motion_weights(const drc_model* m, double* rho, double* wt, uint32_t* travel_mask) {
+  if (!m) return drc_amd::set_err(DRC_ERR_INVALID_ARGUMENT, "null model");
+  const drc_amd::DevModel& d = m->hm.dev;
+  if (rho)
+    for (int i = 0; i < d.nv * d.ngeom; ++i) rho[i] = m->hm.motion_rho[i];
+  if (wt)
+    for (int j = 0; j < d.nv; ++j)
+      for (int p = 0; p < d.npairs; ++p)
+        wt[static_cast<size_t>(j) * d.npairs + p] = m->hm.motion_wt[static_cast<size_t>(j) * d.motion_ld + p];
+  if (travel_mask) *travel_mask = d.travel_mask;
   return DRC_OK;
 }
 
@@ -2248,6 +2324,28 @@ int drc_clearance_path_obstacles_batch(const drc_model* m, int64_t B, int waypoi
   if (int rc = clearance_params(m, &pp)) return rc;
   return drc_amd::clearance(m, &pp, B, waypoints, substeps, d_stop, q_path, result, sample_stop, d_min, sample_min,
                             pair_min, dist_traj, stream, drc_amd::stage_in(obstacle_pose, obstacle_ld));
+}
+
+int drc_clearance_certify_batch(const drc_model* m, int64_t B, int waypoints, double d_stop, int max_depth,
+                                const double* q_path, int32_t* result, int32_t* seg_stop, double* t_stop,
+                                double* d_min, int32_t* seg_min, double* t_min, int32_t* pair_min, double* d_lower,
+                                int32_t* samples_used, double* motion_bound, void* stream) {
+  drc_qpik_params pp;
+  if (int rc = clearance_params(m, &pp)) return rc;
+  return drc_amd::certify(m, &pp, B, waypoints, d_stop, max_depth, q_path, result, seg_stop, t_stop, d_min, seg_min,
+                          t_min, pair_min, d_lower, samples_used, motion_bound, stream);
+}
+
+int drc_clearance_certify_obstacles_batch(const drc_model* m, int64_t B, int waypoints, double d_stop, int max_depth,
+                                          const double* q_path, const double* obstacle_pose, int64_t obstacle_ld,
+                                          int32_t* result, int32_t* seg_stop, double* t_stop, double* d_min,
+                                          int32_t* seg_min, double* t_min, int32_t* pair_min, double* d_lower,
+                                          int32_t* samples_used, double* motion_bound, void* stream) {
+  drc_qpik_params pp;
+  if (int rc = clearance_params(m, &pp)) return rc;
+  return drc_amd::certify(m, &pp, B, waypoints, d_stop, max_depth, q_path, result, seg_stop, t_stop, d_min, seg_min,
+                          t_min, pair_min, d_lower, samples_used, motion_bound, stream,
+                          drc_amd::stage_in(obstacle_pose, obstacle_ld));
 }
 
 // ---- QPID -------------------------------------------------

@@ -141,6 +141,30 @@ struct ClearArgs {
 int launch_clearance_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
                             const IO& io, const ClearArgs& ca, const StageIn& si);
 
+// drc_clearance_certify_batch (certify_kernel.hip): what its kernel takes beyond
+// IO, as an argument of its own, as ClearArgs is.  q_path [waypoints][dof][ld];
+// every output [B]; motion_bound [waypoints - 1][ld] or NULL
+struct CertArgs {
+  int waypoints, max_depth;
+  double d_stop;
+  const double* q_path;
+  int32_t *result, *seg_stop;
+  double *t_stop, *d_min;
+  int32_t* seg_min;
+  double* t_min;
+  int32_t* pair_min;
+  double* d_lower;
+  int32_t* samples_used;
+  double* motion_bound;
+};
+// persistent certify kernel (the Plain, Mesh and Obst builds, as the clearance
+// kernel's; hipErrorInvalidValue for Rate): one path per wave from the work
+// queue io.queue, the distance stage on the states that the fold of
+// clearance_certify.hpp asks for.  kp: the task plan (lds its bytes); of io it
+// reads B, b0, ld and queue; the model's motion_wt must be uploaded
+int launch_certify_kernel(unsigned grid, size_t lds, hipStream_t st, const DevModel* m, const KParams& kp,
+                          const IO& io, const CertArgs& ca, const StageIn& si);
+
 // queue order of one sub-batch (order_kernel.hip): penetration-prone
 // instances first (*hot_n zeroed; hot_list [B], hot_flag [B] scratch), then the
 // others in index order, into order[b0 .. b0 + B)

@@ -518,6 +518,7 @@ int build_model_from_urdf(const std::string& urdf_path, const std::string& srdf_
   m.nobst = 0;
   m.obst0 = m.ngeom;
   build_pair_tables(out);
+  build_motion_tables(out);
   return DRC_OK;
 }
 
@@ -656,7 +657,57 @@ int set_obstacles(HostModel* hm, int n, const int* type, const double* param, co
     }
   }
   build_pair_tables(hm);
+  build_motion_tables(hm);
   return DRC_OK;
+}
+
+void build_motion_tables(HostModel* hm) {
+  DevModel& m = hm->dev;
+  const int nv = m.nv;
+  auto norm3 = [](const double* p) { return std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]); };
+  auto travel = [&](int k) { return std::max(std::fabs(m.lower[k - 1]), std::fabs(m.upper[k - 1])); };
+  hm->motion_rho.assign(static_cast<size_t>(std::max(nv * m.ngeom, 1)), 0.0);
+  for (int g = 0; g < m.ngeom; ++g) {
+    const int c = m.gparent[g];
+    if (c <= 0) continue;  // fixed links and obstacle slots do not move with q
+    const double* pr = m.gparam[g];
+    double rad = 0.0;
+    switch (m.gtype[g]) {
+      case kSphere: rad = pr[0]; break;
+      case kCylinder: rad = std::sqrt(pr[0] * pr[0] + pr[1] * pr[1]); break;
+      default: rad = norm3(pr); break;  // box, hull: the half extents
+    }
+    // up the chain from c: `below` is the sum over the joints strictly below j
+    double below = 0.0;
+    for (int j = c; j > 0; j = m.parent[j]) {
+      hm->motion_rho[static_cast<size_t>(j - 1) * m.ngeom + g] = below + norm3(m.gplace[g] + 9) + rad;
+      below += norm3(m.jplace[j] + 9) + (m.jtype[j] == kPrismatic ? travel(j) : 0.0);
+    }
+  }
+  m.travel_mask = 0;
+  hm->motion_unbounded = false;
+  for (int k = 1; k <= nv; ++k) {
+    if (m.jtype[k] != kPrismatic) continue;
+    bool rev_above = false, geom_below = false;
+    for (int j = m.parent[k]; j > 0; j = m.parent[j]) rev_above |= m.jtype[j] == kRevolute;
+    for (int g = 0; g < m.ngeom; ++g) geom_below |= m.gparent[g] > 0 && (m.anc[m.gparent[g]] >> (k - 1) & 1u) != 0;
+    if (!rev_above || !geom_below) continue;
+    m.travel_mask |= 1u << (k - 1);
+    if (!std::isfinite(travel(k))) hm->motion_unbounded = true;
+  }
+  m.motion_ld = m.pair_ld;
+  m.motion_wt = nullptr;  // (the device buffer: the caller uploads the table)
+  hm->motion_wt.assign(static_cast<size_t>(std::max(nv, 1)) * std::max(m.motion_ld, 1), 0.0);
+  for (int p = 0; p < m.npairs; ++p) {
+    const int ga = m.pair_a[p], gb = m.pair_b[p];
+    const uint32_t sa = m.gparent[ga] > 0 ? m.anc[m.gparent[ga]] : 0u, sb = m.gparent[gb] > 0 ? m.anc[m.gparent[gb]] : 0u;
+    for (int j = 1; j <= nv; ++j) {
+      const bool ia = (sa >> (j - 1) & 1u) != 0, ib = (sb >> (j - 1) & 1u) != 0;
+      if (ia == ib) continue;  // moves both alike, or neither
+      hm->motion_wt[static_cast<size_t>(j - 1) * m.motion_ld + p] =
+          m.jtype[j] == kPrismatic ? 1.0 : hm->motion_rho[static_cast<size_t>(j - 1) * m.ngeom + (ia ? ga : gb)];
+    }
+  }
 }
 
 void build_stage_tables(HostModel* hm) {

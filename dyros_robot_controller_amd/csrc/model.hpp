@@ -78,6 +78,14 @@ struct DevModel {
   // geometries [obst0, obst0 + nobst) have parent 0 and a pose that is an input
   // of each call, not gplace (which holds the identity)
   int nobst, obst0;
+  // motion weights of the certified path clearance (build_motion_tables;
+  // appended): weight of joint j (1-based) on pair p at
+  // motion_wt[(j - 1) * motion_ld + p], the bound on the pair's relative motion
+  // per unit of |dq_j| (clearance_certify.hpp); travel_mask: bit (k-1) set iff
+  // the weights assume |q_k| <= max(|lower_k|, |upper_k|) of the prismatic joint k
+  const double* motion_wt;         // device buffer [nv][motion_ld] (model-owned)
+  int motion_ld;
+  uint32_t travel_mask;
 };
 constexpr int kPairFields = 9;
 constexpr int kPairMeta = 0, kPairParamA = 1, kPairParamB = 4, kPairBoundA = 7, kPairBoundB = 8;
@@ -98,6 +106,9 @@ struct HostModel {
   std::vector<double> pair_tab;             // DevModel::pair_tab, [kPairFields][dev.pair_ld]
   std::vector<std::string> geom_link;       // per geometry of the URDF: its link
   int base_pairs = 0;                       // pairs of the URDF / SRDF (the obstacle pairs follow them)
+  std::vector<double> motion_rho;           // [nv][ngeom]: reach of geometry g about joint j's origin (build_motion_tables)
+  std::vector<double> motion_wt;            // DevModel::motion_wt, [nv][dev.motion_ld]
+  bool motion_unbounded = false;            // a joint of travel_mask has a non-finite limit: no certificate
   bool has_mesh() const { return !mesh_verts.empty(); }
 };
 
@@ -112,6 +123,17 @@ void build_stage_tables(HostModel* hm);
 // from the geometry and pair arrays (called by build_model_from_urdf and
 // set_obstacles).
 void build_pair_tables(HostModel* hm);
+// Fills motion_rho, motion_wt, motion_ld, travel_mask and motion_unbounded from
+// the kinematic tree, the joint limits and the geometry and pair arrays (called
+// where build_pair_tables is: by build_model_from_urdf and set_obstacles).
+//   rad_g      bounding radius of geometry g about its frame origin, from gparam
+//   travel_k   max(|lower_k|, |upper_k|) of a prismatic joint k
+//   rho[j][g]  for j supporting g's parent joint c: the sum over the joints k of
+//              the chain strictly below j down to c of |p(jplace[k])| (+ travel_k,
+//              k prismatic), plus |p(gplace[g])| + rad_g; 0 otherwise
+//   wt[j][p]   0 if j supports both or neither geometry of pair p; otherwise 1
+//              (j prismatic) or rho[j][the supported one] (j revolute)
+void build_motion_tables(HostModel* hm);
 // Declares n obstacle slots (replacing any earlier ones; n = 0 removes them and
 // leaves the model what build_model_from_urdf made): geometries ngeom .. with
 // parent 0, identity placement, type[i] (kSphere, kCylinder, kBox, kHalfSpace)

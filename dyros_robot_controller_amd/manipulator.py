@@ -281,6 +281,16 @@ class RobotData:
         return _batch.clearance_path_batch(self.model, _batch.as_device(q_path, self.device), substeps=substeps,
                                            d_stop=d_stop, obstacle_pose=obstacle_pose, dist_traj=dist_traj)
 
+    def certify_path_batch(self, q_path, d_stop=0.0, max_depth=8, obstacle_pose=None, motion_bound=False):
+        """Certified path clearance on device tensors: the continuous check
+        of the joint-space paths ``q_path`` [waypoints][dof][B] against
+        ``d_stop`` by adaptive bisection down to ``max_depth``; FREE means that
+        every state of the motion has d >= d_lower >= d_stop.  Returns a
+        ``_batch.CertifyResult``; see _batch.clearance_certify_batch."""
+        return _batch.clearance_certify_batch(self.model, _batch.as_device(q_path, self.device), d_stop=d_stop,
+                                              max_depth=max_depth, obstacle_pose=obstacle_pose,
+                                              motion_bound=motion_bound)
+
     get_mass_matrix, get_mass_matrix_inv, get_gravity = getMassMatrix, getMassMatrixInv, getGravity
     get_coriolis, get_nonlinear_effects = getCoriolis, getNonlinearEffects
     compute_mass_matrix, compute_gravity = computeMassMatrix, computeGravity

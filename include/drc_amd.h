@@ -737,6 +737,107 @@ int drc_clearance_path_host(drc_model* model, int64_t B, int waypoints, int subs
                             double* d_min, int32_t* sample_min, int32_t* pair_min,
                             double* dist_traj);
 
+/* ---- certified path clearance: the continuous check of joint-space paths ------
+ * drc_clearance_path_batch's FREE speaks of its samples.  This entry's FREE
+ * speaks of the motion: every state of every straight segment between
+ * consecutive waypoints of q_path [waypoints][dof][B] has d >= d_lower >=
+ * d_stop.  It evaluates the distance stage where the path is close to
+ * something and nowhere else (adaptive bisection, after Schwarzer, Saha and
+ * Latombe); d and pair at a state are bit for bit dist[0] and pair of
+ * drc_qpik_stages_batch, as for drc_clearance_path_batch.
+ *
+ * The model's motion weights (drc_model_motion_weights) bound how far a pair's
+ * two geometries move against each other per unit of joint motion; the signed
+ * distance of two convex bodies is 1-Lipschitz in that motion, on both sides of
+ * contact.  Per segment j (waypoint j -> j + 1, ends qa, qb):
+ *   M_j = max over the pairs p of  sum_{i = 1 .. dof} Wt[i][p] |qb_i - qa_i|,
+ * the sum in ascending i, the difference, each product and each sum rounded
+ * once, the max exact.  Positions on a segment are t = k / 2^e, e <= max_depth;
+ * the state there is that of sample k of drc_clearance_path_batch with
+ * substeps = 2^e (waypoint j + 1 itself at t = 1, waypoint j at t = 0).
+ * The walk, left to right and depth first:
+ *   1. d_min = d_lower = +inf, seg_min = pair_min = seg_stop = -1,
+ *      t_min = t_stop = -1, samples_used = 0.  Waypoint 0 is evaluated
+ *      (segment 0, t = 0).  A path of one waypoint ends here, FREE.
+ *   2. Start of segment j: if a coordinate k of travel_mask has
+ *      !(max(|qa_k|, |qb_k|) <= travel_k): DRC_CLEAR_UNDECIDED,
+ *      (seg_stop, t_stop) = (j, 0), stop.  Then t = 1 is evaluated; t = 0 is
+ *      the previous segment's end.
+ *   3. Every evaluated sample (d, pair) at (j, t) counts in samples_used, then
+ *        d NaN:       DRC_CLEAR_INVALID, (seg_stop, t_stop) = (j, t), stop;
+ *        d < d_min:   (d_min, seg_min, t_min, pair_min) = (d, j, t, pair) --
+ *                     strict: the first evaluated wins a tie;
+ *        d < d_stop:  DRC_CLEAR_BLOCKED, (seg_stop, t_stop) = (j, t), stop.
+ *   4. Interval [t0, t1] at depth e (t1 - t0 = 2^-e), end distances d0, d1:
+ *        lb = 0.5 (d0 + d1) - (0.5 (t1 - t0)) M_j, each operation rounded;
+ *        lb >= d_stop:    certified: d_lower = min(d_lower, lb), on to the
+ *                         next pending interval;
+ *        e == max_depth:  DRC_CLEAR_UNDECIDED, (seg_stop, t_stop) = (j, t0), stop;
+ *        otherwise the midpoint is evaluated, then the left half is treated,
+ *        then the right half.
+ *   5. After the last segment: DRC_CLEAR_FREE.
+ * d_stop = -INFINITY certifies every interval at depth 0; +INFINITY blocks at
+ * the first sample that is not +inf.  max_depth is 0 .. DRC_CERTIFY_MAX_DEPTH;
+ * a path takes at most (waypoints - 1) 2^max_depth + 1 evaluations, which must
+ * stay below 2^31.  motion_bound [waypoints - 1][B] (may be NULL) receives M_j
+ * of the segments that were started.
+ * What is certified is the model the distance stage sees: hull models are
+ * certified against their hulls, and the 256-vertex cap is an inner
+ * approximation whose residual drc_model_geom_info reports.  A penetration
+ * depth (d < 0) carries EPA's 1e-6; a separated distance the stage's 1e-9.
+ * The bound uses the path's minimum distance with the largest pair weight,
+ * which is conservative; obstacle slots are static for the call.
+ * One persistent kernel, one path per wave, asynchronous on `stream`.
+ * DRC_ERR_INVALID_ARGUMENT: as drc_clearance_path_batch (waypoints < 1, d_stop
+ * NaN, B, a NULL among q_path and the outputs other than motion_bound, a model
+ * with slots), max_depth outside its range, too many evaluations.
+ * DRC_ERR_UNSUPPORTED: a prismatic joint of travel_mask has no finite limit.
+ * B = 0: DRC_OK, nothing is touched. */
+enum {
+    DRC_CLEAR_UNDECIDED = 3,     /* not certified within max_depth, or out of the travel */
+    DRC_CERTIFY_MAX_DEPTH = 20
+};
+int drc_clearance_certify_batch(const drc_model* model, int64_t B, int waypoints, double d_stop,
+                                int max_depth, const double* q_path,
+                                int32_t* result, int32_t* seg_stop, double* t_stop,
+                                double* d_min, int32_t* seg_min, double* t_min, int32_t* pair_min,
+                                double* d_lower, int32_t* samples_used, double* motion_bound,
+                                void* stream);
+
+/* drc_clearance_certify_batch on a model with obstacle slots: obstacle_pose and
+ * obstacle_ld as for drc_clearance_path_obstacles_batch.  A pair with a slot
+ * weighs the robot's side only.  DRC_ERR_INVALID_ARGUMENT on a model without
+ * slots (drc_clearance_certify_batch runs it). */
+int drc_clearance_certify_obstacles_batch(const drc_model* model, int64_t B, int waypoints,
+                                          double d_stop, int max_depth, const double* q_path,
+                                          const double* obstacle_pose, int64_t obstacle_ld,
+                                          int32_t* result, int32_t* seg_stop, double* t_stop,
+                                          double* d_min, int32_t* seg_min, double* t_min,
+                                          int32_t* pair_min, double* d_lower,
+                                          int32_t* samples_used, double* motion_bound,
+                                          void* stream);
+
+/* The motion weights behind drc_clearance_certify_batch (host only).
+ *   rad_g      bounding radius of geometry g about its own frame origin:
+ *              sphere r, cylinder sqrt(r^2 + (h/2)^2), box and hull the norm
+ *              of the half extents
+ *   travel_k   max(|lower_k|, |upper_k|) of a prismatic joint k
+ *   rho [dof][n_geoms]   rho[j][g], for a joint j that supports the joint c
+ *              carrying g: the sum of |p(placement of k)| (+ travel_k, k
+ *              prismatic) over the joints k strictly below j down to c, plus
+ *              |p(placement of g)| + rad_g -- no point of g is ever farther
+ *              from the origin of j's frame; 0 for every other j, and for
+ *              geometries that no joint moves (fixed links, obstacle slots)
+ *   wt [dof][n_pairs]    wt[j][p] = 0 if j supports both geometries of pair p
+ *              or neither; otherwise 1 (j prismatic) or rho[j][the supported
+ *              geometry] (j revolute)
+ *   *travel_mask  bit k - 1 set for each prismatic joint k that has a revolute
+ *              joint above it and geometry below: the weights hold while
+ *              |q_k| <= travel_k
+ * Outputs may be NULL. */
+int drc_model_motion_weights(const drc_model* model, double* rho, double* wt,
+                             uint32_t* travel_mask);
+
 /* Host-buffer forms of drc_qpik_batch / drc_qpik_stages_batch: same
  * arguments, but every array is a HOST array ([field][B], row stride B).  The
  * call stages them through model-owned device memory on an internal stream
